@@ -10,7 +10,11 @@ detections over RCCL (frames are sharded: rank r owns its own 16 frames).
 ``--workload e2e`` starts each step from raw point clouds (BEV voxelisation on
 the GPU as well).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+       A plain run sets up, warms up, times the K steps and prints the result line (headline
+       fields, ``ms_per_step``, the configuration).  ``--dump-outputs DIR`` also writes what the
+       last timed step computed (DIR/<name>.npy, float32).  ``--full`` adds everything that takes
+       runs of its own: the per-stage times, the roofline probes and the CPU baseline + parity leg.
        N > 1: either launched per rank by torch.distributed.run (RANK / WORLD_SIZE set), or
        self-launched: with WORLD_SIZE unset the process touches no GPU, starts N rank processes
        of itself (RANK, LOCAL_RANK, WORLD_SIZE, MASTER_ADDR=127.0.0.1, MASTER_PORT) and exits with
@@ -127,7 +131,17 @@ def parse(argv=None):
     ap.add_argument("--share-weights", action="store_true",
                     help="the in-flight pipelines share one device copy of the packed weights "
                          "(KfpnEngine.twin) instead of one copy each")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what takes runs of its own and add it "
+                         "to the line: stages_ms, roofline (heads probe, --probe-forwards), bev_roofline "
+                         "(e2e) and, at N = 1, cpu_baseline + parity (--no-cpu-baseline leaves them out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region rank 0 writes what the last timed step computed, as a "
+                         "caller of the timed path receives it: DIR/dets.npy (B, K, 10) and the head maps "
+                         "DIR/<head>.npy (fusion: the per-frame fused lists), float32; the inputs are "
+                         "seeded, so two builds can be compared output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline + parity leg")
     ap.add_argument("--serial-heads", action="store_true",
                     help="keep the level-0 heads on the main stream (no side stream) for the whole "
                          "run: with --inflight 1 every head launch then has the chip to itself, "
@@ -483,6 +497,34 @@ def dump_gathered(args, bench, rank, world):
                  side_streams=np.int64(bench.side))
 
 
+def write_outputs(directory, arrays):
+    """--dump-outputs: one float32 .npy per array (integer lists are cast)."""
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        total += a.nbytes
+        np.save(os.path.join(directory, name + ".npy"), a)
+    assert total <= 64 << 20, total
+
+
+def pipeline_outputs(pipe):
+    """What a DetectorPipeline step hands its caller: the (B, K, 10) detections and the head maps."""
+    out = {"dets": pipe.dets.cpu().numpy()}
+    for h, _ in pipe.engine.heads:
+        out[h] = pipe.outs[h].cpu().numpy()
+    return out
+
+
+def fusion_outputs(fp):
+    """FusionPipeline.results() of every frame as flat arrays + the per-frame list lengths."""
+    res = fp.results()
+    out = {"fused_count": np.array([len(r[0]) for r in res]), "keep_count": np.array([len(r[4]) for r in res])}
+    for j, name in enumerate(("fused_boxes", "fused_conf", "fused_cls", "fused_src", "nms_keep")):
+        out[name] = np.concatenate([np.asarray(r[j], dtype=np.float64).reshape(len(r[j]), -1) for r in res])
+    return out
+
+
 def _lib_sha256():
     import hashlib
     with open(_lib.LIB_PATH, "rb") as f:
@@ -801,6 +843,8 @@ def run_stream(args, rank, world, dev):
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:  # the pipeline that took the last timed batch
+            write_outputs(args.dump_outputs, pipeline_outputs(det.pipes[(args.steps - 1) % len(det.pipes)]))
         det.close()
         return elapsed, threads
     finally:
@@ -870,7 +914,10 @@ def run_fusion(args, rank, world, dev):
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    return time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, fusion_outputs(fps[(args.steps - 1) % nf]))
+    return elapsed
 
 
 def runtime_make_calib(c):
@@ -951,19 +998,29 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        last = (args.steps - 1) % nf  # the pipeline of the last timed step
+        arrays = pipeline_outputs(pipes[last])
+        if bench.gather:
+            arrays["gathered_dets"] = bench.last_gathered[last][0].cpu().numpy()
+            arrays["gathered_ids"] = bench.last_gathered[last][1].cpu().numpy()
+        write_outputs(args.dump_outputs, arrays)
     if args.dump_dets:
         dump_gathered(args, bench, rank, world)
-    if nf > 1:
+    if args.full and nf > 1:
         # per-stage times with one step in flight (the in-flight events overlap): a short
         # untimed-for-value pass on stream 0 only, for the roofline and stages_ms
         torch.cuda.synchronize()
         for k in range(args.steps):
             one_step(k * nf, ev[k])
         torch.cuda.synchronize()
-    fwd_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
-    dec_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
-    heads = probe_heads(args, pipes[0], steps[0]) if rank == 0 and args.probe_forwards > 0 else None
-    bev_roof = probe_bev(args, pipes[0]) if rank == 0 else None
+    fwd_ms = dec_ms = 0.0
+    heads = bev_roof = None
+    if args.full:
+        fwd_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
+        dec_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
+        heads = probe_heads(args, pipes[0], steps[0]) if rank == 0 and args.probe_forwards > 0 else None
+        bev_roof = probe_bev(args, pipes[0]) if rank == 0 else None
     if world > 1:
         t = torch.tensor([elapsed, fwd_ms, dec_ms], dtype=torch.float64,
                          device=dev if dist.get_backend() == "nccl" else "cpu")
@@ -972,17 +1029,6 @@ def main():
     frames = world * args.batch * args.steps
     value = frames / elapsed
     if rank == 0:
-        flop_step = CONV_FLOP_PER_FRAME * args.batch
-        # the forward's own event time with one step in flight (the conv launches + aux)
-        achieved = flop_step / (fwd_ms * 1e-3) / 1e12
-        peak, peak_basis = PEAKS[args.math]
-        capped = PEAKS_CAPPED.get(args.math)
-        forward_roofline = {
-            "scope": "the whole forward (22 implicit-GEMM launches + the stem + aux kernels), "
-                     "algorithmic f32 FLOP over its event time with one step in flight",
-            "achieved": round(achieved, 3), "frac": round(achieved / peak, 4),
-            "frac_of_power_capped": round(achieved / capped, 4) if capped else None,
-            "algorithmic_flop_per_step": flop_step}
         line = {
             "metric": METRIC,
             "value": round(value, 2),
@@ -1016,14 +1062,26 @@ def main():
                            if world > 1 else "simulated: device copy on a lazily created stream joined "
                            "like ProcessGroupNCCL's (--sim-gather)" if args.sim_gather else None),
             },
-            "stages_ms": {"forward": round(fwd_ms, 4), "decode": round(dec_ms, 4),
-                          "note": "one step in flight; value/ms_per_step use %d in flight" % nf},
-            "roofline": roofline_line(args, heads, forward_roofline, achieved, peak, peak_basis, capped),
         }
-        if bev_roof is not None:
-            line["bev_roofline"] = bev_roof
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"], line["parity"] = cpu_baseline(args, bench)
+        if args.full:
+            flop_step = CONV_FLOP_PER_FRAME * args.batch
+            # the forward's own event time with one step in flight (the conv launches + aux)
+            achieved = flop_step / (fwd_ms * 1e-3) / 1e12
+            peak, peak_basis = PEAKS[args.math]
+            capped = PEAKS_CAPPED.get(args.math)
+            forward_roofline = {
+                "scope": "the whole forward (22 implicit-GEMM launches + the stem + aux kernels), "
+                         "algorithmic f32 FLOP over its event time with one step in flight",
+                "achieved": round(achieved, 3), "frac": round(achieved / peak, 4),
+                "frac_of_power_capped": round(achieved / capped, 4) if capped else None,
+                "algorithmic_flop_per_step": flop_step}
+            line["stages_ms"] = {"forward": round(fwd_ms, 4), "decode": round(dec_ms, 4),
+                                 "note": "one step in flight; value/ms_per_step use %d in flight" % nf}
+            line["roofline"] = roofline_line(args, heads, forward_roofline, achieved, peak, peak_basis, capped)
+            if bev_roof is not None:
+                line["bev_roofline"] = bev_roof
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"], line["parity"] = cpu_baseline(args, bench)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

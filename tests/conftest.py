@@ -6,9 +6,11 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SFA_ROOT = os.path.join(REPO, "lidar-image_object-detection_-fpn_resnet-yolov8_amd", "sfa")
 GOLDEN = os.path.join(REPO, "tests", "golden")
-for p in (REPO, SFA_ROOT):
+for p in (REPO, SFA_ROOT, os.path.join(REPO, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
+
+import golden_io  # noqa: E402
 
 
 def pytest_configure(config):
@@ -25,31 +27,26 @@ def gpu_available():
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
-
     class G:
-        bev = np.load(os.path.join(GOLDEN, "bev_golden.npz"))
-        decode = np.load(os.path.join(GOLDEN, "decode_golden.npz"))
-        model = np.load(os.path.join(GOLDEN, "model_golden.npz"))
+        bev = golden_io.load(GOLDEN, "bev_golden")
+        decode = golden_io.load(GOLDEN, "decode_golden")
+        model = golden_io.load(GOLDEN, "model_golden")
     return G
 
 
 @pytest.fixture(scope="session")
 def golden_bench():
-    import numpy as np
-    return np.load(os.path.join(GOLDEN, "bench_golden.npz"))
+    return golden_io.load(GOLDEN, "bench_golden")
 
 
 @pytest.fixture(scope="session")
 def golden_fusion():
-    import numpy as np
-    return np.load(os.path.join(GOLDEN, "fusion_golden.npz"))
+    return golden_io.load(GOLDEN, "fusion_golden")
 
 
 @pytest.fixture(scope="session")
 def golden_gaussian_nms():
-    import numpy as np
-    return np.load(os.path.join(GOLDEN, "gaussian_nms_golden.npz"))
+    return golden_io.load(GOLDEN, "gaussian_nms_golden")
 
 
 def gaussian_nms_case_names(g):
@@ -58,14 +55,12 @@ def gaussian_nms_case_names(g):
 
 @pytest.fixture(scope="session")
 def golden_back():
-    import numpy as np
-    return np.load(os.path.join(GOLDEN, "back_golden.npz"))
+    return golden_io.load(GOLDEN, "back_golden")
 
 
 @pytest.fixture(scope="session")
 def golden_project():
-    import numpy as np
-    return np.load(os.path.join(GOLDEN, "project_golden.npz"))
+    return golden_io.load(GOLDEN, "project_golden")
 
 
 @pytest.fixture(scope="session")

@@ -65,7 +65,7 @@ def main():
     for j in range(3):
         res[f"detect/post{j}"] = post[0][j]
     print(f"back detect: dets {dets.shape}, post {[post[0][j].shape[0] for j in range(3)]}")
-    np.savez_compressed(os.path.join(HERE, "back_golden.npz"), **res)
+    gg.golden_io.save(HERE, "back_golden", res)
 
 
 if __name__ == "__main__":

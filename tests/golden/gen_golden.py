@@ -45,6 +45,8 @@ PKG = os.path.join(REPO, "lidar-image_object-detection_-fpn_resnet-yolov8_amd", 
 REF = "/root/reference"
 
 sys.path.insert(0, PKG)
+sys.path.insert(0, os.path.dirname(HERE))
+import golden_io  # noqa: E402
 from sfa_hip import synthetic  # noqa: E402
 
 HEADS = {"hm_cen": 3, "cen_offset": 2, "direction": 2, "z_coor": 1, "dim": 3}
@@ -144,7 +146,7 @@ def gen_bev(ref, out):
         if name in ("kat_edges", "single_point", "empty_after_filter"):
             res[f"{name}/cloud"] = cloud
         print(f"bev {name}: n={cloud.shape[0]} kept={filt.shape[0]} cells={nz.size}")
-    np.savez_compressed(os.path.join(out, "bev_golden.npz"), **res)
+    golden_io.save(out, "bev_golden", res)
 
 
 def _ref_model(ref, seed=0):
@@ -190,7 +192,7 @@ def gen_decode(ref, out):
         real = ref["ev"].convert_det_to_real_values(post[0])
         res[f"{case}/real"] = real
         print(f"decode {case}: dets {dets.shape}, post sizes {[post[0][j].shape[0] for j in range(3)]}")
-    np.savez_compressed(os.path.join(out, "decode_golden.npz"), **res)
+    golden_io.save(out, "decode_golden", res)
 
 
 def gen_model(ref, out):
@@ -238,7 +240,7 @@ def gen_model(ref, out):
         flat = np.sort(ref["ev"]._nms(hm).numpy().reshape(-1))[::-1][:51]
         res["e2e/top51"] = flat
         print(f"model e2e: dets {dets.shape}, min top-51 gap {np.min(-np.diff(flat)):.3g}")
-    np.savez_compressed(os.path.join(out, "model_golden.npz"), **res)
+    golden_io.save(out, "model_golden", res)
 
 
 def _frame_top51(ref, hm_sig):
@@ -300,7 +302,7 @@ def gen_bench(ref, out):
                 break
         else:
             raise SystemExit("no sweep seed in 2..39 gives a tie-free top-51")
-    np.savez_compressed(os.path.join(out, "bench_golden.npz"), **res)
+    golden_io.save(out, "bench_golden", res)
 
 
 def main():

@@ -54,7 +54,7 @@ def main():
 
     cals = project_cases.calibs()
     cases = project_cases.cases()
-    mg = np.load(os.path.join(HERE, "model_golden.npz"))
+    mg = gen_golden.golden_io.load(HERE, "model_golden")
     cases["e2e"] = (mg["e2e/dets"].astype(np.float32), ["avg"])
     res = {}
     for name, (dets, cal_names) in cases.items():

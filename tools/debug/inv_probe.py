@@ -6,6 +6,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [REPO, os.path.join(REPO, "tests"), os.path.join(REPO, "lidar-image_object-detection_-fpn_resnet-yolov8_amd", "sfa")]
 import golden_cases as gc
+import golden_io
 from sfa_hip import synthetic
 from test_gpu_model import make_model, _math
 
@@ -17,7 +18,7 @@ class G:  # minimal stand-in for the golden fixture (model weights only)
 def main():
     gpu = torch.device("cuda", 0)
     golden = G()
-    golden.model = np.load(os.path.join(REPO, "tests", "golden", "model_golden.npz"))
+    golden.model = golden_io.load(os.path.join(REPO, "tests", "golden"), "model_golden")
     model = make_model(golden, gpu)
     model._engine(gpu).set_math(_math("fp16x3"))
     model.capture_visualization = True

@@ -9,6 +9,6 @@ i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
   timeout -k 10 240 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/p$i" -o run -- \
-    python bench.py --workload e2e --steps 2 --warmup 1 --no-graph --no-cpu-baseline --probe-forwards 0 > "$OUT/p$i.log" 2>&1 \
+    python bench.py --full --workload e2e --steps 2 --warmup 1 --no-graph --no-cpu-baseline --probe-forwards 0 > "$OUT/p$i.log" 2>&1 \
     || { echo "pass $i failed: $grp" >> "$OUT/failed.txt"; exit 1; }
 done
