@@ -185,6 +185,45 @@ static int launch_conv_h3(const ConvArgs& a, int epilogue, hipStream_t st) {
   return rc;
 }
 
+// SFA_MATH_FP16 (one fp16 product per MAC): the TERMS = 1 instances of the three MFMA-bound
+// fp16x3 kernel families, with launch_conv_h3's shape rules and tile choices, so a shape takes the same
+// tiles, K order and split-K slices in both modes. SFA_E_UNSUPPORTED for everything else (other head
+// counts, K-sliced weights / upsampled residuals — the FPN convs stay fp16x3 —, shapes on the conv_x6g
+// fallback, 16-wide K-tiles): launch_conv then runs the fp16x3 path.
+static int launch_conv_h1(const ConvArgs& a, int epilogue, hipStream_t st) {
+  if (!a.wh || !a.winv || a.wstride || a.wk0 || a.res_up) return SFA_E_UNSUPPORTED;
+  auto ok = [](int rc) { return rc != SFA_E_UNSUPPORTED; };
+  int rc = SFA_E_UNSUPPORTED;
+  const bool strip = strip_ok(a);
+  if (epilogue == EPI_HEAD) {
+    if (a.N == 320) rc = launch_conv_r3_cfg<256, 320, 32, EPI_HEAD, 1, 3, R3_HEAD_STAG, 1>(a, st);
+    return rc;
+  }
+  if (a.N == 64) {
+    if (strip) rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64, 1>(a, st);
+    if (!ok(rc) && a.Kpad >= 256) rc = launch_conv_h3_cfg<256, 64, 32, EPI_STD, 1, 32, 2, false, 0, 1, 64, 1>(a, st);
+    return rc;
+  }
+  if (a.N % 128 == 0) {
+    ConvArgs b = a;
+    b.ksplit = pick_ksplit(a);
+    if (strip && b.ksplit == 1 && a.N == 256 && tile_rows(a) < 50000)
+      rc = launch_conv_h3s_cfg<64, 128, 16, EPI_STD, 3, H3S_128, 1>(b, st);
+    else if (strip && b.ksplit == 2 && a.N == 512 && tile_rows(a) < 50000)
+      rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64, 1>(b, st);
+    else if (strip && (3 * (a.seg[0].C >> 5)) % b.ksplit == 0)
+      rc = launch_conv_h3s_cfg<128, 128, 32, EPI_STD, 3, H3S_128W, 1>(b, st);
+    else if (!strip && tile_rows(a) >= 50000)
+      rc = launch_conv_r3_cfg<128, 128, 32, EPI_STD, 3, 2, R3_BODY, 1>(b, st);
+    if (!ok(rc)) {
+      b.tile_cnt = nullptr;  // conv_h3: the reduce launch
+      if ((a.Kpad / 32) % b.ksplit != 0) b.ksplit = 1;
+      rc = launch_conv_h3_cfg<128, 128, 32, EPI_STD, 2, 32, 2, false, 2, 1, 128, 1>(b, st);
+    }
+  }
+  return rc;
+}
+
 int launch_conv(const ConvArgs& a, int epilogue, int math, hipStream_t st) {
   // Host-side shape checks: the kernels assume these and never bounds-check them.
   if (a.N <= 0 || a.N % 64 != 0 || a.M <= 0 || a.Kpad <= 0 || a.Kpad % 16 != 0) {
@@ -220,6 +259,11 @@ int launch_conv(const ConvArgs& a, int epilogue, int math, hipStream_t st) {
       return SFA_E_UNSUPPORTED;
     }
     return launch_conv_h3(a, epilogue, st);
+  }
+  if (math == SFA_MATH_FP16) {  // never fails where fp16x3 succeeds: shapes without a one-product kernel run fp16x3
+    const int rc = launch_conv_h1(a, epilogue, st);
+    if (rc != SFA_E_UNSUPPORTED) return rc;
+    math = SFA_MATH_FP16X3;
   }
   if (math == SFA_MATH_FP16X3) {
     const int rc = launch_conv_h3(a, epilogue, st);

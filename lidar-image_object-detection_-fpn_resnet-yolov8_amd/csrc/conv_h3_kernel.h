@@ -272,8 +272,11 @@ __device__ __forceinline__ bool splitk_ticket(unsigned* cnt, int tile, int nspli
 }
 
 template <int BM, int BN, int WM, int EPI, int OCC, int BK, int NSTAGE, int NSEG, bool NMAJ = false,
-          int ABL = 0, int MF = 0, int WN = BN, bool RU = false>
+          int ABL = 0, int MF = 0, int WN = BN, bool RU = false, int TERMS = 2>
 __global__ void __launch_bounds__((BM / WM) * (BN / WN) * 64, OCC) conv_h3_kernel(const ConvArgs a) {
+  // TERMS: 2 = fp16x3; 1 = SFA_MATH_FP16 (16x16x32 form only; conv_r3_kernel.h): the high A term alone, only
+  // plane 0 of a.wh in the stage, one MFMA per fragment pair
+  static_assert(TERMS == 2 || (TERMS == 1 && MF == 1), "one-product form: 16x16x32 MFMAs");
   static_assert(BK == 16 || BK == 32, "BK");
   static_assert(NSTAGE >= 2 && NSTAGE <= 4, "ring depth");
   static_assert(NSEG == 1 || NSEG == 2, "segments");
@@ -285,9 +288,9 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WN) * 64, OCC) conv_h3_kerne
   constexpr int KST = BK / 16;
   constexpr int AROW = BK * 4, BROW = BK * 2;  // bytes per LDS row
   constexpr int A_BYTES = BM * AROW, TERM_B = BN * BROW;
-  constexpr int STAGE = A_BYTES + 2 * TERM_B;
+  constexpr int STAGE = A_BYTES + TERMS * TERM_B;
   constexpr int A_RPD = 1024 / AROW, B_RPD = 1024 / BROW;  // rows per DMA instruction
-  constexpr int ND_A = BM / A_RPD, ND_BT = BN / B_RPD, ND_B = 2 * ND_BT;
+  constexpr int ND_A = BM / A_RPD, ND_BT = BN / B_RPD, ND_B = TERMS * ND_BT;
   static_assert(BM % A_RPD == 0 && BN % B_RPD == 0 && BN % 32 == 0 && WM % 32 == 0, "tile");
   static_assert(ND_A % NW == 0, "A DMA groups per wave");
   constexpr int NA = ND_A / NW;
@@ -584,35 +587,41 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WN) * 64, OCC) conv_h3_kerne
   auto compute16 = [&](const unsigned char* S) {
     if constexpr (MF == 1) {
       const int c16 = lane & 15, g = lane >> 4;
-      f16x8_t hf[2][TM];
+      f16x8_t hf[TERMS][TM];
 #pragma unroll
       for (int mi = 0; mi < TM; ++mi) {
         const int R = wm * WM + mi * 16 + c16;
         const x6_f32x4 q0 = *reinterpret_cast<const x6_f32x4*>(S + R * AROW + (((2 * g) ^ swzA(R)) << 4));
         const x6_f32x4 q1 = *reinterpret_cast<const x6_f32x4*>(S + R * AROW + (((2 * g + 1) ^ swzA(R)) << 4));
+        if constexpr (TERMS == 1) {
+          hf[0][mi] = hi1h_x8<true>(q0, q1, as[mi]);
+          continue;
+        }
         f16x4_t t0, t1, u0, u1;
         split2h(q0, as[mi], t0, t1);
         split2h(q1, as[mi], u0, u1);
         hf[0][mi] = __builtin_shufflevector(t0, u0, 0, 1, 2, 3, 4, 5, 6, 7);
-        hf[1][mi] = __builtin_shufflevector(t1, u1, 0, 1, 2, 3, 4, 5, 6, 7);
+        hf[TERMS - 1][mi] = __builtin_shufflevector(t1, u1, 0, 1, 2, 3, 4, 5, 6, 7);
       }
       const unsigned char* SB = S + A_BYTES + (wn * WN + c16) * BROW + ((g ^ swzB(c16)) << 4);
-      f16x8_t bq[3][2];
+      f16x8_t bq[3][TERMS];
       auto read_b = [&](int ni) {
         bq[ni % 3][0] = *reinterpret_cast<const f16x8_t*>(SB + ni * 16 * BROW);
-        bq[ni % 3][1] = *reinterpret_cast<const f16x8_t*>(SB + TERM_B + ni * 16 * BROW);
+        if constexpr (TERMS == 2) bq[ni % 3][1] = *reinterpret_cast<const f16x8_t*>(SB + TERM_B + ni * 16 * BROW);
       };
       read_b(0);
       if (TN > 1) read_b(1);
 #pragma unroll
       for (int ni = 0; ni < TN; ++ni) {
         if (ni + 2 < TN) read_b(ni + 2);
-        const f16x8_t c0 = bq[ni % 3][0], c1 = bq[ni % 3][1];
+        const f16x8_t c0 = bq[ni % 3][0], c1 = bq[ni % 3][TERMS - 1];
 #pragma unroll
         for (int mi = 0; mi < TM; ++mi) {
           f32x4_t cc = acc[mi][ni];
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf[1][mi], c0, cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf[0][mi], c1, cc, 0, 0, 0);
+          if constexpr (TERMS == 2) {
+            cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf[1][mi], c0, cc, 0, 0, 0);
+            cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf[0][mi], c1, cc, 0, 0, 0);
+          }
           cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf[0][mi], c0, cc, 0, 0, 0);
           acc[mi][ni] = cc;
         }
@@ -714,7 +723,7 @@ static __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ConvArg
 }
 
 template <int BM, int BN, int WM, int EPI, int OCC, int BK, int NSTAGE, bool NMAJ = false, int ABL = 0,
-          int MF = 0, int WN = BN>
+          int MF = 0, int WN = BN, int TERMS = 2>
 inline int launch_conv_h3_cfg(const ConvArgs& a, hipStream_t st) {
   if (!a.wh || !a.winv || a.Kpad % BK != 0 || (a.nseg == 2 && a.kseg1 % BK != 0) || a.N % BN != 0) {
     set_error("conv_h3: K/N not aligned to the tile or no split weights (Kpad=%d kseg1=%d N=%d)", a.Kpad,
@@ -744,17 +753,18 @@ inline int launch_conv_h3_cfg(const ConvArgs& a, hipStream_t st) {
   c.fd_ow = make_fast_div((unsigned)a.OW);
   c.fd_oh = make_fast_div((unsigned)a.OH);
   if (a.res_up) {  // FPN skip convs (one segment): the instance with the upsampled-residual epilogue
-    if (a.nseg != 1) {
-      set_error("conv_h3: upsampled residual with two K-segments");
+    if (a.nseg != 1 || TERMS != 2) {
+      set_error("conv_h3: upsampled residual with two K-segments or the one-product form");
       return SFA_E_UNSUPPORTED;
     }
-    hipLaunchKernelGGL((conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, 1, NMAJ, ABL, MF, WN, true>),
-                       dim3((unsigned)nblocks), dim3((BM / WM) * (BN / WN) * 64), 0, st, c);
+    if constexpr (TERMS == 2)
+      hipLaunchKernelGGL((conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, 1, NMAJ, ABL, MF, WN, true>),
+                         dim3((unsigned)nblocks), dim3((BM / WM) * (BN / WN) * 64), 0, st, c);
   } else if (a.nseg == 2) {
-    hipLaunchKernelGGL((conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, 2, NMAJ, ABL, MF, WN>),
+    hipLaunchKernelGGL((conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, 2, NMAJ, ABL, MF, WN, false, TERMS>),
                        dim3((unsigned)nblocks), dim3((BM / WM) * (BN / WN) * 64), 0, st, c);
   } else {
-    hipLaunchKernelGGL((conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, 1, NMAJ, ABL, MF, WN>),
+    hipLaunchKernelGGL((conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, 1, NMAJ, ABL, MF, WN, false, TERMS>),
                        dim3((unsigned)nblocks), dim3((BM / WM) * (BN / WN) * 64), 0, st, c);
   }
   SFA_LAUNCH_CHECK();

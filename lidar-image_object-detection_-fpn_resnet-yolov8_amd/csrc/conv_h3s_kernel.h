@@ -39,15 +39,18 @@ namespace sfa {
 // 1024 = (with 4; round 5) the strip into REGISTERS: each wave loads its own WM + 2 rows (the kw halo) of
 // the next (kh, chunk) strip with buffer loads at kw 1 and splits them from its VGPRs at kw 0, so the f32
 // strip never passes through LDS (no strip buffer, no LDS-DMA pieces, no f32 LDS reads in the split).
-template <int BM, int BN, int WM, int EPI, int OCC, int ABL = 0>
+// TERMS: 2 = fp16x3; 1 = SFA_MATH_FP16 (one product per MAC, conv_r3_kernel.h): the pre-split rows hold the
+// high term alone, only plane 0 of a.wh is staged, one MFMA per fragment pair.
+template <int BM, int BN, int WM, int EPI, int OCC, int ABL = 0, int TERMS = 2>
 __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const ConvArgs a) {
+  static_assert(TERMS == 1 || TERMS == 2, "fp16 terms per operand");
   constexpr int NW = BM / WM, NT = NW * 64;
   constexpr int TM = WM / 16, TN = BN / 16;
   constexpr int AROW = 128, BROW = 64;  // bytes per LDS row: 32 f32 / 32 fp16
   constexpr int SROWS = BM + 2;          // strip rows m0 - 1 .. m0 + BM
   constexpr int ND_S = (SROWS + 7) / 8;  // strip DMA pieces (8 rows each)
   constexpr int S_BYTES = ND_S * 1024;
-  constexpr int TERM_B = BN * BROW, W_BYTES = 2 * TERM_B;
+  constexpr int TERM_B = BN * BROW, W_BYTES = TERMS * TERM_B;
   constexpr int ND_B = W_BYTES / 1024;  // W pieces per k-step (16 rows each)
   constexpr int NS = (ND_S + NW - 1) / NW, NS_REM = ND_S % NW;
   constexpr int NB = (ND_B + NW - 1) / NW, NB_REM = ND_B % NW;
@@ -59,7 +62,7 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
   constexpr int PR_BYTES = (PROWS + 1) * 64;  // per term: 32 fp16 per row, + one zero row
   constexpr int NSB = PS ? (SREG ? 0 : 1) : 2;  // f32 strip buffers
   constexpr int NP = (PROWS + 7) / 8;         // PS: pre-split row groups per wave (8 rows x 8 lanes)
-  constexpr int MAIN_BYTES = NSB * S_BYTES + 2 * W_BYTES + (PS ? NW * 2 * PR_BYTES : 0);
+  constexpr int MAIN_BYTES = NSB * S_BYTES + 2 * W_BYTES + (PS ? NW * TERMS * PR_BYTES : 0);
   constexpr int CSB_OFF = MAIN_BYTES;  // the tile's winv / bias columns (epilogue), staged in the prologue
   constexpr int LDS_BYTES = MAIN_BYTES + 2 * BN * 4;
   static_assert(NW % 2 == 0 && WM % 16 == 0 && BN % 16 == 0, "tile");
@@ -114,8 +117,8 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
 #pragma unroll
   for (int jj = 0; jj < NB; ++jj) {
     const int e = wave + NW * jj < ND_B ? wave + NW * jj : ND_B - 1;
-    const int term = e / (ND_B / 2);
-    const int R = (e - term * (ND_B / 2)) * 16 + (lane >> 2);
+    const int term = e / (ND_B / TERMS);
+    const int R = (e - term * (ND_B / TERMS)) * 16 + (lane >> 2);
     const int lc = (lane & 3) ^ swzB(R);
     boff[jj] = (int)(term * term_bytes) + (int)(((n0 + R) * a.Kpad + 8 * lc) << 1);
   }
@@ -238,7 +241,7 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
       for (int v = 0; v < 4; ++v) acc[mi][ni][v] = 0.f;
   x6_f32x4 rvp[TM][TN];  // RESPF: the residual tile, loaded during the last super-step
 
-  unsigned char* const PH = smem + NSB * S_BYTES + 2 * W_BYTES + wave * 2 * PR_BYTES;  // PS: hi rows, lo + PR_BYTES
+  unsigned char* const PH = smem + NSB * S_BYTES + 2 * W_BYTES + wave * TERMS * PR_BYTES;  // PS: hi rows, lo + PR_BYTES
   auto presplit = [&](const unsigned char* Ss) {
     const int rr = lane >> 3, q = lane & 7;
     // every row's read first: one LDS latency, not one per row (the compiler cannot tell the strip
@@ -259,11 +262,15 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
         const float sc = m0 - 1 + j >= fb ? sB : sA;
         const int off = r * 64 + (((q >> 1) ^ swzP(r)) << 4) + (q & 1) * 8;
         typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-        unsigned h0, h1, l0, l1;
-        split2h_pair(x[0], x[1], sc, h0, l0);
-        split2h_pair(x[2], x[3], sc, h1, l1);
-        *reinterpret_cast<u32x2_t*>(PH + off) = u32x2_t{h0, h1};
-        *reinterpret_cast<u32x2_t*>(PH + PR_BYTES + off) = u32x2_t{l0, l1};
+        if constexpr (TERMS == 1) {
+          *reinterpret_cast<u32x2_t*>(PH + off) = u32x2_t{hi1h_pair(x[0], x[1], sc), hi1h_pair(x[2], x[3], sc)};
+        } else {
+          unsigned h0, h1, l0, l1;
+          split2h_pair(x[0], x[1], sc, h0, l0);
+          split2h_pair(x[2], x[3], sc, h1, l1);
+          *reinterpret_cast<u32x2_t*>(PH + off) = u32x2_t{h0, h1};
+          *reinterpret_cast<u32x2_t*>(PH + PR_BYTES + off) = u32x2_t{l0, l1};
+        }
       }
     }
   };
@@ -273,10 +280,10 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
   static_assert(2 * BN <= NT, "one winv / bias value per thread");
   const float csb_v = tid < BN ? a.winv[n0 + tid] : (tid < 2 * BN && a.bias ? a.bias[n0 + tid - BN] : 0.f);
   if constexpr (PS) {  // the zero rows (conv padding at kw 0 / 2)
-    if (lane < 8) *reinterpret_cast<x6_f32x4*>(PH + (lane & 4 ? PR_BYTES : 0) + PROWS * 64 + (lane & 3) * 16) =
+    if (lane < 4 * TERMS) *reinterpret_cast<x6_f32x4*>(PH + (lane & 4 ? PR_BYTES : 0) + PROWS * 64 + (lane & 3) * 16) =
         x6_f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  auto read_a = [&](const unsigned char* Ss, int kw, f16x8_t (&hf)[2][TM]) {
+  auto read_a = [&](const unsigned char* Ss, int kw, f16x8_t (&hf)[TERMS][TM]) {
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi) {
       if constexpr (PS) {
@@ -284,7 +291,7 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
         const int R = pad ? PROWS : mi * 16 + c16 + kw;
         const int o = R * 64 + ((gq ^ swzP(R)) << 4);
         hf[0][mi] = *reinterpret_cast<const f16x8_t*>(PH + o);
-        hf[1][mi] = *reinterpret_cast<const f16x8_t*>(PH + PR_BYTES + o);
+        if constexpr (TERMS == 2) hf[1][mi] = *reinterpret_cast<const f16x8_t*>(PH + PR_BYTES + o);
         continue;
       }
       const int R = wave * WM + mi * 16 + c16 + kw;
@@ -295,29 +302,32 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
         q0 = x6_f32x4{0.f, 0.f, 0.f, 0.f};
         q1 = q0;
       }
-      split2h_x8(q0, q1, as[mi], hf[0][mi], hf[1][mi]);
+      if constexpr (TERMS == 1) hf[0][mi] = hi1h_x8<true>(q0, q1, as[mi]);
+      else split2h_x8(q0, q1, as[mi], hf[0][mi], hf[TERMS - 1][mi]);
     }
   };
   auto compute = [&](const unsigned char* Ss, const unsigned char* Sw, int kw) {
-    f16x8_t hf[2][TM];
+    f16x8_t hf[TERMS][TM];
     read_a(Ss, kw, hf);
     const unsigned char* SB = Sw + c16 * BROW + ((gq ^ swzB(c16)) << 4);
-    f16x8_t bq[3][2];
+    f16x8_t bq[3][TERMS];
     auto read_b = [&](int ni) {
       bq[ni % 3][0] = *reinterpret_cast<const f16x8_t*>(SB + ni * 16 * BROW);
-      bq[ni % 3][1] = *reinterpret_cast<const f16x8_t*>(SB + TERM_B + ni * 16 * BROW);
+      if constexpr (TERMS == 2) bq[ni % 3][1] = *reinterpret_cast<const f16x8_t*>(SB + TERM_B + ni * 16 * BROW);
     };
     read_b(0);
     if (TN > 1) read_b(1);
 #pragma unroll
     for (int ni = 0; ni < TN; ++ni) {
       if (ni + 2 < TN) read_b(ni + 2);
-      const f16x8_t c0 = bq[ni % 3][0], c1 = bq[ni % 3][1];
+      const f16x8_t c0 = bq[ni % 3][0], c1 = bq[ni % 3][TERMS - 1];
 #pragma unroll
       for (int mi = 0; mi < TM; ++mi) {
         f32x4_t cc = acc[mi][ni];
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, hf[1][mi], cc, 0, 0, 0);
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, hf[0][mi], cc, 0, 0, 0);
+        if constexpr (TERMS == 2) {
+          cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, hf[1][mi], cc, 0, 0, 0);
+          cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, hf[0][mi], cc, 0, 0, 0);
+        }
         cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, hf[0][mi], cc, 0, 0, 0);
         acc[mi][ni] = cc;
       }
@@ -482,7 +492,7 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
   r3t_epilogue_std<TM, TN, NT, false, RESPF, true>(a, acc, smem, m0 + wave * WM, m0, n0, lane, ainv, rvp, CSB);
 }
 
-template <int BM, int BN, int WM, int EPI, int OCC, int ABL = 0>
+template <int BM, int BN, int WM, int EPI, int OCC, int ABL = 0, int TERMS = 2>
 inline int launch_conv_h3s_cfg(const ConvArgs& a, hipStream_t st) {
   const ConvSeg& g = a.seg[0];
   const int ks = a.ksplit > 1 ? a.ksplit : 1;
@@ -511,7 +521,7 @@ inline int launch_conv_h3s_cfg(const ConvArgs& a, hipStream_t st) {
   b.fd_h = make_fast_div((unsigned)g.H);
   // tickets only with one word per output tile in the array: else the reduce launch
   if (ks == 1 || (long long)ceil_div(a.M, BM) * (a.N / BN) > (long long)a.tile_cnt_words) b.tile_cnt = nullptr;
-  hipLaunchKernelGGL((conv_h3s_kernel<BM, BN, WM, EPI, OCC, ABL>), dim3((unsigned)nblocks), dim3((BM / WM) * 64), 0,
+  hipLaunchKernelGGL((conv_h3s_kernel<BM, BN, WM, EPI, OCC, ABL, TERMS>), dim3((unsigned)nblocks), dim3((BM / WM) * 64), 0,
                      st, b);
   SFA_LAUNCH_CHECK();
   if (ks > 1 && !b.tile_cnt) {  // the slices' partials combined by the reduce launch

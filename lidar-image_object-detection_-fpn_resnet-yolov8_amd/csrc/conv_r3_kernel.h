@@ -328,8 +328,13 @@ __device__ __forceinline__ void r3t_epilogue_head(const ConvArgs& a, f32x4_t (&a
 // Without the stagger the ring has two stages (NSTAGE 2).
 // The kernel body for output tile (and split-K slice) lbid; conv_r3_kernel maps blockIdx to lbid
 // with xcd_remap.
-template <int BM, int BN, int WM, int EPI, int OCC, int NSTAGE, int NSEG, int ABL = 0>
+// TERMS: 2 = fp16x3 (hi / lo terms, three products); 1 = SFA_MATH_FP16: one product per MAC — the A
+// fragment is the high term alone (fp16(x s), the hi of the fp16x3 split), only plane 0 of a.wh is
+// staged (half the W ring, DMA pieces and fragment reads) and each (A, W) fragment pair takes one MFMA.
+// Scales, epilogues, split-K partials are the fp16x3 ones.
+template <int BM, int BN, int WM, int EPI, int OCC, int NSTAGE, int NSEG, int ABL = 0, int TERMS = 2>
 __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
+  static_assert(TERMS == 1 || TERMS == 2, "fp16 terms per operand");
   constexpr bool STAG = (ABL & 1048576) != 0;
   static_assert((ABL & (256 | 2048)) == (256 | 2048) &&
                     (ABL & ~(4 | 256 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536 | 524288 | 1048576 | 2097152)) == 0,
@@ -340,8 +345,8 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
   constexpr int NW = BM / WM, NT = NW * 64;
   constexpr int TM = WM / 16, TN = BN / 16;
   constexpr int BK = 32, BROW = BK * 2;  // W row bytes per term
-  constexpr int TERM_B = BN * BROW, STAGE = 2 * TERM_B;
-  constexpr int ND_BT = TERM_B / 1024, ND_B = 2 * ND_BT;  // 1-KiB DMA pieces (16 rows each)
+  constexpr int TERM_B = BN * BROW, STAGE = TERMS * TERM_B;
+  constexpr int ND_BT = TERM_B / 1024, ND_B = TERMS * ND_BT;  // 1-KiB DMA pieces (16 rows each)
   constexpr int NB = (ND_B + NW - 1) / NW;
   constexpr int NB_REM = ND_B % NW;  // if != 0: waves < NB_REM issue NB pieces, the rest NB - 1
   static_assert(BM % WM == 0 && WM % 16 == 0 && BN % 16 == 0 && TERM_B % 1024 == 0, "tile");
@@ -537,23 +542,28 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
   constexpr bool DMA_DEL = (ABL & 2097152) != 0;
   [[maybe_unused]] int boff_p[NB];
   if constexpr (DMA_DEL) {
-    static_assert(NB_REM == 0, "whole pieces per wave");
+    static_assert(NB_REM == 0 || TERMS == 1, "whole pieces per wave");
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-      const int e = (wave >= NW / 2 ? wave - NW / 2 : wave) + NW * j;
+      int e = (wave >= NW / 2 ? wave - NW / 2 : wave) + NW * j;
+      if constexpr (NB_REM != 0) e = e < ND_B ? e : ND_B - 1;  // (a piece past the tile is never issued)
       boff_p[j] = (int)((e / ND_BT) * term_bytes) + (e % ND_BT) * 16 * wst * 2;
     }
   }
   auto load_w_piece_p = [&](int j, int kt, unsigned char* S) {
     const int e = wave - NW / 2 + NW * j;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void*)(S + e * 1024), 16,
-                                             (unsigned)(wlane + boff_p[j] + 2 * kcol(kt)), 0, 0, 0);
+    if (NB_REM == 0 || e < ND_B)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void*)(S + e * 1024), 16,
+                                               (unsigned)(wlane + boff_p[j] + 2 * kcol(kt)), 0, 0, 0);
   };
-  f16x8_t hf[2][TM];  // split A of this K-tile
-  auto split_a = [&](f16x8_t (&h)[2][TM]) {
+  f16x8_t hf[TERMS][TM];  // split A of this K-tile
+  auto split_a = [&](f16x8_t (&h)[TERMS][TM]) {
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi) {
-      if constexpr ((ABL & 4096) != 0) {  // 2 VALU per value (split2h_x8)
+      if constexpr (TERMS == 1) {  // the high term alone
+        h[0][mi] = hi1h_x8<(ABL & 4096) != 0>(__builtin_bit_cast(x6_f32x4, raw[mi][0]),
+                                              __builtin_bit_cast(x6_f32x4, raw[mi][1]), as[mi]);
+      } else if constexpr ((ABL & 4096) != 0) {  // 2 VALU per value (split2h_x8)
         split2h_x8(__builtin_bit_cast(x6_f32x4, raw[mi][0]), __builtin_bit_cast(x6_f32x4, raw[mi][1]), as[mi],
                    h[0][mi], h[1][mi]);
       } else {
@@ -579,10 +589,10 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
   constexpr int RS = RA + 1;
   static_assert(RA == 2 || STAG, "3-block read-ahead: with the stagger only");
   static_assert(!STAG || (TN % RS == 0 && TN % 2 == 0 && TN / 2 > RA), "stagger: W ring slots must repeat per tile");
-  f16x8_t bq[RS][2];  // W fragment ring: block p in slot p % RS
-  auto read_b = [&](const unsigned char* S, int ni, f16x8_t (&dst)[2]) {
+  f16x8_t bq[RS][TERMS];  // W fragment ring: block p in slot p % RS
+  auto read_b = [&](const unsigned char* S, int ni, f16x8_t (&dst)[TERMS]) {
     dst[0] = *reinterpret_cast<const f16x8_t*>(S + bfo + ni * 16 * BROW);
-    dst[1] = *reinterpret_cast<const f16x8_t*>(S + TERM_B + bfo + ni * 16 * BROW);
+    if constexpr (TERMS == 2) dst[1] = *reinterpret_cast<const f16x8_t*>(S + TERM_B + bfo + ni * 16 * BROW);
   };
 
   const int nk = a.Kpad / BK / nsplit;  // this block's K-tiles: kt0 .. kt0 + nk - 1
@@ -607,12 +617,14 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
   }
   const int wave_half = wave >= NW / 2 ? 1 : 0;  // SIMD partners: waves w and w + NW / 2
   auto mma_block = [&](int ni) {
-    const f16x8_t c0 = bq[ni % RS][0], c1 = bq[ni % RS][1];
+    const f16x8_t c0 = bq[ni % RS][0], c1 = bq[ni % RS][TERMS - 1];
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi) {
       f32x4_t cc = acc[mi][ni];
-      cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, hf[1][mi], cc, 0, 0, 0);
-      cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, hf[0][mi], cc, 0, 0, 0);
+      if constexpr (TERMS == 2) {
+        cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, hf[1][mi], cc, 0, 0, 0);
+        cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, hf[0][mi], cc, 0, 0, 0);
+      }
       cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, hf[0][mi], cc, 0, 0, 0);
       acc[mi][ni] = cc;
     }
@@ -756,9 +768,9 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
   }
 }
 
-template <int BM, int BN, int WM, int EPI, int OCC, int NSTAGE, int NSEG, int ABL = 0>
+template <int BM, int BN, int WM, int EPI, int OCC, int NSTAGE, int NSEG, int ABL = 0, int TERMS = 2>
 __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_r3_kernel(const ConvArgs a) {
-  conv_r3_body<BM, BN, WM, EPI, OCC, NSTAGE, NSEG, ABL>(a, xcd_remap(blockIdx.x, gridDim.x));
+  conv_r3_body<BM, BN, WM, EPI, OCC, NSTAGE, NSEG, ABL, TERMS>(a, xcd_remap(blockIdx.x, gridDim.x));
 }
 
 // Launch-time checks of one conv_r3 launch (the kernel never bounds-checks these).
@@ -803,7 +815,7 @@ inline int conv_r3_check(const ConvArgs& a) {
   return SFA_OK;
 }
 
-template <int BM, int BN, int WM, int EPI, int OCC, int NSTAGE, int ABL = 0>
+template <int BM, int BN, int WM, int EPI, int OCC, int NSTAGE, int ABL = 0, int TERMS = 2>
 inline int launch_conv_r3_cfg(const ConvArgs& a, hipStream_t st) {
   const int crc = conv_r3_check<BM, BN, EPI, ABL>(a);
   if (crc != SFA_OK) return crc;
@@ -817,10 +829,10 @@ inline int launch_conv_r3_cfg(const ConvArgs& a, hipStream_t st) {
   b.fd_ow = make_fast_div((unsigned)a.OW);
   b.fd_oh = make_fast_div((unsigned)a.OH);
   if (a.nseg == 2)
-    hipLaunchKernelGGL((conv_r3_kernel<BM, BN, WM, EPI, OCC, NSTAGE, 2, ABL>), dim3((unsigned)nblocks),
+    hipLaunchKernelGGL((conv_r3_kernel<BM, BN, WM, EPI, OCC, NSTAGE, 2, ABL, TERMS>), dim3((unsigned)nblocks),
                        dim3((BM / WM) * 64), 0, st, b);
   else
-    hipLaunchKernelGGL((conv_r3_kernel<BM, BN, WM, EPI, OCC, NSTAGE, 1, ABL>), dim3((unsigned)nblocks),
+    hipLaunchKernelGGL((conv_r3_kernel<BM, BN, WM, EPI, OCC, NSTAGE, 1, ABL, TERMS>), dim3((unsigned)nblocks),
                        dim3((BM / WM) * 64), 0, st, b);
   SFA_LAUNCH_CHECK();
   if (ks > 1) {  // the slices' partials combined by the reduce launch

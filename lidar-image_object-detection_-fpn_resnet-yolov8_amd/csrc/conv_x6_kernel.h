@@ -84,6 +84,35 @@ __device__ __forceinline__ void split2h_x8(const x6_f32x4 q0, const x6_f32x4 q1,
   lo = __builtin_bit_cast(f16x8_t, u32x4_t{l0, l1, l2, l3});
 }
 
+// SFA_MATH_FP16 (one product per MAC): only the high term, fp16(x s) rounded once to nearest even —
+// the first two instructions of split2h_pair, so bit-equal to its hi2; no low term is formed.
+__device__ __forceinline__ unsigned hi1h_pair(float x0, float x1, float s) {
+  unsigned hi2;
+  asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\t"
+      "v_fma_mixhi_f16 %0, %2, %3, 0"
+      : "=&v"(hi2)
+      : "v"(x0), "v"(x1), "v"(s));
+  return hi2;
+}
+// 8 f32 values (two quads) -> the fp16 high fragment alone. MIX: the v_fma_mix form (as split2h_x8),
+// else the compiler's multiply + convert (as split2h: x s is exact, the convert rounds to nearest even).
+template <bool MIX>
+__device__ __forceinline__ f16x8_t hi1h_x8(const x6_f32x4 q0, const x6_f32x4 q1, float s) {
+  if constexpr (MIX) {
+    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+    return __builtin_bit_cast(f16x8_t, u32x4_t{hi1h_pair(q0[0], q0[1], s), hi1h_pair(q0[2], q0[3], s),
+                                               hi1h_pair(q1[0], q1[1], s), hi1h_pair(q1[2], q1[3], s)});
+  } else {
+    f16x8_t h;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      h[i] = (_Float16)(q0[i] * s);
+      h[4 + i] = (_Float16)(q1[i] * s);
+    }
+    return h;
+  }
+}
+
 // Shared epilogue of the bf16x6 kernels (the accumulator layout of every 32x32 MFMA:
 // lane (r, h), register v -> row (v & 3) + 8 (v >> 2) + 4h, column r).
 // PREC 1 (fp16x3): the accumulator of row R holds sum (x s_R)(w 2^e[n]); it is scaled

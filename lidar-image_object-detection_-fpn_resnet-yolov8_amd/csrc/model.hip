@@ -550,7 +550,7 @@ extern "C" int sfa_model_get_option(const sfa_model* model, int key, int* value)
 
 extern "C" int sfa_model_set_math(sfa_model* model, int math) {
   SFA_CHECK_ARG(model, "set_math: null model");
-  SFA_CHECK_ARG(math == SFA_MATH_F32 || math == SFA_MATH_BF16X6 || math == SFA_MATH_FP16X3,
+  SFA_CHECK_ARG(math == SFA_MATH_F32 || math == SFA_MATH_BF16X6 || math == SFA_MATH_FP16X3 || math == SFA_MATH_FP16,
                 "set_math: unknown mode %d", math);
   model->math = math;
   return SFA_OK;
@@ -726,7 +726,10 @@ static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B
   const Plan& p = m->plan;
 
   // fp16x3: every conv input's max |x| is recorded by its producer (slots zeroed here)
-  const bool h3 = m->math == SFA_MATH_FP16X3;
+  // SFA_MATH_FP16: the fp16x3 plumbing (scales, amax words, tickets, patch stem, commuted FPN) with one
+  // product per MAC in the body convs and the heads; the stem and the FPN convs stay fp16x3 (math_sf)
+  const bool h3 = m->math == SFA_MATH_FP16X3 || m->math == SFA_MATH_FP16;
+  const int math_sf = m->math == SFA_MATH_FP16 ? SFA_MATH_FP16X3 : m->math;
   auto AM = [&](int slot) -> unsigned* {
     return h3 ? reinterpret_cast<unsigned*>(ws + bf.amax) + (size_t)slot * B * SFA_AMAX_WORDS : nullptr;
   };
@@ -770,7 +773,7 @@ static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B
       a.part_floats = (size_t)B * H2 * W2 * 64;
       SFA_RC(launch_stem_patch(a, st));
     } else {
-      SFA_RC(launch_conv(a, EPI_STD, m->math, st));
+      SFA_RC(launch_conv(a, EPI_STD, math_sf, st));
     }
   }
   if (!patch_stem) SFA_RC(launch_maxpool3s2(F(bf.s0), F(bf.p0), B, H2, W2, 64, st));  // :182
@@ -858,7 +861,7 @@ static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B
       a.seg[0] = seg(x, B, xh, xw, xc, 1, 1, 0);
       a.fpn_gemm = (m->fpn_gemm >> f) & 1;
       io(a, xslot_in, -1, -1);
-      SFA_RC(launch_conv(a, EPI_STD, m->math, fs));
+      SFA_RC(launch_conv(a, EPI_STD, math_sf, fs));
     }
     ConvArgs a = conv_args(wb, pc, B, 2 * xh, 2 * xw, out, nullptr, 0);
     a.Kpad = sc;
@@ -870,7 +873,7 @@ static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B
     a.res_sw = xw > 1 ? (float)(xw - 1) / (float)(2 * xw - 1) : 0.f;
     a.fpn_gemm = (m->fpn_gemm >> (3 + f)) & 1;
     io(a, skip_slot, -1, out_slot);
-    return launch_conv(a, EPI_STD, m->math, fs);
+    return launch_conv(a, EPI_STD, math_sf, fs);
   };
   if (commute_at(0)) {
     SFA_RC(fpn_pair(0, F(bf.l[3]), H / 32, W / 32, 512, blk_slot(3, 1, 1), F(bf.l[2]), 256, blk_slot(2, 1, 1),
@@ -884,7 +887,7 @@ static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B
       a.seg[0] = seg(F(bf.up1), B, H16, W16, 512, 1, 1, 0);
       a.seg[1] = seg(F(bf.l[2]), B, H16, W16, 256, 1, 1, 0);
       io(a, blk_slot(3, 1, 1), blk_slot(2, 1, 1), AM_FPN + 0);  // up1 = upsample(layer4)
-      SFA_RC(launch_conv(a, EPI_STD, m->math, st));
+      SFA_RC(launch_conv(a, EPI_STD, math_sf, st));
     }
   }
   SFA_RC(launch_upsample2x(F(bf.c1), F(bf.up2), B, H16, W16, 256, st));
@@ -967,7 +970,7 @@ static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B
     a.seg[0] = seg(F(bf.up2), B, H8, W8, 256, 1, 1, 0);
     a.seg[1] = seg(F(bf.l[1]), B, H8, W8, 128, 1, 1, 0);
     io(a, AM_FPN + 0, blk_slot(1, 1, 1), AM_FPN + 1);
-    SFA_RC(launch_conv(a, EPI_STD, m->math, st));
+    SFA_RC(launch_conv(a, EPI_STD, math_sf, st));
   }
   SFA_RC(launch_upsample2x(F(bf.c2), F(bf.up3), B, H8, W8, 128, st));
   // FPN level 3 (-> up_level4) on stream fs
@@ -981,7 +984,7 @@ static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B
     a.seg[0] = seg(F(bf.up3), B, H4, W4, 128, 1, 1, 0);
     a.seg[1] = seg(F(bf.l[0]), B, H4, W4, 64, 1, 1, 0);
     io(a, AM_FPN + 1, blk_slot(0, 1, 1), AM_FPN + 2);
-    return launch_conv(a, EPI_STD, m->math, fs);
+    return launch_conv(a, EPI_STD, math_sf, fs);
   };
   SFA_RC(fpn3(st));
   // level 2 (needs up_level4, just written) on the side stream after level 0, level 1 here:

@@ -106,6 +106,7 @@ class PoseResNet(nn.Module):
         self.backbone_features = {}
         self._arch = _lib.make_arch(dict(self.heads), head_conv)
         self._engines = {}
+        self._math = None  # set_math: None = the engine's default (SFA_MATH or fp16x3)
         self._sig = None
         self._state_tensors = None  # (structure generation, [state tensors]) cache of _signature
 
@@ -142,9 +143,25 @@ class PoseResNet(nn.Module):
         eng = self._engines.get(device)
         if eng is None:
             packed = pack_state_dict(self.state_dict(), self._arch)
-            eng = KfpnEngine(self._arch, packed, device)
+            eng = KfpnEngine(self._arch, packed, device, math=self._math)
             self._engines[device] = eng
         return eng
+
+    def set_math(self, math):
+        """Convolution arithmetic of this model's forwards: "fp16x3" (the default), "bf16x6", "f32" or the
+        opt-in reduced-precision "fp16" (one fp16 product per MAC in the residual layers and the heads: faster,
+        logit error ~1e-3 instead of <= 1e-5; include/sfa_hip.h sfa_math), or the _lib.MATH_* integer.
+        Applies to the engines this model already has and to every one it creates later."""
+        if isinstance(math, str):
+            if math.strip().lower() not in _lib.MATH_NAMES:
+                raise ValueError(f"set_math({math!r}): expected one of {sorted(_lib.MATH_NAMES)}")
+            math = _lib.MATH_NAMES[math.strip().lower()]
+        math = int(math)
+        if math not in _lib.MATH_NAMES.values():
+            raise ValueError(f"set_math({math}): expected one of {sorted(_lib.MATH_NAMES.values())}")
+        for eng in self._engines.values():
+            eng.set_math(math)
+        self._math = math
 
     def forward(self, x):
         return self.forward_layout(x, _lib.IN_NCHW3)

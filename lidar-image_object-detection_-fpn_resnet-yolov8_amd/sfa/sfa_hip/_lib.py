@@ -77,7 +77,8 @@ _PROTOS = {
                             _vp, _vp, _c_size, _vp]),
 }
 
-MATH_F32, MATH_BF16X6, MATH_FP16X3 = 0, 1, 2
+MATH_F32, MATH_BF16X6, MATH_FP16X3, MATH_FP16 = 0, 1, 2, 3
+MATH_NAMES = {"f32": MATH_F32, "bf16x6": MATH_BF16X6, "fp16x3": MATH_FP16X3, "fp16": MATH_FP16}
 _PROTOS["sfa_model_set_math"] = (_c_int, [_vp, _c_int])
 _PROTOS["sfa_model_get_math"] = (_c_int, [_vp])
 _PROTOS["sfa_model_set_option"] = (_c_int, [_vp, _c_int, _c_int])
@@ -94,7 +95,8 @@ _PROTOS["sfa_gather_feat"] = (_c_int, [_vp, _c_int, _c_i64, _c_int, _c_i64, _c_i
 
 
 def math_from_env(default=MATH_FP16X3) -> int:
-    """SFA_MATH=f32 | bf16x6 | fp16x3 selects the convolution arithmetic (include/sfa_hip.h)."""
+    """SFA_MATH=f32 | bf16x6 | fp16x3 | fp16 selects the convolution arithmetic (include/sfa_hip.h;
+    fp16 is the opt-in reduced-precision mode, below the parity bar)."""
     v = os.environ.get("SFA_MATH", "").strip().lower()
     if not v:
         return default
@@ -104,7 +106,9 @@ def math_from_env(default=MATH_FP16X3) -> int:
         return MATH_BF16X6
     if v in ("fp16x3", "h3"):
         return MATH_FP16X3
-    raise ValueError(f"SFA_MATH={v!r}: expected 'f32', 'bf16x6' or 'fp16x3'")
+    if v in ("fp16", "fp16x1"):
+        return MATH_FP16
+    raise ValueError(f"SFA_MATH={v!r}: expected 'f32', 'bf16x6', 'fp16x3' or 'fp16'")
 
 
 class SfaFusionParams(ctypes.Structure):

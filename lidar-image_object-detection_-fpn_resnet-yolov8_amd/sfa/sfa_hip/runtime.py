@@ -102,7 +102,9 @@ class KfpnEngine:
             self.set_side_streams(False)
 
     def set_math(self, math: int):
-        """_lib.MATH_FP16X3 (default), _lib.MATH_BF16X6 or _lib.MATH_F32 for every convolution."""
+        """_lib.MATH_FP16X3 (default), _lib.MATH_BF16X6 or _lib.MATH_F32 for every convolution, or the opt-in
+        reduced-precision _lib.MATH_FP16: one fp16 product per MAC in the residual layers' convolutions and the
+        heads (stem and FPN stay fp16x3), logit error ~1e-3 instead of <= 1e-5 (include/sfa_hip.h)."""
         check(lib().sfa_model_set_math(self._h, int(math)), "sfa_model_set_math")
         self.math = int(math)
 
