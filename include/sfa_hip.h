@@ -237,7 +237,22 @@ int sfa_model_forward(const sfa_model* model, const float* x, int in_layout, int
  * sfa_model_forward returns on the stream (for the reference's opt-in
  * visualisation capture, fpn_resnet.py:189-242).  LAYERk / UP_LEVELk are NHWC
  * float32 (B, h, w, C); HEADS_Lk are channel-planar float32
- * [sum(head_channels)][B][h][w] per KFPN level.  -1 on bad arguments. */
+ * [sum(head_channels)][B][h][w] per KFPN level.  -1 on bad arguments.
+ * Which reference tensor each buffer holds (fpn_resnet.py:184-233):
+ *   LAYER1..4   out_layer1..4, (B, H/4 .. H/32, W/4 .. W/32, 64 .. 512)
+ *   UP_LEVEL2   up_level2 = bilinear x2 of conv_up_level1's output, (B, H/8, W/8, 256): head level 0's input
+ *   UP_LEVEL3   up_level3 = bilinear x2 of conv_up_level2's output, (B, H/4, W/4, 128): head level 1's input
+ *   UP_LEVEL4   up_level4 = conv_up_level3's output itself,        (B, H/4, W/4, 64):  head level 2's input
+ *   HEADS_Lk    level k's head maps BEFORE the resize and apply_kfpn, heads in forward order along the
+ *               channel axis; level 0 at (H/8, W/8), levels 1, 2 at (H/4, W/4)
+ * (up_level1, the concatenations and the conv_up_level1/2 outputs at their own resolution are not kept:
+ * the fp16x3 forward never forms the first two.)
+ * Ordering: the side stream that runs head levels 0 and 2 forks from and joins back into the caller's
+ * stream inside sfa_model_forward, before the KFPN combine, on failure too; so work ordered after the
+ * forward on the caller's stream (or a synchronisation of that stream alone) sees every buffer
+ * complete; a device-wide synchronisation is sufficient, not required.  Another stream needs an event.
+ * The offsets are those of one pass: for batch > sfa_forward_max_batch the buffers hold the last pass
+ * only, at the offsets of a batch of sfa_forward_max_batch frames. */
 enum sfa_buffer {
   SFA_BUF_LAYER1 = 0, SFA_BUF_LAYER2, SFA_BUF_LAYER3, SFA_BUF_LAYER4,
   SFA_BUF_UP_LEVEL2, SFA_BUF_UP_LEVEL3, SFA_BUF_UP_LEVEL4,

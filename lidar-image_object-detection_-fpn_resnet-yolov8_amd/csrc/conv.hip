@@ -63,7 +63,8 @@ static bool strip_ok(const ConvArgs& a) {
 // tools/experiments/r03/ with its convbench hook.
 //  * heads: conv_r3_kernel 256 x 320 (all 5 heads of a level per tile), half-tile stagger, 3-stage
 //    W ring, 3-block W read-ahead, scalar taps, chunk-major K order, packed head epilogue;
-//  * 3x3/s1 body convs: conv_h3s_kernel (A staged once per kh as a row strip for the three kw
+//  * 3x3/s1 body convs on maps of >= 128 rows per frame (smaller ones: "the rest" below, see
+//    launch_conv_h3s_cfg): conv_h3s_kernel (A staged once per kh as a row strip for the three kw
 //    taps), transposed float4 epilogue, v_fma_mix split; 64-wide 128 x 64 at 3 blocks / CU with the
 //    pre-split strip and the residual loaded during the last super-step, 128..512-wide 128 x 128
 //    (split-K 2 for the 512-wide; the 256-wide layer3 convs on 64 x 128 tiles);

@@ -177,8 +177,8 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
     }
   };
   // the fp16x3 scales of the block's first two frames (uniform loads); x of this lane's A row in each
-  // 16-row tile (kw edge masks) and its frame's scale — rows of later frames (blocks taller than a
-  // frame: small maps) read their own
+  // 16-row tile (kw edge masks) and its frame's scale — rows of later frames read their own here, but
+  // presplit does not: the launcher refuses maps whose blocks could reach a third frame
   const int P = a.OH * a.OW;
   const int f0 = m0 / P;
   const int fb = (f0 + 1) * P;  // first row of the next frame
@@ -500,6 +500,18 @@ inline int launch_conv_h3s_cfg(const ConvArgs& a, hipStream_t st) {
       (g.C & 31) != 0 || a.Kpad != 9 * g.C || a.OH != g.H || a.OW != g.W || a.N % BN != 0) {
     set_error("conv_h3s: not a one-segment 3x3/s1/p1 conv with C %% 32 == 0 (C=%d Kpad=%d N=%d)", g.C, a.Kpad,
               a.N);
+    return SFA_E_UNSUPPORTED;
+  }
+  // The pre-split strip (presplit) knows two fp16x3 scales per block, those of the frames of its first
+  // row and the next one, while the epilogue scales every row back by its own frame's: a block must not
+  // reach a third frame. With frames of at least BM rows none does. The bound is the largest product
+  // tile's (128 rows) for every tile shape, so which kernel a map takes, and with it a frame's bits,
+  // depends on the map's size alone, never on the batch; smaller maps take the caller's next kernel,
+  // which looks every row's frame up. (Frames of equal binary exponent hid this: a 2^9 x brighter third
+  // frame was split with its neighbour's scale, overflowed fp16 and came out as zeros after the ReLU.)
+  constexpr int MIN_FRAME_ROWS = BM > 128 ? BM : 128;
+  if (a.OH * a.OW < MIN_FRAME_ROWS) {
+    set_error("conv_h3s: frames of %d rows are shorter than %d", a.OH * a.OW, MIN_FRAME_ROWS);
     return SFA_E_UNSUPPORTED;
   }
   if (ks > 1 && (EPI != EPI_STD || (3 * (g.C >> 5)) % ks != 0 || !a.part ||

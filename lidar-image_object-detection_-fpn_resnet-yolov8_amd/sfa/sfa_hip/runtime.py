@@ -217,8 +217,15 @@ class KfpnEngine:
         return outs
 
     def debug_views(self, ws: torch.Tensor, B, H, W) -> dict:
-        """NCHW views of intermediate maps left in the workspace by the last forward."""
+        """NCHW views of intermediate maps left in the workspace by the last forward (include/sfa_hip.h
+        sfa_forward_buffer_offset says which reference tensor each one is).  A batch above
+        sfa_forward_max_batch(H, W) runs in passes that share the workspace, so it has no such views:
+        ValueError."""
         L = lib()
+        bmax = int(L.sfa_forward_max_batch(H, W))
+        if B < 1 or B > bmax:
+            raise ValueError(f"debug_views: batch {B} is outside 1..{bmax}, what one forward pass holds at "
+                             f"{H}x{W}; the workspace keeps the maps of one pass only")
 
         def nhwc(which, h, w, c):
             off = int(L.sfa_forward_buffer_offset(self._h, B, H, W, which))
