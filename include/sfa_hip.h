@@ -1,6 +1,7 @@
 /*
  * sfa_hip.h — C ABI of the MI355X (gfx950) hot path of the SFA3D-style
- * FPN-ResNet-18 LiDAR detector: BEV voxelisation -> KFPN forward -> decode.
+ * FPN-ResNet-18 LiDAR detector: BEV voxelisation -> KFPN forward -> decode
+ * (and of its plain ResNet-18 sibling, arch "resnet_18": sfa_arch_ex).
  *
  * Plain C: pointers, sizes and status codes only; no torch / C++ types.
  * Every entry point that touches the device takes the caller's hipStream_t
@@ -124,6 +125,33 @@ size_t sfa_state_floats(const sfa_arch* arch);
 size_t sfa_packed_floats(const sfa_arch* arch);
 int sfa_pack_weights(const sfa_arch* arch, const float* state, size_t state_floats, float* packed);
 
+/* Second detector family (models/model_utils.py:34-37 -> models/resnet.py get_pose_net(18, heads, 64),
+ * PoseResNet.forward :219-234): arch "resnet_18", the plain CenterNet-style model — the same stem and
+ * residual layers, then three ConvTranspose2d(k=4, s=2, p=1, bias=False) + BatchNorm + ReLU layers
+ * (512 -> 256 -> 256 -> 256, H/32 -> H/4) and the heads (conv3x3 -> ReLU -> conv1x1) on that one
+ * 256-channel map; no FPN, no apply_kfpn.  sfa_arch cannot grow (the ABI version is pinned), so the family
+ * is named beside it: the sfa_arch entry points above are the SFA_BACKBONE_KFPN case of the _ex ones,
+ * with identical results.  reserved must be zero; a nonzero word or an unknown backbone is
+ * SFA_E_INVALID (-1 / 0 from the count / size entry points); depths other than 18 stay refused.
+ * State layout of SFA_BACKBONE_DECONV (resnet.py registration order): the stem and layers as above,
+ * deconv_layers.{0,3,6}.weight (512|256, 256, 4, 4) — (Cin, Cout, kh, kw), not OIHW — each followed by
+ * its BatchNorm deconv_layers.{1,4,7}.*, then the heads in sorted() order under their plain names:
+ * <head>.0.weight (64, 256, 3, 3), .0.bias, .2.weight, .2.bias.  Packed: each transposed conv as the
+ * four 2 x 2 phase matrices [256][4 Cin] of its output parities (BN scale folded in, BN shift as the
+ * bias), in f32 and as the two fp16 terms of SFA_MATH_FP16X3 (no bf16 terms). */
+enum sfa_backbone { SFA_BACKBONE_KFPN = 0, SFA_BACKBONE_DECONV = 1 };
+typedef struct sfa_arch_ex {
+  sfa_arch base;
+  int backbone;     /* sfa_backbone */
+  int reserved[7];  /* zero */
+} sfa_arch_ex;
+int sfa_state_count_ex(const sfa_arch_ex* arch);
+int sfa_state_entry_ex(const sfa_arch_ex* arch, int index, char* name, int name_len, int64_t* shape4,
+                       int* ndim);
+size_t sfa_state_floats_ex(const sfa_arch_ex* arch);
+size_t sfa_packed_floats_ex(const sfa_arch_ex* arch);
+int sfa_pack_weights_ex(const sfa_arch_ex* arch, const float* state, size_t state_floats, float* packed);
+
 /* A model handle references a device copy of the packed weights (caller-owned,
  * must outlive the handle).  No device memory is allocated.  The handle owns side
  * streams + events on the device current at creation: a forward on a stream of that
@@ -133,6 +161,10 @@ int sfa_pack_weights(const sfa_arch* arch, const float* state, size_t state_floa
  * stream. */
 typedef struct sfa_model sfa_model;
 int sfa_model_create(const sfa_arch* arch, const float* packed_device, sfa_model** out);
+/* The same for either family.  A SFA_BACKBONE_DECONV model has no parallel branch: it creates no side
+ * streams, every launch of its forward is on the caller's stream and sfa_model_set_side_streams is a
+ * no-op on it (returns SFA_OK). */
+int sfa_model_create_ex(const sfa_arch_ex* arch, const float* packed_device, sfa_model** out);
 void sfa_model_destroy(sfa_model* model);
 
 /* Side streams on (1, the default; env SFA_SIDE_STREAMS=0 at create time turns them off) or
@@ -169,7 +201,11 @@ int sfa_model_set_side_streams(sfa_model* model, int on);
  *     the heads, f64-accumulating CPU restatement, profiles/fp16_error_budget.json): 3.8e-3 / 4.0e-3
  *     on the two small fixture cases, 2.6e-3 on the 608 x 608 frame, 4.6e-3 on the 16 bench frames
  *     (FP16X3: <= 9.3e-6), 795 of the bench batch's 800 reference detections found at the same
- *     pixel with the same class; the GPU kernels are held to 2x of these (tests/test_gpu_math_fp16.py). */
+ *     pixel with the same class; the GPU kernels are held to 2x of these (tests/test_gpu_math_fp16.py).
+ * SFA_BACKBONE_DECONV models run SFA_MATH_FP16X3 only: the transposed convolutions have an fp16x3 kernel
+ * alone, so sfa_model_set_math(SFA_MATH_F32 / SFA_MATH_BF16X6) returns SFA_E_UNSUPPORTED on them, and so
+ * does SFA_MATH_FP16 until its logit error on this architecture has a budget (the CPU restatement of the
+ * one-product arithmetic is not extended to it yet); the model stays in its previous mode. */
 enum sfa_math { SFA_MATH_F32 = 0, SFA_MATH_BF16X6 = 1, SFA_MATH_FP16X3 = 2, SFA_MATH_FP16 = 3 };
 int sfa_model_set_math(sfa_model* model, int math);
 int sfa_model_get_math(const sfa_model* model);
@@ -208,7 +244,8 @@ int sfa_model_get_option(const sfa_model* model, int key, int* value);
  * that launches it; SFA_PROBE_SERIAL: all launches stay on the caller's stream (no
  * side streams), so each head launch has the chip to itself.  sfa_model_probe_times
  * waits for the last probed forward's events and returns the launch durations of head
- * levels 0 .. n-1 in ms.  flags = 0 turns the probe off. */
+ * levels 0 .. n-1 in ms.  flags = 0 turns the probe off.  On a SFA_BACKBONE_DECONV model the probed
+ * launches are its three transposed convolutions and its one heads launch, in that order (n <= 4). */
 enum sfa_probe_flags { SFA_PROBE_HEADS = 1, SFA_PROBE_SERIAL = 2 };
 int sfa_model_set_probe(sfa_model* model, int flags);
 int sfa_model_probe_times(const sfa_model* model, float* ms, int n);
@@ -225,9 +262,15 @@ int sfa_model_probe_times(const sfa_model* model, float* ms, int n);
  * conv input, up_level3, is 32 H W bytes per frame): 181 frames at 608 x 608.  A larger batch
  * runs as consecutive passes of that many frames on the caller's stream, sharing one workspace
  * sized for a pass (bit-identical per frame: the arithmetic is batch-invariant); a single frame
- * too large for one pass (H W >= 2^26) is refused with SFA_E_UNSUPPORTED before any launch. */
+ * too large for one pass (H W >= 2^26) is refused with SFA_E_UNSUPPORTED before any launch.
+ * sfa_forward_max_batch is the SFA_BACKBONE_KFPN value.  sfa_model_forward_max_batch is the model's own:
+ * the same for a KFPN model; for a SFA_BACKBONE_DECONV model the widest conv input is the heads'
+ * 256-channel (H/4, W/4) map, 64 H W bytes per frame, so a pass holds floor((2^31 - 1) / (64 H W))
+ * frames: 90 at 608 x 608 (needs a handle only, no device).  The workspace size, the pass chunking and
+ * the buffer offsets of a model follow its own limit. */
 enum sfa_input_layout { SFA_IN_NCHW3 = 0, SFA_IN_NHWC4 = 1, SFA_IN_NCHW3_FLIP_HW = 2 };
 int sfa_forward_max_batch(int height, int width);
+int sfa_model_forward_max_batch(const sfa_model* model, int height, int width);
 size_t sfa_forward_workspace_size(const sfa_model* model, int batch, int height, int width);
 int sfa_model_forward(const sfa_model* model, const float* x, int in_layout, int batch, int height,
                       int width, float* const* head_out, void* workspace, size_t workspace_bytes,
@@ -251,12 +294,17 @@ int sfa_model_forward(const sfa_model* model, const float* x, int in_layout, int
  * stream inside sfa_model_forward, before the KFPN combine, on failure too; so work ordered after the
  * forward on the caller's stream (or a synchronisation of that stream alone) sees every buffer
  * complete; a device-wide synchronisation is sufficient, not required.  Another stream needs an event.
+ * SFA_BACKBONE_DECONV models: LAYER1..4 as above; DECONV1..3 = the three transposed-conv stage outputs
+ * after BN + ReLU (resnet.py:230 deconv_layers[2], [5], [8]), NHWC float32 (B, H/16, W/16, 256),
+ * (B, H/8, W/8, 256), (B, H/4, W/4, 256) — DECONV3 is the heads' input.  UP_LEVEL* and HEADS_L* do not
+ * exist there (-1), as DECONV* do not on a KFPN model (-1).
  * The offsets are those of one pass: for batch > sfa_forward_max_batch the buffers hold the last pass
  * only, at the offsets of a batch of sfa_forward_max_batch frames. */
 enum sfa_buffer {
   SFA_BUF_LAYER1 = 0, SFA_BUF_LAYER2, SFA_BUF_LAYER3, SFA_BUF_LAYER4,
   SFA_BUF_UP_LEVEL2, SFA_BUF_UP_LEVEL3, SFA_BUF_UP_LEVEL4,
-  SFA_BUF_HEADS_L0, SFA_BUF_HEADS_L1, SFA_BUF_HEADS_L2
+  SFA_BUF_HEADS_L0, SFA_BUF_HEADS_L1, SFA_BUF_HEADS_L2,
+  SFA_BUF_DECONV1, SFA_BUF_DECONV2, SFA_BUF_DECONV3
 };
 int64_t sfa_forward_buffer_offset(const sfa_model* model, int batch, int height, int width,
                                   int which);

@@ -20,6 +20,8 @@ int launch_maxpool3s2(const float* x, float* y, int B, int H, int W, int C, hipS
 int launch_upsample2x(const float* x, float* y, int B, int H, int W, int C, hipStream_t st);
 int launch_kfpn(const float* L0, const float* L1, const float* L2, const KfpnOut& o, int B, int h,
                 int w, hipStream_t st);
+// channel-planar heads block L[total_ch][B][h w] -> each head's own NCHW (B, ch, h, w) buffer
+int launch_heads_relayout(const float* L, const KfpnOut& o, int B, int h, int w, hipStream_t st);
 int launch_sigmoid_clamp(float* x, long long n, hipStream_t st);
 // Zero `bytes` (a multiple of 4, 4-B aligned) of device memory with a kernel instead of
 // hipMemsetAsync: on this ROCm a memset captured into a single-branch HIP graph is replayed from a

@@ -273,6 +273,37 @@ int launch_kfpn(const float* L0, const float* L1, const float* L2, const KfpnOut
   return SFA_OK;
 }
 
+// Plain resnet_18 heads (models/resnet.py:231-233): the fused-heads launch writes one channel-planar
+// block L[total_ch][B][h w]; each head's channels go to its own NCHW (B, ch, h, w) buffer.
+__global__ void __launch_bounds__(256) heads_relayout_kernel(const float* __restrict__ L, const KfpnOut o, int B,
+                                                             int P) {
+  const int i = blockIdx.x * 256 + threadIdx.x;  // pixel
+  const int b = blockIdx.y, c = blockIdx.z;      // frame, planar channel
+  if (i >= P) return;
+  int head = 0;
+#pragma unroll
+  for (int j = 1; j < SFA_MAX_HEADS; ++j)
+    if (j < o.num_heads && c >= o.off[j]) head = j;
+  float* dst = o.ptr[0];
+  int ch = o.ch[0], off = o.off[0];
+#pragma unroll
+  for (int j = 1; j < SFA_MAX_HEADS; ++j)
+    if (j == head) {
+      dst = o.ptr[j];
+      ch = o.ch[j];
+      off = o.off[j];
+    }
+  dst[((size_t)b * ch + (c - off)) * P + i] = L[((size_t)c * B + b) * P + i];
+}
+
+int launch_heads_relayout(const float* L, const KfpnOut& o, int B, int h, int w, hipStream_t st) {
+  SFA_CHECK_ARG(B <= 65535 && o.total_ch <= 65535, "heads relayout: grid too large");
+  hipLaunchKernelGGL(heads_relayout_kernel, dim3((unsigned)((h * w + 255) / 256), (unsigned)B, (unsigned)o.total_ch),
+                     dim3(256), 0, st, L, o, B, h * w);
+  SFA_LAUNCH_CHECK();
+  return SFA_OK;
+}
+
 __global__ void zero_words_kernel(uint4* __restrict__ p4, long long n4, unsigned* __restrict__ tail, int ntail) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n4) p4[i] = make_uint4(0u, 0u, 0u, 0u);

@@ -282,6 +282,23 @@ __device__ __forceinline__ float res_up_sample(const ConvArgs& a, int m, int n) 
   return fmaf(ly0, fmaf(lx0, a00, lx1 * a01), ly1 * fmaf(lx0, a10, lx1 * a11));  // as r3t_epilogue_std
 }
 
+// Transposed convolution k=4 / s=2 / p=1 + folded BN + ReLU, fp16x3 (deconv_h3_kernel.h): the four
+// output parities as four 2 x 2 convolutions of the input, one launch.
+struct DeconvArgs {
+  const float* x;          // input NHWC (B, H, W, C), C a power of two, multiple of 32
+  int H, W, C, logC;
+  unsigned bytes;          // size of x in bytes (< 2^31): buffer-load range, OOB -> 0
+  const uint16_t* wh;      // [4 phases][2 terms][N][K] fp16, K = 4 C; phase = 2 py + px
+  const float* winv;       // [4][N]
+  const float* bias;       // [N]
+  const unsigned* amax_in; // per-frame max |x| words of the input (conv.h), or null (scale 1)
+  unsigned* amax_out;      // per-frame max |y| words of the output, or null
+  float* y;                // output NHWC (B, 2H, 2W, N)
+  int M, N, K;             // M = B H W rows per phase
+  FastDiv fd_w, fd_h;
+};
+int launch_deconv(const DeconvArgs& a, int B, hipStream_t stream);
+
 int launch_conv(const ConvArgs& a, int epilogue, int math, hipStream_t stream);
 // fp16x3 stem 7x7/s2 + BN + ReLU + max-pool 3x3/s2 in one kernel over 16 x 16 patches + a merge
 // pass (stem_patch_kernel.h); SFA_E_UNSUPPORTED if the stem's shape does not tile 16 x 16.

@@ -7,6 +7,7 @@
 #include "conv_h3_kernel.h"
 #include "conv_h3s_kernel.h"
 #include "conv_r3_kernel.h"
+#include "deconv_h3_kernel.h"
 #include "fpn_kernel.h"
 #include "stem_patch_kernel.h"
 
@@ -296,6 +297,8 @@ int launch_conv(const ConvArgs& a, int epilogue, int math, hipStream_t st) {
   }
   return launch_conv_cfg<64, 64, 32, 32, 16, EPI_STD, 4>(a, st);
 }
+
+int launch_deconv(const DeconvArgs& a, int B, hipStream_t st) { return launch_deconv_h3_cfg(a, B, st); }
 
 int launch_stem_patch(const ConvArgs& a, hipStream_t st) { return launch_stem_patch_pool(a, st); }
 

@@ -1,7 +1,9 @@
-// FPN-ResNet-18 (KFPN) model: reference state_dict layout, host-side weight
-// packing (BatchNorm folding + OHWI re-layout) and the forward orchestration.
+// FPN-ResNet-18 (KFPN) and plain ResNet-18 (deconv) models: reference state_dict layout, host-side
+// weight packing (BatchNorm folding + OHWI re-layout) and the forward orchestration.  The two
+// families (sfa_backbone) share the stem and the residual layers; what follows layer4 differs.
 //
 // Reference: models/fpn_resnet.py:112-301 (PoseResNet, BasicBlock, get_pose_net),
+//            models/resnet.py:115-284 (the plain PoseResNet: three transposed convs, one head level),
 //            models/model_utils.py:25-43 (create_model).
 #include <algorithm>
 #include <cmath>
@@ -42,10 +44,11 @@ static int64_t numel(const Entry& e) {
 
 static const int kFpnC[3] = {256, 128, 64};
 
-static int check_arch(const sfa_arch* a) {
+static int check_arch(const sfa_arch* a, int backbone = SFA_BACKBONE_KFPN) {
   SFA_CHECK_ARG(a != nullptr, "arch is null");
   if (a->num_layers != 18) {
-    set_error("only fpn_resnet_18 is implemented (got %d layers)", a->num_layers);
+    set_error("only %s is implemented (got %d layers)", backbone == SFA_BACKBONE_DECONV ? "resnet_18" : "fpn_resnet_18",
+              a->num_layers);
     return SFA_E_UNSUPPORTED;
   }
   if (a->head_conv != 64) {
@@ -63,6 +66,15 @@ static int check_arch(const sfa_arch* a) {
   return SFA_OK;
 }
 
+// The extended descriptor: the base checks of its family; reserved words zero, a known backbone.
+static int check_arch_ex(const sfa_arch_ex* x) {
+  SFA_CHECK_ARG(x != nullptr, "arch is null");
+  SFA_CHECK_ARG(x->backbone == SFA_BACKBONE_KFPN || x->backbone == SFA_BACKBONE_DECONV, "unknown backbone %d",
+                x->backbone);
+  for (int r : x->reserved) SFA_CHECK_ARG(r == 0, "sfa_arch_ex.reserved must be zero");
+  return check_arch(&x->base, x->backbone);
+}
+
 static std::vector<int> sorted_heads(const sfa_arch* a) {
   std::vector<int> idx(a->num_heads);
   for (int j = 0; j < a->num_heads; ++j) idx[j] = j;
@@ -72,8 +84,10 @@ static std::vector<int> sorted_heads(const sfa_arch* a) {
   return idx;
 }
 
-// nn.Module registration order of PoseResNet (fpn_resnet.py:114-151, 42-53).
-static std::vector<Entry> state_layout(const sfa_arch* a) {
+// nn.Module registration order of PoseResNet (fpn_resnet.py:114-151, 42-53; resnet.py:117-158 for
+// the deconv family: deconv_layers.{0,3,6} ConvTranspose2d (Cin, 256, 4, 4), .{1,4,7} BatchNorm, then
+// the heads under their plain names).
+static std::vector<Entry> state_layout(const sfa_arch* a, int backbone = SFA_BACKBONE_KFPN) {
   std::vector<Entry> v;
   auto bn = [&](const std::string& p, int64_t c) {
     v.push_back({p + ".weight", {c}});
@@ -101,13 +115,27 @@ static std::vector<Entry> state_layout(const sfa_arch* a) {
     }
     inplanes = planes;
   }
+  const auto order = sorted_heads(a);
+  if (backbone == SFA_BACKBONE_DECONV) {
+    for (int i = 0; i < 3; ++i) {
+      v.push_back({"deconv_layers." + std::to_string(3 * i) + ".weight", {i == 0 ? 512 : 256, 256, 4, 4}});
+      bn("deconv_layers." + std::to_string(3 * i + 1), 256);
+    }
+    for (int j : order) {
+      const std::string p = a->head_names[j];
+      v.push_back({p + ".0.weight", {a->head_conv, 256, 3, 3}});
+      v.push_back({p + ".0.bias", {a->head_conv}});
+      v.push_back({p + ".2.weight", {a->head_channels[j], a->head_conv, 1, 1}});
+      v.push_back({p + ".2.bias", {a->head_channels[j]}});
+    }
+    return v;
+  }
   const int up_out[3] = {256, 128, 64}, up_in[3] = {768, 384, 192};
   for (int i = 0; i < 3; ++i) {
     const std::string p = "conv_up_level" + std::to_string(i + 1);
     v.push_back({p + ".weight", {up_out[i], up_in[i], 1, 1}});
     v.push_back({p + ".bias", {up_out[i]}});
   }
-  const auto order = sorted_heads(a);
   for (int f = 0; f < 3; ++f)
     for (int j : order) {
       const std::string p = "fpn" + std::to_string(f) + "_" + a->head_names[j];
@@ -131,16 +159,27 @@ struct PHeads {
   size_t w3, b3, w1, b1, wx, wh, winv;
   int N, K;
 };
+// One transposed conv (deconv_h3_kernel.h): w = the four phase matrices [4][N][K] f32, K = 4 C in
+// (dy, dx, c) order, BN scale folded in; b = the BN shift [N]; wh = [4][2][N][K] fp16 terms and
+// winv = [4][N], split per phase and row.
+struct PDeconv {
+  size_t w, b, wh, winv;
+  int N, C, K;
+};
 struct Plan {
+  int backbone;
   PConv stem;
   PConv blk[4][2][2];  // [layer][block][conv1, conv2(+downsample)]
-  PConv fpn[3];
-  PHeads heads[3];
+  PConv fpn[3];        // KFPN
+  PDeconv dec[3];      // deconv family
+  PHeads heads[3];     // KFPN: per level; deconv family: heads[0] alone (256 channels in)
   size_t total;
 };
 
-static Plan make_plan(const sfa_arch* a) {
+static Plan make_plan(const sfa_arch* a, int backbone = SFA_BACKBONE_KFPN) {
   Plan p;
+  memset(&p, 0, sizeof p);
+  p.backbone = backbone;
   size_t cur = 0;
   auto take = [&](size_t n) {
     const size_t o = cur;
@@ -171,10 +210,24 @@ static Plan make_plan(const sfa_arch* a) {
     }
     inplanes = planes;
   }
-  p.fpn[0] = conv(256, 768);
-  p.fpn[1] = conv(128, 384);
-  p.fpn[2] = conv(64, 192);
-  for (int f = 0; f < 3; ++f) {
+  const bool deconv = backbone == SFA_BACKBONE_DECONV;
+  if (deconv) {
+    for (int i = 0; i < 3; ++i) {
+      PDeconv& d = p.dec[i];
+      d.N = 256;
+      d.C = i == 0 ? 512 : 256;
+      d.K = 4 * d.C;
+      d.w = take((size_t)4 * d.N * d.K);
+      d.b = take(d.N);
+      d.wh = take((size_t)4 * d.N * d.K);
+      d.winv = take((size_t)4 * d.N);
+    }
+  } else {
+    p.fpn[0] = conv(256, 768);
+    p.fpn[1] = conv(128, 384);
+    p.fpn[2] = conv(64, 192);
+  }
+  for (int f = 0; f < (deconv ? 1 : 3); ++f) {
     PHeads& h = p.heads[f];
     h.N = a->num_heads * a->head_conv;
     h.K = 9 * kFpnC[f];
@@ -279,6 +332,7 @@ using namespace sfa;
 
 struct sfa_model {
   sfa_arch arch;
+  int backbone = SFA_BACKBONE_KFPN;  // sfa_backbone: what follows layer4
   const float* w;
   Plan plan;
   int math;
@@ -310,7 +364,8 @@ struct sfa_model {
   // on the stream that launches it (never while that stream is being captured); PROBE_SERIAL
   // keeps every launch on the caller's stream so each head launch has the chip to itself.
   int probe = 0;
-  hipEvent_t probe_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // (a deconv model: pairs 0..2 around its three transposed convs, pair 3 around its heads launch)
+  hipEvent_t probe_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 // The model's side stream(s) and their events, created on the current device; on failure
@@ -340,16 +395,22 @@ static void make_side_streams(sfa_model* m) {
 extern "C" int sfa_abi_version(void) { return SFA_ABI_VERSION; }
 extern "C" const char* sfa_last_error_string(void) { return g_err.c_str(); }
 
+// The six layout / pack / create entry points: the sfa_arch forms are the SFA_BACKBONE_KFPN case of
+// the sfa_arch_ex forms (one implementation each, by family).
 extern "C" int sfa_state_count(const sfa_arch* arch) {
   if (check_arch(arch) != SFA_OK) return -1;
   return (int)state_layout(arch).size();
 }
 
-extern "C" int sfa_state_entry(const sfa_arch* arch, int index, char* name, int name_len,
-                               int64_t* shape4, int* ndim) {
-  int rc = check_arch(arch);
-  if (rc != SFA_OK) return rc;
-  const auto v = state_layout(arch);
+extern "C" int sfa_state_count_ex(const sfa_arch_ex* x) {
+  if (check_arch_ex(x) != SFA_OK) return -1;
+  return (int)state_layout(&x->base, x->backbone).size();
+}
+
+static int state_entry(const sfa_arch* arch, int backbone, int index, char* name, int name_len, int64_t* shape4,
+                       int* ndim) {
+  SFA_CHECK_ARG(shape4 && ndim, "state_entry: null argument");
+  const auto v = state_layout(arch, backbone);
   SFA_CHECK_ARG(index >= 0 && index < (int)v.size(), "state index %d out of range", index);
   const Entry& e = v[index];
   SFA_CHECK_ARG(name && name_len > (int)e.name.size(), "name buffer too small");
@@ -359,12 +420,35 @@ extern "C" int sfa_state_entry(const sfa_arch* arch, int index, char* name, int 
   return SFA_OK;
 }
 
-extern "C" size_t sfa_state_floats(const sfa_arch* arch) {
-  if (check_arch(arch) != SFA_OK) return 0;
+extern "C" int sfa_state_entry(const sfa_arch* arch, int index, char* name, int name_len,
+                               int64_t* shape4, int* ndim) {
+  int rc = check_arch(arch);
+  if (rc != SFA_OK) return rc;
+  return state_entry(arch, SFA_BACKBONE_KFPN, index, name, name_len, shape4, ndim);
+}
+
+extern "C" int sfa_state_entry_ex(const sfa_arch_ex* x, int index, char* name, int name_len, int64_t* shape4,
+                                  int* ndim) {
+  int rc = check_arch_ex(x);
+  if (rc != SFA_OK) return rc;
+  return state_entry(&x->base, x->backbone, index, name, name_len, shape4, ndim);
+}
+
+static size_t state_floats_of(const sfa_arch* arch, int backbone) {
   size_t n = 0;
-  for (const auto& e : state_layout(arch))
+  for (const auto& e : state_layout(arch, backbone))
     if (e.name.find("num_batches_tracked") == std::string::npos) n += numel(e);
   return n;
+}
+
+extern "C" size_t sfa_state_floats(const sfa_arch* arch) {
+  if (check_arch(arch) != SFA_OK) return 0;
+  return state_floats_of(arch, SFA_BACKBONE_KFPN);
+}
+
+extern "C" size_t sfa_state_floats_ex(const sfa_arch_ex* x) {
+  if (check_arch_ex(x) != SFA_OK) return 0;
+  return state_floats_of(&x->base, x->backbone);
 }
 
 extern "C" size_t sfa_packed_floats(const sfa_arch* arch) {
@@ -372,21 +456,24 @@ extern "C" size_t sfa_packed_floats(const sfa_arch* arch) {
   return make_plan(arch).total;
 }
 
-extern "C" int sfa_pack_weights(const sfa_arch* arch, const float* state, size_t state_floats,
-                                float* packed) {
-  int rc = check_arch(arch);
-  if (rc != SFA_OK) return rc;
+extern "C" size_t sfa_packed_floats_ex(const sfa_arch_ex* x) {
+  if (check_arch_ex(x) != SFA_OK) return 0;
+  return make_plan(&x->base, x->backbone).total;
+}
+
+static int pack_weights(const sfa_arch* arch, int backbone, const float* state, size_t state_floats, float* packed) {
   SFA_CHECK_ARG(state && packed, "pack: null argument");
-  SFA_CHECK_ARG(state_floats == sfa_state_floats(arch), "pack: expected %zu state floats, got %zu",
-                sfa_state_floats(arch), state_floats);
+  SFA_CHECK_ARG(state_floats == state_floats_of(arch, backbone), "pack: expected %zu state floats, got %zu",
+                state_floats_of(arch, backbone), state_floats);
+  const bool deconv = backbone == SFA_BACKBONE_DECONV;
   StateView s;
   size_t off = 0;
-  for (const auto& e : state_layout(arch)) {
+  for (const auto& e : state_layout(arch, backbone)) {
     if (e.name.find("num_batches_tracked") != std::string::npos) continue;
     s.m[e.name] = {state + off, e};
     off += numel(e);
   }
-  const Plan p = make_plan(arch);
+  const Plan p = make_plan(arch, backbone);
   std::fill(packed, packed + p.total, 0.f);
   std::vector<double> sc, sh, sc2, sh2;
 
@@ -420,8 +507,29 @@ extern "C" int sfa_pack_weights(const sfa_arch* arch, const float* state, size_t
     }
     inplanes = planes;
   }
+  // deconv family: ConvTranspose2d weight (Cin, Cout, 4, 4) -> phase (py, px) matrix
+  // W[n][(2 dy + dx) C + c] = w[c][n][3 - py - 2 dy][3 - px - 2 dx] * BN scale[n] (deconv_h3_kernel.h)
+  for (int i = 0; deconv && i < 3; ++i) {
+    const PDeconv& d = p.dec[i];
+    const float* w = s.get("deconv_layers." + std::to_string(3 * i) + ".weight");
+    bn_fold(s, "deconv_layers." + std::to_string(3 * i + 1), d.N, sc, sh);
+    for (int ph = 0; ph < 4; ++ph) {
+      const int py = ph >> 1, px = ph & 1;
+      float* Wp = packed + d.w + (size_t)ph * d.N * d.K;
+      for (int n = 0; n < d.N; ++n)
+        for (int dy = 0; dy < 2; ++dy)
+          for (int dx = 0; dx < 2; ++dx)
+            for (int c = 0; c < d.C; ++c) {
+              const double v = w[(((size_t)c * d.N + n) * 4 + (3 - py - 2 * dy)) * 4 + (3 - px - 2 * dx)];
+              Wp[(size_t)n * d.K + (2 * dy + dx) * d.C + c] = (float)(v * sc[n]);
+            }
+      split_terms_h3(Wp, d.N, d.K, reinterpret_cast<uint16_t*>(packed + d.wh) + (size_t)ph * 2 * d.N * d.K,
+                     packed + d.winv + (size_t)ph * d.N);
+    }
+    for (int n = 0; n < d.N; ++n) packed[d.b + n] = (float)sh[n];
+  }
   const int up_out[3] = {256, 128, 64}, up_in[3] = {768, 384, 192};
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; !deconv && i < 3; ++i) {
     const std::string pre = "conv_up_level" + std::to_string(i + 1);
     std::vector<double> one(up_out[i], 1.0);
     put_conv(packed + p.fpn[i].w, p.fpn[i].Kpad, 0, s.get(pre + ".weight"), up_out[i], up_in[i], 1,
@@ -429,11 +537,13 @@ extern "C" int sfa_pack_weights(const sfa_arch* arch, const float* state, size_t
     const float* b = s.get(pre + ".bias");
     for (int o = 0; o < up_out[i]; ++o) packed[p.fpn[i].b + o] = b[o];
   }
-  for (int f = 0; f < 3; ++f) {
+  const int nlev = deconv ? 1 : 3;  // head levels
+  for (int f = 0; f < nlev; ++f) {
     const PHeads& hp = p.heads[f];
     std::vector<double> one(arch->head_conv, 1.0);
     for (int j = 0; j < arch->num_heads; ++j) {
-      const std::string pre = "fpn" + std::to_string(f) + "_" + arch->head_names[j];
+      const std::string pre = deconv ? std::string(arch->head_names[j])
+                                     : "fpn" + std::to_string(f) + "_" + arch->head_names[j];
       put_conv(packed + hp.w3 + (size_t)j * 64 * hp.K, hp.K, 0, s.get(pre + ".0.weight"), 64,
                kFpnC[f], 3, 3, kFpnC[f], one);
       const float* b3 = s.get(pre + ".0.bias");
@@ -456,8 +566,8 @@ extern "C" int sfa_pack_weights(const sfa_arch* arch, const float* state, size_t
   for (int li = 0; li < 4; ++li)
     for (int bi = 0; bi < 2; ++bi)
       for (int ci = 0; ci < 2; ++ci) split(p.blk[li][bi][ci]);
-  for (int i = 0; i < 3; ++i) split(p.fpn[i]);
-  for (int f = 0; f < 3; ++f) {
+  for (int i = 0; !deconv && i < 3; ++i) split(p.fpn[i]);
+  for (int f = 0; f < nlev; ++f) {
     const PHeads& hp = p.heads[f];
     split_terms(packed + hp.w3, (size_t)hp.N * hp.K, reinterpret_cast<uint16_t*>(packed + hp.wx));
     split_terms_h3(packed + hp.w3, hp.N, hp.K, reinterpret_cast<uint16_t*>(packed + hp.wh),
@@ -466,14 +576,26 @@ extern "C" int sfa_pack_weights(const sfa_arch* arch, const float* state, size_t
   return SFA_OK;
 }
 
-extern "C" int sfa_model_create(const sfa_arch* arch, const float* packed_device, sfa_model** out) {
+extern "C" int sfa_pack_weights(const sfa_arch* arch, const float* state, size_t state_floats,
+                                float* packed) {
   int rc = check_arch(arch);
   if (rc != SFA_OK) return rc;
+  return pack_weights(arch, SFA_BACKBONE_KFPN, state, state_floats, packed);
+}
+
+extern "C" int sfa_pack_weights_ex(const sfa_arch_ex* x, const float* state, size_t state_floats, float* packed) {
+  int rc = check_arch_ex(x);
+  if (rc != SFA_OK) return rc;
+  return pack_weights(&x->base, x->backbone, state, state_floats, packed);
+}
+
+static int model_create(const sfa_arch* arch, int backbone, const float* packed_device, sfa_model** out) {
   SFA_CHECK_ARG(packed_device && out, "model_create: null argument");
   sfa_model* m = new sfa_model;
   m->arch = *arch;
+  m->backbone = backbone;
   m->w = packed_device;
-  m->plan = make_plan(arch);
+  m->plan = make_plan(arch, backbone);
   m->math = SFA_MATH_FP16X3;
   // A/B convenience: the environment seeds the options once, here (sfa_model_set_option
   // overrides them; nothing reads the environment on the launch path)
@@ -483,9 +605,22 @@ extern "C" int sfa_model_create(const sfa_arch* arch, const float* packed_device
   if (const char* e = getenv("SFA_SPLITK_TICKETS")) m->splitk_tickets = atoi(e) != 0;
   bool side_streams = true;  // env SFA_SIDE_STREAMS=0: every launch on the caller's stream (A/B)
   if (const char* e = getenv("SFA_SIDE_STREAMS")) side_streams = strcmp(e, "0") != 0;
-  if (side_streams) make_side_streams(m);
+  // the deconv family has no parallel branch: no side streams, every launch on the caller's stream
+  if (side_streams && backbone == SFA_BACKBONE_KFPN) make_side_streams(m);
   *out = m;
   return SFA_OK;
+}
+
+extern "C" int sfa_model_create(const sfa_arch* arch, const float* packed_device, sfa_model** out) {
+  int rc = check_arch(arch);
+  if (rc != SFA_OK) return rc;
+  return model_create(arch, SFA_BACKBONE_KFPN, packed_device, out);
+}
+
+extern "C" int sfa_model_create_ex(const sfa_arch_ex* x, const float* packed_device, sfa_model** out) {
+  int rc = check_arch_ex(x);
+  if (rc != SFA_OK) return rc;
+  return model_create(&x->base, x->backbone, packed_device, out);
 }
 
 extern "C" void sfa_model_destroy(sfa_model* model) {
@@ -498,6 +633,7 @@ extern "C" void sfa_model_destroy(sfa_model* model) {
 
 extern "C" int sfa_model_set_side_streams(sfa_model* model, int on) {
   SFA_CHECK_ARG(model, "set_side_streams: null model");
+  if (model->backbone == SFA_BACKBONE_DECONV) return SFA_OK;  // no parallel branch: nothing to switch
   std::lock_guard<std::mutex> lk(model->fork_mu);
   if (!on && model->side) {
     // the side streams' last forward must be done before they go (the caller's stream has
@@ -552,6 +688,11 @@ extern "C" int sfa_model_set_math(sfa_model* model, int math) {
   SFA_CHECK_ARG(model, "set_math: null model");
   SFA_CHECK_ARG(math == SFA_MATH_F32 || math == SFA_MATH_BF16X6 || math == SFA_MATH_FP16X3 || math == SFA_MATH_FP16,
                 "set_math: unknown mode %d", math);
+  if (model->backbone == SFA_BACKBONE_DECONV && math != SFA_MATH_FP16X3) {
+    set_error("set_math: the resnet_18 (deconv) model runs SFA_MATH_FP16X3 only: its transposed convolutions have "
+              "no f32 / bf16x6 kernel, and its SFA_MATH_FP16 error is not yet budgeted (mode %d refused)", math);
+    return SFA_E_UNSUPPORTED;
+  }
   model->math = math;
   return SFA_OK;
 }
@@ -569,7 +710,8 @@ extern "C" int sfa_model_set_probe(sfa_model* model, int flags) {
 }
 
 extern "C" int sfa_model_probe_times(const sfa_model* model, float* ms, int n) {
-  SFA_CHECK_ARG(model && ms && n >= 0 && n <= 3, "probe_times: bad arguments");
+  SFA_CHECK_ARG(model && ms && n >= 0 && n <= (model->backbone == SFA_BACKBONE_DECONV ? 4 : 3),
+                "probe_times: bad arguments");
   SFA_CHECK_ARG(model->probe & SFA_PROBE_HEADS, "probe_times: probe not enabled");
   for (int f = 0; f < n; ++f) {
     SFA_HIP_TRY(hipEventSynchronize(model->probe_ev[2 * f + 1]));
@@ -584,16 +726,18 @@ namespace sfa {
 struct Bufs {
   size_t xin, s0, p0, t[4], a[4], l[4], up1, c1, up2, c2, up3, up4, L0, L1, L2, amax, tick, tick_words, part,
       part_floats, total;
+  size_t d[3];  // deconv family: the three transposed convs' outputs (up1 .. up4, L1, L2 unused)
 };
 
 // fp16x3 activation maxima (conv.h): per tensor a conv reads (named by its producer), B
 // frames of SFA_AMAX_WORDS words.  Pooling and bilinear upsampling never raise max |x|, so their
 // outputs share their input's slot.
 enum AmaxSlot { AM_INPUT = 0, AM_STEM = 1, AM_BLK = 2 /* + 4 li + 2 bi + ci */, AM_FPN = 18,
-                AM_COUNT = 21 };
+                AM_DECONV = 18 /* deconv family, + layer */, AM_COUNT = 21 };
 
-static Bufs plan_bufs(const sfa_arch* arch, int B, int H, int W) {
+static Bufs plan_bufs(const sfa_arch* arch, int backbone, int B, int H, int W) {
   Bufs b;
+  memset(&b, 0, sizeof b);
   size_t cur = 0;
   auto take = [&](size_t floats) {
     const size_t o = cur;
@@ -612,17 +756,24 @@ static Bufs plan_bufs(const sfa_arch* arch, int B, int H, int W) {
     b.l[li] = take(n);
   }
   const size_t P8 = (size_t)(H / 8) * (W / 8), P16 = (size_t)(H / 16) * (W / 16);
-  b.up1 = take((size_t)B * P16 * 512);
-  b.c1 = take((size_t)B * P16 * 256);
-  b.up2 = take((size_t)B * P8 * 256);
-  b.c2 = take((size_t)B * P8 * 128);
-  b.up3 = take((size_t)B * P4 * 128);
-  b.up4 = take((size_t)B * P4 * 64);
   int nch = 0;
   for (int j = 0; j < arch->num_heads; ++j) nch += arch->head_channels[j];
-  b.L0 = take((size_t)nch * B * P8);
-  b.L1 = take((size_t)nch * B * P4);
-  b.L2 = take((size_t)nch * B * P4);
+  if (backbone == SFA_BACKBONE_DECONV) {
+    b.d[0] = take((size_t)B * P16 * 256);
+    b.d[1] = take((size_t)B * P8 * 256);
+    b.d[2] = take((size_t)B * P4 * 256);
+    b.L0 = take((size_t)nch * B * P4);  // the one head level, channel-planar, at (H/4, W/4)
+  } else {
+    b.up1 = take((size_t)B * P16 * 512);
+    b.c1 = take((size_t)B * P16 * 256);
+    b.up2 = take((size_t)B * P8 * 256);
+    b.c2 = take((size_t)B * P8 * 128);
+    b.up3 = take((size_t)B * P4 * 128);
+    b.up4 = take((size_t)B * P4 * 64);
+    b.L0 = take((size_t)nch * B * P8);
+    b.L1 = take((size_t)nch * B * P4);
+    b.L2 = take((size_t)nch * B * P4);
+  }
   // the activation maxima and the split-K tickets (one zeroing memset per forward, right after them)
   b.amax = take((size_t)AM_COUNT * B * SFA_AMAX_WORDS);
   // split-K tickets (conv_h3_kernel.h splitk_ticket): one word per output tile of each of the four
@@ -671,29 +822,39 @@ static ConvArgs conv_args(const float* wbase, const PConv& pc, int B, int OH, in
 // 32 H W bytes (the stem input, 12-16 H W bytes, and every other map are smaller), so a pass holds
 // floor((2^31 - 1) / (32 H W)) frames: 181 at 608 x 608. Larger batches run in passes of that
 // many frames (sfa_model_forward); frames are independent and their arithmetic batch-invariant
-// (per-frame fp16x3 scales), so the chunking changes no bit.
-static int forward_max_batch(int H, int W) {
+// (per-frame fp16x3 scales), so the chunking changes no bit.  Deconv family: the widest conv input is
+// the heads' 256-channel (H/4)(W/4) map, 64 H W bytes per frame: 90 frames at 608 x 608.
+static int forward_max_batch(int H, int W, int backbone = SFA_BACKBONE_KFPN) {
   if (H <= 0 || W <= 0) return 0;
-  const unsigned long long per_frame = 32ull * (unsigned long long)H * (unsigned long long)W;
+  const unsigned long long per_frame =
+      (backbone == SFA_BACKBONE_DECONV ? 64ull : 32ull) * (unsigned long long)H * (unsigned long long)W;
   const unsigned long long n = ((1ull << 31) - 1) / per_frame;
   return n > 0x7fffffffull ? 0x7fffffff : (int)n;
 }
 
 extern "C" int sfa_forward_max_batch(int height, int width) { return forward_max_batch(height, width); }
 
+extern "C" int sfa_model_forward_max_batch(const sfa_model* m, int height, int width) {
+  return m ? forward_max_batch(height, width, m->backbone) : 0;
+}
+
 extern "C" size_t sfa_forward_workspace_size(const sfa_model* m, int batch, int height, int width) {
   if (!m || batch <= 0 || height <= 0 || width <= 0) return 0;
-  const int bmax = forward_max_batch(height, width);
+  const int bmax = forward_max_batch(height, width, m->backbone);
   if (bmax < 1) return 0;
-  return plan_bufs(&m->arch, std::min(batch, bmax), height, width).total;
+  return plan_bufs(&m->arch, m->backbone, std::min(batch, bmax), height, width).total;
 }
 
 extern "C" int64_t sfa_forward_buffer_offset(const sfa_model* m, int batch, int height, int width,
                                              int which) {
   if (!m || batch <= 0 || height <= 0 || width <= 0) return -1;
-  const int bmax = forward_max_batch(height, width);
+  const int bmax = forward_max_batch(height, width, m->backbone);
   if (bmax < 1) return -1;
-  const Bufs b = plan_bufs(&m->arch, std::min(batch, bmax), height, width);
+  const Bufs b = plan_bufs(&m->arch, m->backbone, std::min(batch, bmax), height, width);
+  const bool deconv = m->backbone == SFA_BACKBONE_DECONV;
+  if (deconv ? (which >= SFA_BUF_UP_LEVEL2 && which <= SFA_BUF_HEADS_L2)
+             : (which >= SFA_BUF_DECONV1 && which <= SFA_BUF_DECONV3))
+    return -1;  // the other family's maps
   switch (which) {
     case SFA_BUF_LAYER1: return (int64_t)b.l[0];
     case SFA_BUF_LAYER2: return (int64_t)b.l[1];
@@ -705,6 +866,9 @@ extern "C" int64_t sfa_forward_buffer_offset(const sfa_model* m, int batch, int 
     case SFA_BUF_HEADS_L0: return (int64_t)b.L0;
     case SFA_BUF_HEADS_L1: return (int64_t)b.L1;
     case SFA_BUF_HEADS_L2: return (int64_t)b.L2;
+    case SFA_BUF_DECONV1: return (int64_t)b.d[0];
+    case SFA_BUF_DECONV2: return (int64_t)b.d[1];
+    case SFA_BUF_DECONV3: return (int64_t)b.d[2];
     default: return -1;
   }
 }
@@ -718,7 +882,7 @@ extern "C" int64_t sfa_forward_buffer_offset(const sfa_model* m, int batch, int 
 // One pass over B <= forward_max_batch(H, W) frames (arguments checked by sfa_model_forward).
 static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B, int H, int W,
                         float* const* head_out, void* workspace, void* stream) {
-  const Bufs bf = plan_bufs(&m->arch, B, H, W);
+  const Bufs bf = plan_bufs(&m->arch, m->backbone, B, H, W);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
@@ -838,9 +1002,86 @@ static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B
     w = ow;
     cin = planes;
   }
+  const int H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16;
+  if (m->backbone == SFA_BACKBONE_DECONV) {
+    // Plain resnet_18 (resnet.py:230-234): three ConvTranspose2d(4, s2, p1) + BN + ReLU, layer4 ->
+    // (H/4, W/4, 256), one launch each (deconv_h3_kernel.h); then every head in one fused launch
+    // (conv3x3 -> ReLU -> conv1x1, the KFPN level-0 heads kernel's shape) into a channel-planar block,
+    // and its relayout into the caller's per-head buffers.  All on the caller's stream.
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool probe = (m->probe & SFA_PROBE_HEADS) && hipStreamIsCapturing(st, &cap) == hipSuccess &&
+                       cap == hipStreamCaptureStatusNone;
+    const float* dx = F(bf.l[3]);
+    int dslot = blk_slot(3, 1, 1), dh = H / 32, dw = W / 32;
+    for (int i = 0; i < 3; ++i) {
+      const PDeconv& pd = p.dec[i];
+      DeconvArgs d;
+      memset(&d, 0, sizeof d);
+      d.x = dx;
+      d.H = dh;
+      d.W = dw;
+      d.C = pd.C;
+      d.logC = ilog2(pd.C);
+      d.bytes = (unsigned)((size_t)B * dh * dw * pd.C * 4);  // <= 16 H W bytes per frame: inside the pass limit
+      d.wh = reinterpret_cast<const uint16_t*>(wb + pd.wh);
+      d.winv = wb + pd.winv;
+      d.bias = wb + pd.b;
+      d.amax_in = AM(dslot);
+      d.amax_out = AM(AM_DECONV + i);
+      d.y = F(bf.d[i]);
+      d.M = B * dh * dw;
+      d.N = pd.N;
+      d.K = pd.K;
+      if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[2 * i], st));
+      SFA_RC(launch_deconv(d, B, st));
+      if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[2 * i + 1], st));
+      dx = F(bf.d[i]);
+      dslot = AM_DECONV + i;
+      dh *= 2;
+      dw *= 2;
+    }
+    int hoff[SFA_MAX_HEADS] = {0};
+    int nch = 0;
+    for (int j = 0; j < m->arch.num_heads; ++j) {
+      hoff[j] = nch;
+      nch += m->arch.head_channels[j];
+    }
+    const PHeads& hp = p.heads[0];
+    ConvArgs a;
+    memset(&a, 0, sizeof a);
+    a.nseg = 1;
+    a.seg[0] = seg(dx, B, H4, W4, 256, 3, 1, 1);
+    a.Kpad = hp.K;
+    a.w = wb + hp.w3;
+    a.wx = reinterpret_cast<const uint16_t*>(wb + hp.wx);
+    a.wh = reinterpret_cast<const uint16_t*>(wb + hp.wh);
+    a.winv = wb + hp.winv;
+    a.amax_in[0] = AM(AM_DECONV + 2);
+    a.bias = wb + hp.b3;
+    a.M = B * H4 * W4;
+    a.N = hp.N;
+    a.OH = H4;
+    a.OW = W4;
+    a.relu = 1;
+    a.hw1 = wb + hp.w1;
+    a.hb1 = wb + hp.b1;
+    KfpnOut ko;
+    memset(&ko, 0, sizeof ko);
+    for (int j = 0; j < m->arch.num_heads; ++j) {
+      a.hch[j] = ko.ch[j] = m->arch.head_channels[j];
+      a.hoff[j] = ko.off[j] = hoff[j];
+      ko.ptr[j] = head_out[j];
+    }
+    ko.num_heads = m->arch.num_heads;
+    ko.total_ch = nch;
+    a.hout = F(bf.L0);
+    if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[6], st));
+    SFA_RC(launch_conv(a, EPI_HEAD, m->math, st));
+    if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[7], st));
+    return launch_heads_relayout(F(bf.L0), ko, B, H4, W4, st);
+  }
   // FPN top-down (fpn_resnet.py:197-210): bilinear x2 (align_corners) + channel
   // concat, read by the 1x1 conv as two K-segments (no concat buffer).
-  const int H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16;
   // fp16x3: each FPN 1x1 conv over cat(up(x), skip) runs as two convs on K-slices of its
   // packed weights, W_a up(x) + W_b skip + b = up(W_a x) + W_b skip + b (bilinear resize and a
   // 1x1 conv commute; the interpolation weights sum to 1): W_a x at the LOW resolution into a
@@ -1028,13 +1269,13 @@ extern "C" int sfa_model_forward(const sfa_model* m, const float* x, int in_layo
   SFA_CHECK_ARG(in_layout == SFA_IN_NCHW3 || in_layout == SFA_IN_NHWC4 ||
                     in_layout == SFA_IN_NCHW3_FLIP_HW,
                 "forward: bad layout");
-  const int bmax = forward_max_batch(H, W);
+  const int bmax = forward_max_batch(H, W, m->backbone);
   if (bmax < 1) {
     set_error("forward: one %d x %d frame exceeds the conv kernels' 32-bit buffer offsets", H, W);
     return SFA_E_UNSUPPORTED;
   }
   const int bc = std::min(B, bmax);
-  const size_t need = plan_bufs(&m->arch, bc, H, W).total;
+  const size_t need = plan_bufs(&m->arch, m->backbone, bc, H, W).total;
   if (workspace_bytes < need) {
     set_error("forward: workspace %zu < required %zu bytes", workspace_bytes, need);
     return SFA_E_WORKSPACE;

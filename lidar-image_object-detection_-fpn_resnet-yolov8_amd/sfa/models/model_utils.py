@@ -1,17 +1,18 @@
 """Drop-in for the reference's models/model_utils.py (create_model, :25-43).
 
-``create_model(configs)`` reads ``configs.arch`` ('fpn_resnet_18'), ``.heads``
-(dict; insertion order = forward output order), ``.head_conv`` and
+``create_model(configs)`` reads ``configs.arch`` ('fpn_resnet_18' or 'resnet_18'),
+``.heads`` (dict; insertion order = forward output order), ``.head_conv`` and
 ``.imagenet_pretrained`` exactly as the reference does and returns the
-HIP-backed ``PoseResNet``.  Error behaviour follows the reference: a bad arch
-suffix raises ``ValueError`` (:27-31), an unknown backbone fails an assertion
-(:41).  The plain ``resnet_*`` arch (models/resnet.py) is not part of this
-hot path and raises ``NotImplementedError``.
+HIP-backed ``PoseResNet`` of that family: the keypoint-FPN model
+(models/fpn_resnet.py) or the plain CenterNet-style one (models/resnet.py).
+Error behaviour follows the reference: a bad arch suffix raises ``ValueError``
+(:27-31), an unknown backbone fails an assertion (:41).  Depths other than 18
+raise ``NotImplementedError`` in both families.
 """
 
 from __future__ import annotations
 
-from models import fpn_resnet
+from models import fpn_resnet, resnet
 from sfa_hip import dropin as _dropin
 
 
@@ -26,7 +27,9 @@ def create_model(configs):
                                        head_conv=configs.head_conv,
                                        imagenet_pretrained=configs.imagenet_pretrained)
     if "resnet" in configs.arch:
-        raise NotImplementedError("plain resnet_* (models/resnet.py) is outside the gfx950 hot path")
+        print("using ResNet architecture")
+        return resnet.get_pose_net(num_layers=num_layers, heads=configs.heads, head_conv=configs.head_conv,
+                                   imagenet_pretrained=configs.imagenet_pretrained)
     assert False, "Undefined model backbone"
 
 

@@ -45,6 +45,27 @@ class SfaArch(ctypes.Structure):
     ]
 
 
+BACKBONE_KFPN, BACKBONE_DECONV = 0, 1  # include/sfa_hip.h sfa_backbone
+# sfa_forward_buffer_offset keys (include/sfa_hip.h sfa_buffer)
+BUF_LAYER1, BUF_UP_LEVEL2, BUF_HEADS_L0, BUF_DECONV1 = 0, 4, 7, 10
+
+
+class SfaArchEx(ctypes.Structure):
+    """sfa_arch_ex: the base descriptor + the family (fpn_resnet_18: KFPN, resnet_18: DECONV)."""
+    _fields_ = [
+        ("base", SfaArch),
+        ("backbone", ctypes.c_int),
+        ("reserved", ctypes.c_int * 7),
+    ]
+
+    # the base descriptor's fields, so engines and models read either form alike
+    num_layers = property(lambda self: self.base.num_layers)
+    head_conv = property(lambda self: self.base.head_conv)
+    num_heads = property(lambda self: self.base.num_heads)
+    head_channels = property(lambda self: self.base.head_channels)
+    head_names = property(lambda self: self.base.head_names)
+
+
 _c_size = ctypes.c_size_t
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -66,6 +87,14 @@ _PROTOS = {
     "sfa_pack_weights": (_c_int, [ctypes.POINTER(SfaArch), _vp, _c_size, _vp]),
     "sfa_model_create": (_c_int, [ctypes.POINTER(SfaArch), _vp, ctypes.POINTER(_vp)]),
     "sfa_model_destroy": (None, [_vp]),
+    "sfa_state_count_ex": (_c_int, [ctypes.POINTER(SfaArchEx)]),
+    "sfa_state_entry_ex": (_c_int, [ctypes.POINTER(SfaArchEx), _c_int, ctypes.c_char_p, _c_int,
+                                    ctypes.POINTER(_c_i64), ctypes.POINTER(_c_int)]),
+    "sfa_state_floats_ex": (_c_size, [ctypes.POINTER(SfaArchEx)]),
+    "sfa_packed_floats_ex": (_c_size, [ctypes.POINTER(SfaArchEx)]),
+    "sfa_pack_weights_ex": (_c_int, [ctypes.POINTER(SfaArchEx), _vp, _c_size, _vp]),
+    "sfa_model_create_ex": (_c_int, [ctypes.POINTER(SfaArchEx), _vp, ctypes.POINTER(_vp)]),
+    "sfa_model_forward_max_batch": (_c_int, [_vp, _c_int, _c_int]),
     "sfa_forward_max_batch": (_c_int, [_c_int, _c_int]),
     "sfa_forward_workspace_size": (_c_size, [_vp, _c_int, _c_int, _c_int]),
     "sfa_forward_buffer_offset": (_c_i64, [_vp, _c_int, _c_int, _c_int, _c_int]),
@@ -194,8 +223,15 @@ def check(rc: int, what: str) -> None:
         raise SfaNativeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
 
-def make_arch(heads: dict, head_conv: int = 64, num_layers: int = 18) -> SfaArch:
-    """heads: {name: channels} in FORWARD (insertion) order (fpn_resnet.py:220)."""
+def make_arch(heads: dict, head_conv: int = 64, num_layers: int = 18, backbone: int = None):
+    """heads: {name: channels} in FORWARD (insertion) order (fpn_resnet.py:220).  Without ``backbone``
+    the fpn_resnet descriptor (SfaArch); with it (BACKBONE_KFPN / BACKBONE_DECONV) the extended form
+    (SfaArchEx) that the *_ex entry points take — BACKBONE_DECONV is the plain resnet_18."""
+    if backbone is not None:
+        x = SfaArchEx()
+        x.base = make_arch(heads, head_conv, num_layers)
+        x.backbone = int(backbone)
+        return x
     a = SfaArch()
     a.num_layers = int(num_layers)
     a.head_conv = int(head_conv)
@@ -212,10 +248,18 @@ def make_arch(heads: dict, head_conv: int = 64, num_layers: int = 18) -> SfaArch
     return a
 
 
-def state_layout(arch: SfaArch):
+def is_ex(arch) -> bool:
+    return isinstance(arch, SfaArchEx)
+
+
+def arch_fn(arch, name: str):
+    """The entry point ``name`` for this descriptor's form (``name`` + "_ex" for an SfaArchEx)."""
+    return getattr(lib(), name + "_ex" if is_ex(arch) else name)
+
+
+def state_layout(arch):
     """[(name, shape tuple)] of the reference state_dict, from the C side."""
-    L = lib()
-    n = L.sfa_state_count(ctypes.byref(arch))
+    n = arch_fn(arch, "sfa_state_count")(ctypes.byref(arch))
     if n < 0:
         check(-1, "sfa_state_count")
     out = []
@@ -223,7 +267,7 @@ def state_layout(arch: SfaArch):
     shape = (_c_i64 * 4)()
     nd = _c_int()
     for i in range(n):
-        check(L.sfa_state_entry(ctypes.byref(arch), i, buf, 128, shape, ctypes.byref(nd)),
+        check(arch_fn(arch, "sfa_state_entry")(ctypes.byref(arch), i, buf, 128, shape, ctypes.byref(nd)),
               "sfa_state_entry")
         out.append((buf.value.decode(), tuple(int(shape[k]) for k in range(nd.value))))
     return out

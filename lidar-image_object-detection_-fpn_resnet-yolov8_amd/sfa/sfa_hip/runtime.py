@@ -57,7 +57,6 @@ def _boundary_arr(boundary: dict):
 # ------------------------------------------------------------------ weights
 def pack_state_dict(state: dict, arch) -> np.ndarray:
     """Reference-format state_dict (tensors or arrays) -> packed float32 host array."""
-    L = lib()
     layout = _lib.state_layout(arch)
     parts = []
     for name, shape in layout:
@@ -72,27 +71,30 @@ def pack_state_dict(state: dict, arch) -> np.ndarray:
             raise ValueError(f"{name}: shape {tuple(v.shape)} != {tuple(shape)}")
         parts.append(np.ascontiguousarray(v, np.float32).reshape(-1))
     flat = np.concatenate(parts) if parts else np.zeros(0, np.float32)
-    nfl = L.sfa_state_floats(ctypes.byref(arch))
+    nfl = _lib.arch_fn(arch, "sfa_state_floats")(ctypes.byref(arch))
     if flat.size != nfl:
         raise ValueError(f"state has {flat.size} floats, expected {nfl}")
-    packed = np.zeros(L.sfa_packed_floats(ctypes.byref(arch)), np.float32)
-    check(L.sfa_pack_weights(ctypes.byref(arch), flat.ctypes.data, flat.size, packed.ctypes.data),
+    packed = np.zeros(_lib.arch_fn(arch, "sfa_packed_floats")(ctypes.byref(arch)), np.float32)
+    check(_lib.arch_fn(arch, "sfa_pack_weights")(ctypes.byref(arch), flat.ctypes.data, flat.size, packed.ctypes.data),
           "sfa_pack_weights")
     return packed
 
 
 class KfpnEngine:
-    """A device copy of the packed weights + an sfa_model handle + workspace cache."""
+    """A device copy of the packed weights + an sfa_model handle + workspace cache.  ``arch`` is an
+    SfaArch (fpn_resnet_18) or an SfaArchEx (either family: BACKBONE_DECONV is the plain resnet_18, which
+    runs fp16x3 only and has no side streams)."""
 
     def __init__(self, arch, packed_host: np.ndarray, device, math=None, side_streams: bool = True):
         self.arch = arch
+        self.deconv = _lib.is_ex(arch) and arch.backbone == _lib.BACKBONE_DECONV
         self.device = torch.device(device)
         self.heads = [(arch.head_names[j].value.decode(), int(arch.head_channels[j]))
                       for j in range(arch.num_heads)]
         self.weights = torch.from_numpy(packed_host).to(self.device)
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):  # the model's side stream lives on this device
-            check(lib().sfa_model_create(ctypes.byref(arch), self.weights.data_ptr(), ctypes.byref(h)),
+            check(_lib.arch_fn(arch, "sfa_model_create")(ctypes.byref(arch), self.weights.data_ptr(), ctypes.byref(h)),
                   "sfa_model_create")
         self._h = h
         self._ws = {}
@@ -134,10 +136,11 @@ class KfpnEngine:
         pipeline as usual."""
         t = object.__new__(KfpnEngine)
         t.arch, t.device, t.heads, t.weights = self.arch, self.device, self.heads, self.weights
+        t.deconv = self.deconv
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            check(lib().sfa_model_create(ctypes.byref(self.arch), self.weights.data_ptr(), ctypes.byref(h)),
-                  "sfa_model_create")
+            check(_lib.arch_fn(self.arch, "sfa_model_create")(ctypes.byref(self.arch), self.weights.data_ptr(),
+                                                              ctypes.byref(h)), "sfa_model_create")
         t._h = h
         t._ws = {}
         t.side_streams = True
@@ -167,6 +170,11 @@ class KfpnEngine:
                 lib().sfa_model_destroy(self._h)
         except Exception:
             pass
+
+    def max_batch(self, H, W) -> int:
+        """Frames one forward pass of this model holds (sfa_model_forward_max_batch); larger batches run
+        in passes."""
+        return int(lib().sfa_model_forward_max_batch(self._h, H, W))
 
     def workspace_bytes(self, B, H, W) -> int:
         return int(lib().sfa_forward_workspace_size(self._h, B, H, W))
@@ -222,7 +230,7 @@ class KfpnEngine:
         sfa_forward_max_batch(H, W) runs in passes that share the workspace, so it has no such views:
         ValueError."""
         L = lib()
-        bmax = int(L.sfa_forward_max_batch(H, W))
+        bmax = self.max_batch(H, W)
         if B < 1 or B > bmax:
             raise ValueError(f"debug_views: batch {B} is outside 1..{bmax}, what one forward pass holds at "
                              f"{H}x{W}; the workspace keeps the maps of one pass only")
@@ -233,6 +241,10 @@ class KfpnEngine:
             return t.permute(0, 3, 1, 2)
 
         v = {f"layer{i + 1}": nhwc(i, H >> (i + 2), W >> (i + 2), 64 << i) for i in range(4)}
+        if self.deconv:  # the three transposed-conv stage outputs (the last one is the heads' input)
+            for i in range(3):
+                v[f"deconv{i + 1}"] = nhwc(_lib.BUF_DECONV1 + i, H >> (4 - i), W >> (4 - i), 256)
+            return v
         v["up_level2"] = nhwc(4, H // 8, W // 8, 256)
         v["up_level3"] = nhwc(5, H // 4, W // 4, 128)
         v["up_level4"] = nhwc(6, H // 4, W // 4, 64)

@@ -62,6 +62,9 @@ def synthetic_tensor(name: str, shape, seed: int = 0) -> np.ndarray:
     leaf = name.rsplit(".", 1)[-1]
     # BatchNorm entries are recognised by their buffer names / parent module.
     is_bn = (".bn" in name or name.startswith("bn") or ".downsample.1." in name)
+    # plain resnet_18 (models/resnet.py): deconv_layers.{0,3,6} ConvTranspose2d, .{1,4,7} BatchNorm
+    deconv = name.split(".")[1] if name.startswith("deconv_layers.") else None
+    is_bn = is_bn or deconv in ("1", "4", "7")
     if leaf == "num_batches_tracked":
         return np.zeros(shape, dtype=np.int64)
     if leaf == "running_mean":
@@ -72,6 +75,10 @@ def synthetic_tensor(name: str, shape, seed: int = 0) -> np.ndarray:
         v = 0.5 + 0.5 * u
     elif leaf == "bias" and is_bn:
         v = -0.1 + 0.2 * u
+    elif leaf == "weight" and deconv in ("0", "3", "6"):
+        # transposed conv weight (I, O, 4, 4), stride 2: each output sums 2 x 2 taps x I inputs
+        a = np.sqrt(6.0 / (4 * shape[0]))
+        v = -a + 2.0 * a * u
     elif leaf == "weight":  # conv weight (O, I, kh, kw)
         fan_in = int(np.prod(shape[1:]))
         a = np.sqrt(6.0 / fan_in)
