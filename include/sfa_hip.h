@@ -82,6 +82,55 @@ int sfa_bev_voxelize(const float* points, const int64_t* frame_offsets, int batc
                      const double* boundary, int flags, int out_layout, void* out, void* scratch,
                      size_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------- Argoverse BEV --
+ * Replaces argoverse_test2.py:198-257 makeBVFeature(points, discretization, boundary) (the same
+ * function as argoverse_test.py:199-254), for a batch of sweeps, bit for bit on float32 points:
+ * closed box test on all six sides; row = clip(trunc((maxX - x) / d), 0, H - 1), col =
+ * clip(trunc((y - minY) / d), 0, W - 1) in f32; per cell the INDEPENDENT maxima of max(0, z - minZ)
+ * and max(0, intensity) and the point count; channels (density, height, intensity) =
+ * (min(n / 10, 1), h / f32(maxZ - minZ), i / the frame's largest cell intensity when that is > 0).
+ * A frame with no point inside the box gives zeros.
+ *
+ * sfa_argo_bev_shape (HOST only, :224-225): H = int((maxX - minX) / d), W = int((maxY - minY) / d)
+ * in double.  SFA_E_INVALID for a null pointer, a non-finite value, d <= 0 or an inverted boundary
+ * (minX >= maxX, minY >= maxY, minZ > maxZ); SFA_E_UNSUPPORTED when H or W is outside
+ * [1, SFA_ARGO_BEV_MAX_DIM] (608 x 608 and the scripts' 800 x 800 are inside).
+ *
+ * sfa_argo_bev_voxelize
+ * points          device, float32 [total_points][point_stride]; columns 0..3 = x, y, z, intensity
+ * point_stride    floats per point: 3 (no intensity column: every point has intensity 0.5, :201-203)
+ *                 or >= 4 (:204-205); 0, 1, 2 and negative values are SFA_E_INVALID (the reference
+ *                 raises ValueError).  Stride 4 with 16-B aligned points is read as float4.
+ * frame_offsets   HOST, int64 [batch + 1], in points; frame b = points[off[b], off[b+1])
+ * batch           1 .. SFA_BEV_MAX_BATCH (64)
+ * boundary        HOST, double [6] = minX, maxX, minY, maxY, minZ, maxZ; discretization: metres per cell
+ * out_layout      SFA_BEV_NCHW3_F32 (B, 3, H, W) float32, the reference's map, or SFA_BEV_NHWC4_F32
+ *                 (B, H, W, 4) float32 with channel 3 = 0 (SFA_IN_NHWC4, the model's input layout);
+ *                 SFA_BEV_NCHW3_F64 is SFA_E_INVALID (the reference returns float32);
+ *                 | SFA_ARGO_BEV_FORCE_ATOMIC: the atomic path (A/B, the equivalence test).  out: 16-B aligned.
+ * scratch         device, 16-B aligned, scratch_bytes >= sfa_argo_bev_scratch_size(batch, H, W) (else
+ *                 SFA_E_WORKSPACE; the size is 0 for a batch or map out of range), ZERO on first use.
+ *                 Its first half holds the frames' intensity maxima (one word each, raised by one
+ *                 atomicMax per block of the binning pass, read by the pass that writes the map,
+ *                 zeroed again by the call's last launch) and the atomic path's 12 B per cell; every
+ *                 call leaves that half zeroed.  The second half holds the record path's regions and
+ *                 table, written before they are read and left dirty.  The halves are split by
+ *                 scratch_bytes alone, so calls of any batch and map size it holds may share one scratch.
+ * Kernels: the KITTI voxeliser's one-pass form — every 1024 points of a frame binned by strips of the
+ * map (<= 4096 cells) into the pass block's own record region (10 B per point) + a per-strip table,
+ * then one block per (frame, strip) reducing its runs in LDS — while the batch's regions fit the second
+ * half (800 x 800: ~720 k points per frame of the batch on average, at most 1 Mi in one frame);
+ * otherwise device-scope atomics on the per-cell scratch.  Both give the same bits; nothing is
+ * truncated: a frame of >= 2^32 - 1 points is SFA_E_UNSUPPORTED.  All argument errors are
+ * reported before any device call. */
+#define SFA_ARGO_BEV_MAX_DIM 2048
+#define SFA_ARGO_BEV_FORCE_ATOMIC 0x100
+int sfa_argo_bev_shape(const double* boundary, double discretization, int* H, int* W);
+size_t sfa_argo_bev_scratch_size(int batch, int H, int W);
+int sfa_argo_bev_voxelize(const float* points, int point_stride, const int64_t* frame_offsets, int batch,
+                          const double* boundary, double discretization, int out_layout, void* out,
+                          void* scratch, size_t scratch_bytes, void* stream);
+
 /* Replaces data_process/kitti_data_utils.py:228-251 get_filtered_lidar (labels=None):
  * order-preserving compaction of the points inside the inclusive box, with
  * z <- z - minZ.  points/out device float32 [n][4]; out must hold n points;

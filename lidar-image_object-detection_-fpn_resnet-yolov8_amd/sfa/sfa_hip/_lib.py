@@ -185,6 +185,15 @@ _PROTOS["sfa_bin_stream_create"] = (_c_int, [ctypes.POINTER(ctypes.c_char_p), _c
 _PROTOS["sfa_bin_stream_next"] = (_c_int, [_vp, _vp, _c_i64, ctypes.POINTER(_c_i64),
                                            ctypes.POINTER(_c_int), _vp])
 _PROTOS["sfa_bin_stream_destroy"] = (None, [_vp])
+# Argoverse makeBVFeature (include/sfa_hip.h "Argoverse BEV")
+ARGO_BEV_MAX_DIM = 2048
+ARGO_BEV_FORCE_ATOMIC = 0x100  # or-ed into out_layout
+_PROTOS["sfa_argo_bev_shape"] = (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_double,
+                                          ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)])
+_PROTOS["sfa_argo_bev_scratch_size"] = (_c_size, [_c_int, _c_int, _c_int])
+_PROTOS["sfa_argo_bev_voxelize"] = (_c_int, [_vp, _c_int, ctypes.POINTER(_c_i64), _c_int,
+                                             ctypes.POINTER(ctypes.c_double), ctypes.c_double, _c_int, _vp, _vp,
+                                             _c_size, _vp])
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
 _lib = None

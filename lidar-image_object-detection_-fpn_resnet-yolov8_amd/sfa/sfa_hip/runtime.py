@@ -344,6 +344,95 @@ def voxelizer(device) -> BevVoxelizer:
     return v
 
 
+# argoverse_test2.py:37-47 (the scripts' boundary: +-40 m, 0.1 m cells -> 800 x 800)
+ARGO_BOUNDARY = {"minX": -40, "maxX": 40, "minY": -40, "maxY": 40, "minZ": -3, "maxZ": 1}
+ARGO_DISCRETIZATION = 0.1
+
+
+def argo_bev_shape(boundary, discretization) -> tuple:
+    """(H, W) of makeBVFeature's map (argoverse_test2.py:224-225), from the C side (host only)."""
+    H, W = ctypes.c_int(), ctypes.c_int()
+    check(lib().sfa_argo_bev_shape(_boundary_arr(boundary), float(discretization), ctypes.byref(H),
+                                   ctypes.byref(W)), "sfa_argo_bev_shape")
+    return H.value, W.value
+
+
+class ArgoBevVoxelizer:
+    """sfa_argo_bev_voxelize (argoverse_test2.py:198-257 makeBVFeature, bit-exact) for one boundary and
+    discretization, with its (self-cleaning) scratch kept resident: a ragged batch of sweeps, packed
+    back to back, into (B, 3, H, W) or the model's (B, H, W, 4)."""
+
+    def __init__(self, device, boundary=ARGO_BOUNDARY, discretization: float = ARGO_DISCRETIZATION,
+                 max_batch: int = 1, force_atomic: bool = False):
+        """force_atomic: the global-atomic kernels instead of the record ones (same bits; A/B)."""
+        self.device = torch.device(device)
+        self.boundary = dict(boundary)
+        self.discretization = float(discretization)
+        self.H, self.W = argo_bev_shape(boundary, discretization)
+        self.force_atomic = bool(force_atomic)
+        self.max_batch = 0
+        self.scratch = None
+        self._grow(max_batch)
+
+    def _grow(self, b):
+        if b <= self.max_batch:
+            return
+        if b > _lib.SFA_BEV_MAX_BATCH:
+            raise ValueError(f"BEV batch {b} > {_lib.SFA_BEV_MAX_BATCH}")
+        self.scratch = torch.zeros(int(lib().sfa_argo_bev_scratch_size(b, self.H, self.W)), dtype=torch.uint8,
+                                   device=self.device)
+        self.max_batch = b
+
+    def out_shape(self, B: int, layout: int) -> tuple:
+        return (B, self.H, self.W, 4) if layout == _lib.BEV_NHWC4_F32 else (B, 3, self.H, self.W)
+
+    def __call__(self, points: torch.Tensor, offsets, layout: int = _lib.BEV_NCHW3_F32, out=None,
+                 stream: int = None, force_atomic: bool = None) -> torch.Tensor:
+        """points: (N, 3) (intensity 0.5) or (N, >= 4) float32 GPU tensor; offsets: B + 1 frame starts in
+        points.  ``out``: a contiguous float32 GPU tensor of out_shape(B, layout) to write into."""
+        points = _require_gpu_tensor(points, "makeBVFeature")
+        if points.ndim != 2 or points.shape[1] < 3:
+            raise ValueError(f"Invalid point cloud shape: {tuple(points.shape)}")  # the reference's error (:207)
+        if layout not in (_lib.BEV_NCHW3_F32, _lib.BEV_NHWC4_F32):
+            raise ValueError("layout must be BEV_NCHW3_F32 or BEV_NHWC4_F32")
+        offs = np.asarray(offsets, dtype=np.int64)
+        B = offs.size - 1
+        if B < 1 or offs[-1] > points.shape[0] or offs[0] < 0 or np.any(np.diff(offs) < 0):
+            raise ValueError("bad frame offsets")
+        self._grow(B)
+        shape = self.out_shape(B, layout)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()
+              or out.device != points.device):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {points.device}")
+        offs_c = (ctypes.c_int64 * (B + 1))(*offs.tolist())
+        if self.force_atomic if force_atomic is None else force_atomic:
+            layout |= _lib.ARGO_BEV_FORCE_ATOMIC
+        check(lib().sfa_argo_bev_voxelize(points.data_ptr() if points.numel() else None, points.shape[1], offs_c, B,
+                                          _boundary_arr(self.boundary), self.discretization, layout,
+                                          out.data_ptr(), self.scratch.data_ptr(), self.scratch.numel(),
+                                          stream if stream is not None else _lib.stream_ptr(self.device)),
+              "sfa_argo_bev_voxelize")
+        return out
+
+
+_argo_voxelizers = {}
+
+
+def argo_voxelizer(device, boundary, discretization) -> ArgoBevVoxelizer:
+    """The device's shared voxeliser for this boundary / discretization (the host drop-in's)."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, tuple(float(boundary[k]) for k in ("minX", "maxX", "minY", "maxY", "minZ", "maxZ")),
+           float(discretization))
+    v = _argo_voxelizers.get(key)
+    if v is None:
+        v = _argo_voxelizers[key] = ArgoBevVoxelizer(device, boundary, discretization)
+    return v
+
+
 def filter_points(points: torch.Tensor, boundary=DEFAULT_BOUNDARY) -> torch.Tensor:
     """get_filtered_lidar on the device: (N, 4) f32 -> (M, 4) f32 (order kept, z -= minZ)."""
     points = _require_gpu_tensor(points, "get_filtered_lidar")
@@ -508,13 +597,31 @@ class DetectorPipeline:
 
     def __init__(self, engine: KfpnEngine, batch: int, height: int = 608, width: int = 608,
                  K: int = 50, with_bev: bool = False, max_points: int = 0, two_sided: bool = False,
-                 boundary=DEFAULT_BOUNDARY, boundary_back=None, bev_layout: str = "nchw3"):
+                 boundary=None, boundary_back=None, bev_layout: str = "nchw3", bev: str = "kitti",
+                 discretization: float = None):
         """two_sided (with_bev only): every sweep is also voxelised with ``boundary_back``
         and flipped (demo_2_sides.py: demo_dataset.py:70-88 + demo_utils.py:110-111), so one
         run infers 2*batch maps: frames [0, batch) front, [batch, 2*batch) back.
         bev_layout (with_bev only): the voxeliser's output / the model's input — "nchw3" (the
         reference's (B, 3, 608, 608) f32, read by the patch stem directly: 3/4 of NHWC4's bytes)
-        or "nhwc4" ((B, 608, 608, 4), channel 3 = 0)."""
+        or "nhwc4" ((B, 608, 608, 4), channel 3 = 0).
+        bev (with_bev only): "kitti" (default: get_filtered_lidar + makeBEVMap, 608 x 608) or
+        "argoverse": the sweeps go through makeBVFeature (argoverse_test2.py:198-257,
+        ArgoBevVoxelizer) with ``boundary`` (default ARGO_BOUNDARY) and ``discretization`` (default
+        0.1) straight into the model's input; height x width must be that map's H x W; points may
+        have 3 columns (intensity 0.5) or >= 4; not two_sided."""
+        if bev not in ("kitti", "argoverse"):
+            raise ValueError(f"bev must be 'kitti' or 'argoverse', not {bev!r}")
+        self.bev_kind = bev
+        if bev == "argoverse":
+            if not with_bev or two_sided:
+                raise ValueError("bev='argoverse' needs with_bev and has no back view (two_sided)")
+            boundary = ARGO_BOUNDARY if boundary is None else boundary
+            discretization = ARGO_DISCRETIZATION if discretization is None else discretization
+        elif discretization is not None:
+            raise ValueError("discretization belongs to bev='argoverse' (the KITTI grid is fixed)")
+        if boundary is None:
+            boundary = DEFAULT_BOUNDARY
         self.engine = engine
         self.dev = engine.device
         self.B, self.H, self.W, self.K = batch, height, width, K
@@ -536,15 +643,21 @@ class DetectorPipeline:
             self.dec_ws = torch.empty(Decoder.workspace_bytes(nmap, dict(engine.heads)["hm_cen"], K),
                                       dtype=torch.uint8, device=self.dev)
             if with_bev:
-                if (height, width) != (608, 608):
-                    raise ValueError("the BEV grid is 608x608 (config/kitti_config.py:45-46)")
-                self.vox = BevVoxelizer(self.dev, batch)
+                if bev == "argoverse":
+                    self.vox = ArgoBevVoxelizer(self.dev, boundary, discretization, batch)
+                    if (height, width) != (self.vox.H, self.vox.W):
+                        raise ValueError(f"the boundary and discretization give a {self.vox.H}x{self.vox.W} map, "
+                                         f"the pipeline was asked for {height}x{width}")
+                else:
+                    if (height, width) != (608, 608):
+                        raise ValueError("the BEV grid is 608x608 (config/kitti_config.py:45-46)")
+                    self.vox = BevVoxelizer(self.dev, batch)
                 if bev_layout not in ("nchw3", "nhwc4"):
                     raise ValueError(f"bev_layout must be 'nchw3' or 'nhwc4', not {bev_layout!r}")
                 self.bev_layout = bev_layout
                 self.bev_fmt = _lib.BEV_NCHW3_F32 if bev_layout == "nchw3" else _lib.BEV_NHWC4_F32
                 self.in_fmt = _lib.IN_NCHW3 if bev_layout == "nchw3" else _lib.IN_NHWC4
-                shape = (nmap, 3, 608, 608) if bev_layout == "nchw3" else (nmap, 608, 608, 4)
+                shape = (nmap, 3, height, width) if bev_layout == "nchw3" else (nmap, height, width, 4)
                 self.bev = torch.empty(shape, dtype=torch.float32, device=self.dev)
                 self.points = torch.zeros((max(max_points, 1), 4), dtype=torch.float32,
                                           device=self.dev)
@@ -562,6 +675,10 @@ class DetectorPipeline:
         if len(clouds) != self.B or offs[-1] > self.points.shape[0]:
             raise ValueError("clouds do not fit the pipeline's point buffer")
         host = torch.from_numpy(np.concatenate(clouds).astype(np.float32))
+        if host.shape[1] != self.points.shape[1]:
+            if self.bev_kind != "argoverse" or host.shape[1] < 3:
+                raise ValueError(f"clouds must be (N, {self.points.shape[1]}), got (N, {host.shape[1]})")
+            self.points = torch.zeros((self.points.shape[0], host.shape[1]), dtype=torch.float32, device=self.dev)
         self.points[: offs[-1]].copy_(host)
         self.offsets = offs
 
@@ -580,8 +697,11 @@ class DetectorPipeline:
         part replays that graph (``_eager`` forces the eager launches: capture() uses it)."""
         st = _lib.stream_ptr(self.dev)
         if self.with_bev:
-            self.vox(self.points, self.offsets, boundary=self.boundary, layout=self.bev_fmt,
-                     flags=_lib.BEV_RAW, out=self.bev[: self.B], stream=st)
+            if self.bev_kind == "argoverse":
+                self.vox(self.points, self.offsets, layout=self.bev_fmt, out=self.bev, stream=st)
+            else:
+                self.vox(self.points, self.offsets, boundary=self.boundary, layout=self.bev_fmt,
+                         flags=_lib.BEV_RAW, out=self.bev[: self.B], stream=st)
             if self.two_sided:
                 self.vox(self.points, self.offsets, boundary=self.boundary_back,
                          layout=self.bev_fmt, flags=_lib.BEV_RAW | _lib.BEV_FLIP_HW,

@@ -135,3 +135,15 @@ def synthetic_point_cloud(seed: int = 1, n_elev: int = 64, n_azim: int = 1920,
     bi = hash_uniform(seed, 108, nb)
     boxes = np.stack([bx, by, bz, bi], axis=1)
     return np.concatenate([ring, boxes], axis=0).astype(np.float32)
+
+
+def synthetic_argoverse_sweep(seed: int = 1, n: int = 100_000) -> np.ndarray:
+    """The sweep above rescaled into the Argoverse scripts' box (+-40 m, argoverse_test2.py:40-47):
+    x, y halved (the rings reach 80 m), intensity 0..255 as Argoverse stores it, ``n`` points taken
+    evenly over the sweep.  (n, 4) float32; about 94 % of the points are inside the box."""
+    c = synthetic_point_cloud(seed)
+    c = c[np.linspace(0, c.shape[0] - 1, n).astype(np.int64)].copy()
+    c[:, 0] *= np.float32(0.5)
+    c[:, 1] *= np.float32(0.5)
+    c[:, 3] = np.floor(c[:, 3] * np.float32(256.0))
+    return c
