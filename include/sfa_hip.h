@@ -371,9 +371,18 @@ int sfa_sigmoid_clamp_inplace(float* x, int64_t n, void* stream);
  * dets: device float32 (B, K, 10) columns
  *   [score, xs+off0, ys+off1, z, dim0, dim1, dim2, dir0, dir1, class].
  * Ties (unspecified order in torch.topk) break by lower flat index, then lower
- * class.  Constraints: K <= 256, K <= H*W, H*W <= 36864, C <= 16.
- * workspace: sfa_decode_workspace_size(B, C, K) bytes. */
+ * class.  Constraints: K <= 256, K <= H*W, H*W <= 262144 (512 x 512, any aspect, H = 1 or W = 1
+ * included), C <= 16; a larger map is SFA_E_INVALID before any launch.  dets and workspace must
+ * not be hm itself (SFA_E_INVALID).
+ * Maps of H*W <= 36864 run the band / whole-map kernels; larger ones (the Argoverse scripts'
+ * 200 x 200 heat map of an 800 x 800 input, argoverse_test2.py:37-47) run the tiled form: a class
+ * map is cut into tiles of rows and, for W > 1024, of columns, each tile's top K is selected with
+ * a 1-cell halo, and the tile lists are merged per class, then per frame.  Same results, bit for bit.
+ * workspace: sfa_decode_workspace_size_hw(B, C, H, W, K) bytes (0 for an unsupported shape; less
+ * is SFA_E_WORKSPACE before any launch).  sfa_decode_workspace_size(B, C, K) is that value for
+ * every map of H*W <= 36864 and stays sufficient for those. */
 size_t sfa_decode_workspace_size(int batch, int num_classes, int K);
+size_t sfa_decode_workspace_size_hw(int batch, int num_classes, int height, int width, int K);
 int sfa_decode(const float* hm, const float* off, const float* dir, const float* z,
                const float* dim, int batch, int num_classes, int height, int width, int K,
                int apply_sigmoid, float* dets, void* workspace, size_t workspace_bytes,
@@ -393,7 +402,9 @@ int sfa_decode(const float* hm, const float* off, const float* dir, const float*
  *   per_channel = 1: out_scores, out_inds, out_ys, out_xs of shape (B, C, K); out_clses unused.
  * Each class's K by (value desc, index asc), then the classes' C*K by (value desc, class asc,
  * rank asc) — torch.topk's two stages, its unspecified tie order made definite.  Constraints as
- * sfa_decode (K <= 256, K <= H*W <= 36864, C <= 16); workspace sfa_topk_workspace_size(B, C, K).
+ * sfa_decode (K <= 256, K <= H*W <= 262144, C <= 16; the tiled form above 36864); workspace
+ * sfa_topk_workspace_size_hw(B, C, H, W, K) (= sfa_decode_workspace_size_hw;
+ * sfa_topk_workspace_size(B, C, K) covers H*W <= 36864).
  *
  * sfa_gather_feat replaces :29-37 _gather_feat(feat, ind) (mask None: stride_n = dim, stride_d = 1,
  * feat (B, n, dim)) and :40-44 _transpose_and_gather_feat (feat (B, dim, H, W): n = H*W,
@@ -402,6 +413,7 @@ int sfa_decode(const float* hm, const float* off, const float* dir, const float*
  * caller (torch.gather's contract). */
 int sfa_heat_nms(const float* heat, float* out, int64_t maps, int height, int width, void* stream);
 size_t sfa_topk_workspace_size(int batch, int num_classes, int K);
+size_t sfa_topk_workspace_size_hw(int batch, int num_classes, int height, int width, int K);
 int sfa_topk(const float* scores, int batch, int num_classes, int height, int width, int K, int per_channel,
              float* out_scores, int64_t* out_inds, int32_t* out_clses, float* out_ys, float* out_xs,
              void* workspace, size_t workspace_bytes, void* stream);
@@ -467,6 +479,34 @@ int sfa_project_boxes(const double* real, const float* preds, const int32_t* off
                       const sfa_calib* calib, const sfa_project_params* params,
                       int32_t* out_boxes, double* out_conf, int32_t* out_row, double* out_extent,
                       int32_t* out_offsets, void* stream);
+
+/* Argoverse: detections -> image corners (the scripts' draw_3d_bbox_on_image without the drawing).
+ *
+ * sfa_argo_project_boxes replaces argoverse_test2.py:432-436 (grid -> metres through the
+ * boundary), :355-402 create_3d_bbox_corners and :324-353 ArgoverseCalibration.project_to_image,
+ * with the draw condition of :454-458.  preds: DEVICE f32 (capacity, 8) rows
+ * [score, x, y, z, h, w, l, yaw] as sfa_post_process writes them (out_preds); offsets: that call's
+ * DEVICE int32 offsets (batch + 1 entries; rows [0, offsets[batch]) are processed, the rest of the
+ * outputs is left untouched) or NULL (all `capacity` rows).  Per row, in float32 without
+ * contraction (numpy >= 2 keeps f32 scalar arithmetic in f32):
+ *   cx = maxX - x * d, cy = y * d + minY, cz = z + minZ     (boundary as sfa_argo_bev_voxelize)
+ *   corner k = R_y(yaw) @ [+-l/2, 0 or -h, +-w/2] + [cx, cy, cz], k in the reference's order.
+ * Each corner then goes, in float64, through T_l2c (HOST, 16 doubles, 4x4 row-major) and P2 (HOST,
+ * 12 doubles, 3x4), read during the call: a corner with camera Z <= 0.1 is NaN in both
+ * coordinates, the others are (P2 cam)[0:2] / (P2 cam)[2] rounded to float32.
+ *   out_pixels    DEVICE f32 (capacity, 8, 2)
+ *   out_all8      DEVICE int32 (capacity): 1 when all eight corners are finite (the box is drawn)
+ *   out_corners3d DEVICE f32 (capacity, 8, 3) or NULL: the corners in the lidar frame
+ * One thread per corner; capacity <= 2^24.
+ *
+ * sfa_argo_project_points is project_to_image (:324-353) on its own: points DEVICE (n, 3) float32
+ * (points_f64 = 0) or float64 (1) -> out_pixels DEVICE f32 (n, 2). */
+int sfa_argo_project_boxes(const float* preds, const int32_t* offsets, int batch, int capacity,
+                           const double* boundary, double discretization, const double* T_l2c,
+                           const double* P2, float* out_pixels, int32_t* out_all8, float* out_corners3d,
+                           void* stream);
+int sfa_argo_project_points(const void* points, int points_f64, int64_t n, const double* T_l2c,
+                            const double* P2, float* out_pixels, void* stream);
 
 /* ------------------------------------------------------- .bin streaming --
  * KITTI velodyne .bin files (data_process/kitti_dataset.py:119-122

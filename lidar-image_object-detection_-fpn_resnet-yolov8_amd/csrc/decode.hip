@@ -30,13 +30,21 @@
 // own class (or band) before it in that class's (value desc, index asc) order, so it survives
 // every per-class (per-band) top-K; and torch's second stage orders equal values by class*K +
 // rank = (class asc, index asc).  Same results bit for bit as the one-block-per-class kernels.
+// The argument never uses that a part is a band of rows: it holds for ANY partition of a class
+// map into disjoint cell sets, and for any order in which partial top-K lists are merged.
+//
+// Tiled form (maps above kDecMaxHW cells, up to kTileMaxHW; decode_plan.h tile_plan): no workgroup
+// ever holds a whole class map.  decode_band_topk_kernel<.., TILED = true> takes one tile (R rows x
+// TC columns, cut in columns too where a row does not fit) plus a 1-cell halo on all four sides
+// (-inf outside the MAP, the neighbours' real values outside the tile) per workgroup; row-major
+// order inside a tile is monotone in the global flat index, so the ordered tie scan is the same.
+// decode_class_merge_kernel then reduces each (frame, class)'s NT tile lists to one sorted K-list,
+// kMergeMax / K lists per pass, and the per-frame merge + gather above run over those C lists
+// (S = 1).  By the partition argument the result equals the oracle's bit for bit.
 #include "common.h"
+#include "decode_plan.h"
 
 namespace sfa {
-
-constexpr int kDecThreads = 1024;
-constexpr int kDecMaxHW = 36864;  // 144 KiB of LDS
-constexpr int kDecMaxK = 256;
 
 __device__ __forceinline__ float sigmoid_clamp_f(float x) {
   const float s = 1.0f / (1.0f + expf(-x));
@@ -291,13 +299,6 @@ __global__ void __launch_bounds__(256) decode_merge_gather_kernel(
   }
 }
 
-constexpr int kBandThreads = 512;
-constexpr int kBandWaves = kBandThreads / 64;
-constexpr int kBandMaxTile = 8192;   // LDS floats of a band tile ((R + 2) x (W + 2), -inf border)
-constexpr int kBandMaxIPT = 8;       // band pixels per thread
-constexpr int kBandMaxLoads = 16;    // staged tile floats per thread
-constexpr int kMergeMax = 4096;      // C * S * K candidates ranked per frame
-
 // Block-wide exclusive scan of one int per thread (kBandWaves waves).
 __device__ int band_excl_scan(int v, int* wsum /*[kBandWaves]*/) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -323,10 +324,23 @@ __device__ int band_excl_scan(int v, int* wsum /*[kBandWaves]*/) {
 // the map and columns -1 / W), so the 3x3 peak test is nine unconditional reads.  Writes the
 // band's top min(K, band pixels) by (value desc, index asc) as a sorted list of K (key, index),
 // padded with sentinels (key 0, index INT_MAX), to bkey / bidx[((b * C + c) * S + s) * K + j].
-template <int ABL = 0, bool PEAK = true>
+//
+// TILED = true (maps above kDecMaxHW): grid (NY * NX, C, B), s = ty * NX + tx; the workgroup's part
+// is rows [ty*R, ..) x columns [tx*TC, min(W, tx*TC + TC)) with a halo column on both sides too.
+// The border is -inf only outside the map; inside it the halo holds the neighbouring tiles' cells.
+// Indices written are global flat indices (y * W + x).  The tile grid rides in TileGeo<TILED>: empty
+// for TILED = false, whose kernel arguments and code stay those of the band form.
+template <bool TILED>
+struct TileGeo {};
+template <>
+struct TileGeo<true> {
+  int NX, TC;  // column tiles per row of tiles, columns per tile
+};
+
+template <int ABL = 0, bool PEAK = true, bool TILED = false>
 __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
     const float* __restrict__ hm, int C, int H, int W, int K, int R, int apply_sigmoid,
-    unsigned* __restrict__ bkey, int* __restrict__ bidx) {
+    unsigned* __restrict__ bkey, int* __restrict__ bidx, TileGeo<TILED> geo) {
   __shared__ __attribute__((aligned(16))) float tile[kBandMaxTile];
   __shared__ unsigned hist[256];
   __shared__ int wsum[kBandWaves];
@@ -335,8 +349,14 @@ __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
   __shared__ int sel_idx[kDecMaxK];
   const int s = blockIdx.x, c = blockIdx.y, b = blockIdx.z, S = gridDim.x;
   const int tid = threadIdx.x;
-  const int y0 = s * R, y1 = min(H, y0 + R);
-  const int TW = W + 2;                 // tile row: column -1, 0 .. W-1, W
+  int ty = s, x0 = 0, tw = W;  // the part's row of tiles, first column, columns
+  if constexpr (TILED) {
+    ty = s / geo.NX;
+    x0 = (s - ty * geo.NX) * geo.TC;
+    tw = min(geo.TC, W - x0);
+  }
+  const int y0 = ty * R, y1 = min(H, y0 + R);
+  const int TW = tw + 2;                // tile row: column x0 - 1, x0 .. x0 + tw - 1, x0 + tw
   const int n_tile = (y1 - y0 + 2) * TW;  // tile rows y0 - 1 .. y1
   const float* src = hm + ((size_t)b * C + c) * H * W;
   {
@@ -345,7 +365,7 @@ __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
 #pragma unroll
     for (int j = 0; j < kBandMaxLoads; ++j) {
       const int i = tid + j * kBandThreads;
-      const int r = i / TW, x = i - r * TW - 1, y = y0 - 1 + r;
+      const int r = i / TW, x = x0 + i - r * TW - 1, y = y0 - 1 + r;
       const bool in = i < n_tile && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
       v[j] = in ? __builtin_nontemporal_load(src + (size_t)y * W + x) : -INFINITY;
     }
@@ -353,7 +373,7 @@ __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
     for (int j = 0; j < kBandMaxLoads; ++j) {
       const int i = tid + j * kBandThreads;
       if (i < n_tile) {
-        const int r = i / TW, x = i - r * TW - 1, y = y0 - 1 + r;
+        const int r = i / TW, x = x0 + i - r * TW - 1, y = y0 - 1 + r;
         const bool in = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;  // not the border
         tile[i] = (in && apply_sigmoid && !(ABL & 1)) ? sigmoid_clamp_f(v[j]) : v[j];
       }
@@ -362,12 +382,12 @@ __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
   __syncthreads();
   // 3x3 peak test over the band's pixels; each thread owns a contiguous index range so the
   // tie scan follows flat-index order
-  const int nb = (y1 - y0) * W;  // band pixels
+  const int nb = (y1 - y0) * tw;  // band pixels
   const int ipt = (nb + kBandThreads - 1) / kBandThreads;
   const int i0 = min(tid * ipt, nb), i1 = min(i0 + ipt, nb);
   unsigned key[kBandMaxIPT];
   {
-    int r = i0 / W, x = i0 - (i0 / W) * W;  // band row, column (walked incrementally)
+    int r = i0 / tw, x = i0 - (i0 / tw) * tw;  // band row, column (walked incrementally)
 #pragma unroll
     for (int j = 0; j < kBandMaxIPT; ++j) {
       unsigned k = 0u;
@@ -382,7 +402,7 @@ __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
           m = fmaxf(m, fmaxf(a0, fmaxf(a1, a2)));
         }
         k = fkey((m == v) ? v : v * 0.f);  // heat * keep: non-peaks become (signed) zero
-        if (++x == W) {
+        if (++x == tw) {
           x = 0;
           ++r;
         }
@@ -467,7 +487,12 @@ __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
       if (take) {
         const int slot = atomicAdd(&misc[2], 1);
         sel_key[slot] = k;
-        sel_idx[slot] = pix0 + i0 + j;
+        if constexpr (TILED) {
+          const int i = i0 + j, r = i / tw;  // a tile's pixel: row r, column i - r * tw of the part
+          sel_idx[slot] = (y0 + r) * W + x0 + (i - r * tw);
+        } else {
+          sel_idx[slot] = pix0 + i0 + j;
+        }
       }
     }
   }
@@ -598,23 +623,73 @@ __global__ void __launch_bounds__(1024) decode_band_merge_gather_kernel(
   }
 }
 
-// Band geometry: S bands of R rows (8 preferred: 384 workgroups at B = 16, C = 3) with
-// C * S * K <= kMergeMax, (R + 2) * (W + 2) <= kBandMaxTile and ceil(R * W / 512) <= kBandMaxIPT;
-// S = 0 when no band split fits (one block per class, the kernels above).
-static void band_plan(int C, int H, int W, int K, int* S_out, int* R_out) {
-  *S_out = 0;
-  *R_out = H;
-  static const int order[] = {8, 9, 10, 11, 12, 13, 14, 15, 16, 7, 6, 5, 4, 3, 2, 1};
-  for (int S : order) {
-    if (S > H) continue;
-    const int R = (H + S - 1) / S;
-    const int S_eff = (H + R - 1) / R;
-    if (C * S_eff * K > kMergeMax) continue;
-    if ((R + 2) * (W + 2) > kBandMaxTile || (R + 2) * (W + 2) > kBandMaxLoads * kBandThreads) continue;
-    if ((R * W + kBandThreads - 1) / kBandThreads > kBandMaxIPT) continue;
-    *S_out = S_eff;
-    *R_out = R;
-    return;
+// (band_plan / tile_plan: decode_plan.h)
+
+// Tiled form, first merge level.  One workgroup per (frame, class): that class's NT sorted tile
+// lists (decode_band_topk_kernel<.., TILED = true>) are reduced to one sorted K-list in (value
+// desc, index asc) order, kMergeMax / K lists per pass: a pass keeps the running result as list 0,
+// loads the next lists beside it and merges them pairwise like decode_band_merge_gather_kernel
+// (each pair's merge truncated to K; equal entries, only the sentinels, break left-first).  The
+// result goes to ckey / cidx[(b * C + c) * K + j]: the band-list layout with S = 1, which the
+// per-frame merge kernels take as it is.  It holds min(K, H*W) = K real entries (K <= H*W).
+__global__ void __launch_bounds__(1024) decode_class_merge_kernel(
+    const unsigned* __restrict__ tkey, const int* __restrict__ tidx, int NT, int K,
+    unsigned* __restrict__ ckey, int* __restrict__ cidx) {
+  __shared__ unsigned skey[2][kMergeMax];
+  __shared__ int sidx[2][kMergeMax];
+  const int g = blockIdx.x;  // frame * C + class
+  const unsigned* gk = tkey + (size_t)g * NT * K;
+  const int* gi = tidx + (size_t)g * NT * K;
+  const int G = kMergeMax / K;  // lists per pass (>= 16: K <= kDecMaxK)
+  int cur = 0, have = 0;        // have = 1: list 0 of skey[cur] is the result so far
+  for (int done = 0; done < NT;) {
+    const int take = min(G - have, NT - done);
+    for (int t = threadIdx.x; t < take * K; t += blockDim.x) {
+      skey[cur][have * K + t] = gk[(size_t)done * K + t];
+      sidx[cur][have * K + t] = gi[(size_t)done * K + t];
+    }
+    __syncthreads();
+    for (int nl = have + take; nl > 1; nl = (nl + 1) >> 1) {
+      const unsigned* ik = skey[cur];
+      const int* ii = sidx[cur];
+      unsigned* ok = skey[cur ^ 1];
+      int* oi = sidx[cur ^ 1];
+      for (int t = threadIdx.x; t < nl * K; t += blockDim.x) {
+        const int l = t / K, p = t - l * K;
+        const unsigned k = ik[t];
+        const int ci = ii[t];
+        int rank = p;
+        if (!((nl & 1) && l == nl - 1)) {  // the odd list out is carried over as it is
+          const bool left = (l & 1) == 0;
+          const unsigned* pk = ik + (l ^ 1) * K;
+          const int* pi = ii + (l ^ 1) * K;
+          int lo = 0, hi = K;  // partner entries preceding (k, ci)
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            const unsigned km = pk[mid];
+            const int im = pi[mid];
+            const bool before = km > k || (km == k && (left ? im < ci : im <= ci));
+            if (before)
+              lo = mid + 1;
+            else
+              hi = mid;
+          }
+          rank += lo;
+        }
+        if (rank < K) {
+          ok[(l >> 1) * K + rank] = k;
+          oi[(l >> 1) * K + rank] = ci;
+        }
+      }
+      __syncthreads();
+      cur ^= 1;
+    }
+    done += take;
+    have = 1;
+  }
+  for (int t = threadIdx.x; t < K; t += blockDim.x) {
+    ckey[(size_t)g * K + t] = skey[cur][t];
+    cidx[(size_t)g * K + t] = sidx[cur][t];
   }
 }
 
@@ -777,20 +852,72 @@ extern "C" size_t sfa_decode_workspace_size(int batch, int num_classes, int K) {
   return align_up(n * sizeof(unsigned), 256) + align_up(n * sizeof(int), 256);
 }
 
+extern "C" size_t sfa_decode_workspace_size_hw(int batch, int num_classes, int height, int width, int K) {
+  if (batch <= 0 || num_classes <= 0 || num_classes > 16 || K <= 0 || K > kDecMaxK || height <= 0 || width <= 0)
+    return 0;
+  const long long hw = (long long)height * width;
+  if (hw > kTileMaxHW || K > hw) return 0;
+  if (hw <= kDecMaxHW) return sfa_decode_workspace_size(batch, num_classes, K);  // the band / class kernels
+  int R, TC, NY, NX;
+  tile_plan(height, width, &R, &TC, &NY, &NX);
+  return tiled_layout(batch, num_classes, NY * NX, K).total;
+}
+
+extern "C" size_t sfa_topk_workspace_size_hw(int batch, int num_classes, int height, int width, int K) {
+  return sfa_decode_workspace_size_hw(batch, num_classes, height, width, K);
+}
+
+// Tiled form, shared by sfa_decode (PEAK) and sfa_topk: the tile lists, then one K-list per
+// (frame, class) at *ck / *ci (workspace already checked against tiled_layout().total).
+template <bool PEAK>
+static int tiled_class_lists(const float* hm, int batch, int num_classes, int height, int width, int K,
+                             int apply_sigmoid, void* workspace, hipStream_t st, unsigned** ck, int** ci) {
+  int R, TC, NY, NX;
+  tile_plan(height, width, &R, &TC, &NY, &NX);
+  const int NT = NY * NX;
+  const TiledLayout l = tiled_layout(batch, num_classes, NT, K);
+  char* ws = reinterpret_cast<char*>(workspace);
+  auto* tk = reinterpret_cast<unsigned*>(ws);
+  auto* ti = reinterpret_cast<int*>(ws + l.tile_idx);
+  *ck = reinterpret_cast<unsigned*>(ws + l.class_key);
+  *ci = reinterpret_cast<int*>(ws + l.class_idx);
+  hipLaunchKernelGGL((decode_band_topk_kernel<0, PEAK, true>), dim3(NT, num_classes, batch), dim3(kBandThreads), 0,
+                     st, hm, num_classes, height, width, K, R, apply_sigmoid, tk, ti, TileGeo<true>{NX, TC});
+  SFA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(decode_class_merge_kernel, dim3(batch * num_classes), dim3(1024), 0, st, tk, ti, NT, K, *ck,
+                     *ci);
+  SFA_LAUNCH_CHECK();
+  return SFA_OK;
+}
+
 extern "C" int sfa_decode(const float* hm, const float* off, const float* dir, const float* z,
                           const float* dim, int batch, int num_classes, int height, int width, int K,
                           int apply_sigmoid, float* dets, void* workspace, size_t workspace_bytes,
                           void* stream) {
   SFA_CHECK_ARG(hm && dir && z && dim && dets && workspace, "decode: null argument");
   SFA_CHECK_ARG(batch >= 1 && num_classes >= 1 && num_classes <= 16, "decode: bad B/C");
-  SFA_CHECK_ARG(height >= 1 && width >= 1 && height * width <= kDecMaxHW,
-                "decode: H*W = %d exceeds %d", height * width, kDecMaxHW);
+  SFA_CHECK_ARG(height >= 1 && width >= 1 && (long long)height * width <= kTileMaxHW,
+                "decode: H*W = %lld exceeds %d", (long long)height * width, kTileMaxHW);
   SFA_CHECK_ARG(K >= 1 && K <= kDecMaxK && K <= height * width, "decode: K = %d out of range", K);
-  if (workspace_bytes < sfa_decode_workspace_size(batch, num_classes, K)) {
+  // both are written while hm is still being read
+  SFA_CHECK_ARG((const void*)dets != (const void*)hm && (const void*)workspace != (const void*)hm,
+                "decode: dets / workspace alias hm");
+  if (workspace_bytes < sfa_decode_workspace_size_hw(batch, num_classes, height, width, K)) {
     set_error("decode: workspace too small");
     return SFA_E_WORKSPACE;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (height * width > kDecMaxHW) {  // tiled: tile lists -> class lists -> the per-frame merge over C lists
+    unsigned* ck;
+    int* ci;
+    const int rc = tiled_class_lists<true>(hm, batch, num_classes, height, width, K, apply_sigmoid, workspace, st,
+                                           &ck, &ci);
+    if (rc != SFA_OK) return rc;
+    hipLaunchKernelGGL(decode_band_merge_gather_kernel, dim3(batch), dim3(1024), 0, st, ck, ci, num_classes, 1, K,
+                       height, width, apply_sigmoid, off, dir, z, dim, dets);
+    SFA_LAUNCH_CHECK();
+    return SFA_OK;
+  }
   int S = 0, R = height;
   band_plan(num_classes, height, width, K, &S, &R);
   if (S > 0) {
@@ -802,7 +929,7 @@ extern "C" int sfa_decode(const float* hm, const float* off, const float* dir, c
       return SFA_E_WORKSPACE;
     }
     hipLaunchKernelGGL(decode_band_topk_kernel<0>, dim3(S, num_classes, batch), dim3(kBandThreads), 0, st, hm,
-                       num_classes, height, width, K, R, apply_sigmoid, bk, bi);
+                       num_classes, height, width, K, R, apply_sigmoid, bk, bi, TileGeo<false>{});
     SFA_LAUNCH_CHECK();
     hipLaunchKernelGGL(decode_band_merge_gather_kernel, dim3(batch), dim3(1024), 0, st, bk, bi, num_classes, S,
                        K, height, width, apply_sigmoid, off, dir, z, dim, dets);
@@ -842,15 +969,29 @@ extern "C" int sfa_topk(const float* scores, int batch, int num_classes, int hei
   SFA_CHECK_ARG(scores && out_scores && out_inds && out_ys && out_xs && workspace && (per_channel || out_clses),
                 "topk: null argument");
   SFA_CHECK_ARG(batch >= 1 && num_classes >= 1 && num_classes <= 16, "topk: bad B/C");
-  SFA_CHECK_ARG(height >= 1 && width >= 1 && height * width <= kDecMaxHW, "topk: H*W = %d exceeds %d",
-                height * width, kDecMaxHW);
+  SFA_CHECK_ARG(height >= 1 && width >= 1 && (long long)height * width <= kTileMaxHW,
+                "topk: H*W = %lld exceeds %d", (long long)height * width, kTileMaxHW);
   SFA_CHECK_ARG(K >= 1 && K <= kDecMaxK && K <= height * width, "topk: K = %d out of range", K);
-  if (workspace_bytes < sfa_topk_workspace_size(batch, num_classes, K)) {
+  if (workspace_bytes < sfa_topk_workspace_size_hw(batch, num_classes, height, width, K)) {
     set_error("topk: workspace too small");
     return SFA_E_WORKSPACE;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int groups = per_channel ? batch * num_classes : batch;
+  if (height * width > kDecMaxHW) {  // tiled (no peak test), then the band merge over C (or 1) lists
+    unsigned* ck;
+    int* ci;
+    const int rc = tiled_class_lists<false>(scores, batch, num_classes, height, width, K, 0, workspace, st, &ck, &ci);
+    if (rc != SFA_OK) return rc;
+    if (per_channel)
+      hipLaunchKernelGGL(topk_band_merge_kernel<true>, dim3(groups), dim3(1024), 0, st, ck, ci, num_classes, 1, K,
+                         width, out_scores, out_inds, out_clses, out_ys, out_xs);
+    else
+      hipLaunchKernelGGL(topk_band_merge_kernel<false>, dim3(groups), dim3(1024), 0, st, ck, ci, num_classes, 1, K,
+                         width, out_scores, out_inds, out_clses, out_ys, out_xs);
+    SFA_LAUNCH_CHECK();
+    return SFA_OK;
+  }
   int S = 0, R = height;
   band_plan(num_classes, height, width, K, &S, &R);
   if (S > 0) {
@@ -858,7 +999,7 @@ extern "C" int sfa_topk(const float* scores, int batch, int num_classes, int hei
     auto* bk = reinterpret_cast<unsigned*>(workspace);
     auto* bi = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + align_up(nb * sizeof(unsigned), 256));
     hipLaunchKernelGGL((decode_band_topk_kernel<0, false>), dim3(S, num_classes, batch), dim3(kBandThreads), 0, st,
-                       scores, num_classes, height, width, K, R, 0, bk, bi);
+                       scores, num_classes, height, width, K, R, 0, bk, bi, TileGeo<false>{});
     SFA_LAUNCH_CHECK();
     if (per_channel)
       hipLaunchKernelGGL(topk_band_merge_kernel<true>, dim3(groups), dim3(1024), 0, st, bk, bi, num_classes, S, K,

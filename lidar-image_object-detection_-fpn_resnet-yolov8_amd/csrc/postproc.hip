@@ -233,6 +233,98 @@ __global__ void __launch_bounds__(64 * kWaves)
   }
 }
 
+// ---- Argoverse: detections -> image corners (argoverse_test2.py:404-479) ----
+struct ArgoCam {
+  double T[16];  // T_l2c, row-major 4x4
+  double P[12];  // P2, row-major 3x4
+};
+
+// project_to_image (:324-353) for one point: hom = [X, Y, Z, 1.0] in f64 (np.hstack with f64 ones
+// promotes), cam = T_l2c @ hom, NaN unless cam.z > 0.1, else (P2 @ cam)[:2] / (P2 @ cam)[2], rounded
+// to f32 at the store (the f32 result array).  Sums left to right, no contraction.
+__device__ __forceinline__ void argo_project_point(double X, double Y, double Z, const ArgoCam& c, float* uv) {
+  double cam[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    double s = c.T[i * 4] * X;
+    s = s + c.T[i * 4 + 1] * Y;
+    s = s + c.T[i * 4 + 2] * Z;
+    s = s + c.T[i * 4 + 3] * 1.0;
+    cam[i] = s;
+  }
+  if (!(cam[2] > 0.1)) {  // :336 valid_mask (a NaN depth is invalid too)
+    uv[0] = uv[1] = __builtin_nanf("");
+    return;
+  }
+  double pr[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    double s = c.P[i * 4] * cam[0];
+    s = s + c.P[i * 4 + 1] * cam[1];
+    s = s + c.P[i * 4 + 2] * cam[2];
+    s = s + c.P[i * 4 + 3] * cam[3];
+    pr[i] = s;
+  }
+  uv[0] = (float)(pr[0] / pr[2]);
+  uv[1] = (float)(pr[1] / pr[2]);
+}
+
+// One thread per corner (8 consecutive lanes = one detection).  Row = [score, x, y, z, h, w, l, yaw]
+// (sfa_post_process out_preds).  :432-436 metres in f32 (numpy >= 2: an f32 scalar (op) a Python
+// number stays f32), :380-399 corners in f32 (R about the second axis, y from 0 to -h), :324-353
+// projection in f64.  all8[i] = 1 when the detection's eight corners are all finite (:458).
+__global__ void __launch_bounds__(256)
+    argo_project_boxes_kernel(const float* __restrict__ preds, const int32_t* __restrict__ offsets, int batch,
+                              int capacity, float max_x, float min_y, float min_z, float d, ArgoCam cam,
+                              float* __restrict__ out_px, int32_t* __restrict__ out_all8,
+                              float* __restrict__ out_c3) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = t >> 3, k = t & 7;
+  const int n = offsets ? min(offsets[batch], capacity) : capacity;
+  const bool live = i < n;
+  bool finite = false;
+  if (live) {
+    const float* r = preds + (size_t)i * 8;
+    const float cx = max_x - r[1] * d;
+    const float cy = r[2] * d + min_y;
+    const float cz = r[3] + min_z;
+    const float h = r[4], w = r[5], l = r[6], yaw = r[7];
+    const float xc = (k == 0 || k == 1 || k == 4 || k == 5) ? l / 2 : -l / 2;  // :380
+    const float yc = k < 4 ? 0.f : -h;                                          // :381
+    const float zc = (k == 0 || k == 3 || k == 4 || k == 7) ? w / 2 : -w / 2;  // :382
+    const float cs = cosf(yaw), sn = sinf(yaw);
+    // np.dot(R, corners) rows: [cs, 0, sn], [0, 1, 0], [-sn, 0, cs] (the zero products add nothing)
+    const float X = (cs * xc + sn * zc) + cx;
+    const float Y = yc + cy;
+    const float Z = (-sn * xc + cs * zc) + cz;
+    if (out_c3) {
+      out_c3[(size_t)t * 3 + 0] = X;
+      out_c3[(size_t)t * 3 + 1] = Y;
+      out_c3[(size_t)t * 3 + 2] = Z;
+    }
+    float uv[2];
+    argo_project_point((double)X, (double)Y, (double)Z, cam, uv);
+    out_px[(size_t)t * 2 + 0] = uv[0];
+    out_px[(size_t)t * 2 + 1] = uv[1];
+    finite = !isnan(uv[0]) && !isnan(uv[1]);
+  }
+  const unsigned long long m = __ballot(finite);
+  const int lane = threadIdx.x & 63;
+  if (live && k == 0) out_all8[i] = ((m >> lane) & 0xffull) == 0xffull ? 1 : 0;
+}
+
+// project_to_image on its own: (n, 3) points of f32 or f64 -> (n, 2) f32.
+template <typename T>
+__global__ void __launch_bounds__(256)
+    argo_project_points_kernel(const T* __restrict__ pts, int64_t n, ArgoCam cam, float* __restrict__ out_px) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float uv[2];
+  argo_project_point((double)pts[i * 3], (double)pts[i * 3 + 1], (double)pts[i * 3 + 2], cam, uv);
+  out_px[i * 2] = uv[0];
+  out_px[i * 2 + 1] = uv[1];
+}
+
 }  // namespace
 
 }  // namespace sfa
@@ -270,6 +362,50 @@ extern "C" int sfa_project_boxes(const double* real, const float* preds, const i
                      reinterpret_cast<hipStream_t>(stream), real, preds, offsets, batch, calib,
                      *params, reinterpret_cast<int4*>(out_boxes), out_conf, out_row, out_extent,
                      out_offsets);
+  SFA_LAUNCH_CHECK();
+  return SFA_OK;
+}
+
+static bool argo_cam(const double* T_l2c, const double* P2, ArgoCam* c) {
+  if (!T_l2c || !P2) return false;
+  for (int i = 0; i < 16; ++i) c->T[i] = T_l2c[i];
+  for (int i = 0; i < 12; ++i) c->P[i] = P2[i];
+  return true;
+}
+
+extern "C" int sfa_argo_project_boxes(const float* preds, const int32_t* offsets, int batch, int capacity,
+                                      const double* boundary, double discretization, const double* T_l2c,
+                                      const double* P2, float* out_pixels, int32_t* out_all8,
+                                      float* out_corners3d, void* stream) {
+  ArgoCam cam;
+  SFA_CHECK_ARG(capacity >= 0 && capacity <= (1 << 24) && boundary && argo_cam(T_l2c, P2, &cam),
+                "argo_project_boxes: bad arguments");
+  SFA_CHECK_ARG(!offsets || batch >= 0, "argo_project_boxes: bad batch");
+  if (capacity == 0) return SFA_OK;
+  SFA_CHECK_ARG(preds && out_pixels && out_all8, "argo_project_boxes: null buffer");
+  const int threads = capacity * 8;
+  hipLaunchKernelGGL(argo_project_boxes_kernel, dim3((threads + 255) / 256), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), preds, offsets, batch, capacity, (float)boundary[1],
+                     (float)boundary[2], (float)boundary[4], (float)discretization, cam, out_pixels, out_all8,
+                     out_corners3d);
+  SFA_LAUNCH_CHECK();
+  return SFA_OK;
+}
+
+extern "C" int sfa_argo_project_points(const void* points, int points_f64, int64_t n, const double* T_l2c,
+                                       const double* P2, float* out_pixels, void* stream) {
+  ArgoCam cam;
+  SFA_CHECK_ARG(n >= 0 && n <= (1ll << 30) && argo_cam(T_l2c, P2, &cam), "argo_project_points: bad arguments");
+  if (n == 0) return SFA_OK;
+  SFA_CHECK_ARG(points && out_pixels, "argo_project_points: null buffer");
+  const dim3 g((unsigned)((n + 255) / 256)), b(256);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (points_f64)
+    hipLaunchKernelGGL(argo_project_points_kernel<double>, g, b, 0, st, reinterpret_cast<const double*>(points), n,
+                       cam, out_pixels);
+  else
+    hipLaunchKernelGGL(argo_project_points_kernel<float>, g, b, 0, st, reinterpret_cast<const float*>(points), n, cam,
+                       out_pixels);
   SFA_LAUNCH_CHECK();
   return SFA_OK;
 }

@@ -194,6 +194,16 @@ _PROTOS["sfa_argo_bev_scratch_size"] = (_c_size, [_c_int, _c_int, _c_int])
 _PROTOS["sfa_argo_bev_voxelize"] = (_c_int, [_vp, _c_int, ctypes.POINTER(_c_i64), _c_int,
                                              ctypes.POINTER(ctypes.c_double), ctypes.c_double, _c_int, _vp, _vp,
                                              _c_size, _vp])
+# decode / topk above 36864 cells (the tiled form): workspace sized with the map
+_PROTOS["sfa_decode_workspace_size_hw"] = (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int])
+_PROTOS["sfa_topk_workspace_size_hw"] = (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int])
+DECODE_MAX_HW = 1 << 18
+# Argoverse detections -> image corners (include/sfa_hip.h)
+_PROTOS["sfa_argo_project_boxes"] = (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.POINTER(ctypes.c_double),
+                                              ctypes.c_double, ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_double), _vp, _vp, _vp, _vp])
+_PROTOS["sfa_argo_project_points"] = (_c_int, [_vp, _c_int, _c_i64, ctypes.POINTER(ctypes.c_double),
+                                               ctypes.POINTER(ctypes.c_double), _vp, _vp])
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
 _lib = None

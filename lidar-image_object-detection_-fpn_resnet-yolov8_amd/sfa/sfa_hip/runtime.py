@@ -495,7 +495,8 @@ def topk(scores: torch.Tensor, K: int = 40, per_channel: bool = False):
     cls = None if per_channel else torch.empty(shp, dtype=torch.int32, device=dev)
     ys = torch.empty(shp, dtype=torch.float32, device=dev)
     xs = torch.empty(shp, dtype=torch.float32, device=dev)
-    ws = torch.empty(int(lib().sfa_topk_workspace_size(B, C, K)), dtype=torch.uint8, device=dev)
+    nws = int(lib().sfa_topk_workspace_size_hw(B, C, H, W, K)) or int(lib().sfa_topk_workspace_size(B, C, K))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
     check(lib().sfa_topk(scores.data_ptr(), B, C, H, W, K, 1 if per_channel else 0, sc.data_ptr(), ind.data_ptr(),
                          cls.data_ptr() if cls is not None else None, ys.data_ptr(), xs.data_ptr(), ws.data_ptr(),
                          ws.numel(), _lib.stream_ptr(dev)), "sfa_topk")
@@ -544,15 +545,22 @@ class Decoder:
         self._ws = {}
 
     @staticmethod
-    def workspace_bytes(B, C, K) -> int:
+    def workspace_bytes(B, C, K, H: int = None, W: int = None) -> int:
+        """Bytes sfa_decode needs for (B, C, H, W) maps; without H, W the size that serves every map
+        of H*W <= 36864 (the tiled form above that needs the map's own size)."""
+        if H is not None and W is not None:
+            n = int(lib().sfa_decode_workspace_size_hw(B, C, int(H), int(W), K))
+            if n:  # 0: a shape sfa_decode refuses (it names the reason)
+                return n
         return int(lib().sfa_decode_workspace_size(B, C, K))
 
-    def workspace(self, device, B, C, K, stream: int = None):
+    def workspace(self, device, B, C, K, stream: int = None, H: int = None, W: int = None):
         sk = int(stream) if stream is not None else _lib.stream_ptr(device)
-        key = (str(device), sk, B, C, K)
+        n = self.workspace_bytes(B, C, K, H, W)
+        key = (str(device), sk, B, C, K, n)
         ws = self._ws.get(key)
         if ws is None:
-            ws = torch.empty(self.workspace_bytes(B, C, K), dtype=torch.uint8, device=device)
+            ws = torch.empty(n, dtype=torch.uint8, device=device)
             self._ws[key] = ws
         return ws
 
@@ -562,15 +570,16 @@ class Decoder:
         dirn, z, dim = (_require_gpu_tensor(t, "decode") for t in (dirn, z, dim))
         if off is not None:
             off = _require_gpu_tensor(off, "decode")
-        B, C, H, W = hm.shape
+        B, C, H, W = (int(v) for v in hm.shape)
         for t, c in ((off, 2), (dirn, 2), (z, 1), (dim, 3)):
             if t is not None and tuple(t.shape) != (B, c, H, W):
                 raise ValueError(f"decode: map shape {tuple(t.shape)} != {(B, c, H, W)}")
         if out is None:
             out = torch.empty((B, K, 10), dtype=torch.float32, device=hm.device)
         sp = stream if stream is not None else _lib.stream_ptr(hm.device)
-        ws = workspace if workspace is not None else self.workspace(hm.device, B, C, K, sp)
-        if ws.numel() < self.workspace_bytes(B, C, K):
+        need = self.workspace_bytes(B, C, K, H, W)
+        ws = workspace if workspace is not None else self.workspace(hm.device, B, C, K, sp, H, W)
+        if ws.numel() < need:
             raise ValueError("decode: workspace too small")
         check(lib().sfa_decode(hm.data_ptr(), off.data_ptr() if off is not None else None,
                                dirn.data_ptr(), z.data_ptr(), dim.data_ptr(), B, C, H, W, int(K),
@@ -640,7 +649,8 @@ class DetectorPipeline:
                                   device=self.dev)
             self.outs = engine.alloc_outputs(nmap, height, width)
             self.dets = torch.empty((nmap, K, 10), dtype=torch.float32, device=self.dev)
-            self.dec_ws = torch.empty(Decoder.workspace_bytes(nmap, dict(engine.heads)["hm_cen"], K),
+            hm_h, hm_w = (int(v) for v in self.outs["hm_cen"].shape[2:])
+            self.dec_ws = torch.empty(Decoder.workspace_bytes(nmap, dict(engine.heads)["hm_cen"], K, hm_h, hm_w),
                                       dtype=torch.uint8, device=self.dev)
             if with_bev:
                 if bev == "argoverse":
@@ -969,6 +979,61 @@ def project_boxes(real: torch.Tensor, offsets: torch.Tensor, calibs, preds=None,
                                   _lib.stream_ptr(dev)),
           "sfa_project_boxes")
     return boxes, conf, row, ext, off
+
+
+class ArgoBoxProjector:
+    """sfa_argo_project_boxes for one log: the device rows of post_process (preds, offsets) -> the
+    eight image corners of every detection (argoverse_test2.py:432-436 grid -> metres, :355-402
+    create_3d_bbox_corners, :324-353 project_to_image) and the scripts' draw flag (:458), no host hop.
+    ``calib``: an object with ``T_l2c`` (4x4) and ``P2`` (3x4), e.g.
+    utils.argoverse_box_utils.ArgoverseCalibration; their float32 values are widened exactly."""
+
+    def __init__(self, device, calib, boundary=ARGO_BOUNDARY, discretization: float = ARGO_DISCRETIZATION):
+        self.device = torch.device(device)
+        self.T = (ctypes.c_double * 16)(*np.asarray(calib.T_l2c, np.float64).reshape(16).tolist())
+        self.P = (ctypes.c_double * 12)(*np.asarray(calib.P2, np.float64).reshape(12).tolist())
+        self.boundary = _boundary_arr(boundary)
+        self.discretization = float(discretization)
+
+    def __call__(self, preds: torch.Tensor, offsets: torch.Tensor = None, corners3d: bool = False, out=None,
+                 stream: int = None):
+        """preds (n, 8) f32 [score, x, y, z, h, w, l, yaw]; offsets: post_process' (B + 1,) int32 (rows
+        past offsets[B] are left as they are) or None (every row).  Returns (pixels (n, 8, 2) f32 with
+        NaN for corners at camera Z <= 0.1, all8 (n,) int32, corners (n, 8, 3) f32 or None)."""
+        preds = _require_gpu_tensor(preds, "argo_project_boxes")
+        if preds.dim() != 2 or preds.shape[1] != 8:
+            raise ValueError("argo_project_boxes: preds must be (n, 8)")
+        n, dev = int(preds.shape[0]), preds.device
+        B = 0
+        if offsets is not None:
+            offsets = _require_gpu_tensor(offsets, "argo_project_boxes offsets", torch.int32)
+            B = int(offsets.numel()) - 1
+        if out is None:
+            out = (torch.full((n, 8, 2), float("nan"), dtype=torch.float32, device=dev),
+                   torch.zeros(n, dtype=torch.int32, device=dev),
+                   torch.zeros((n, 8, 3), dtype=torch.float32, device=dev) if corners3d else None)
+        px, all8, c3 = out
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        check(lib().sfa_argo_project_boxes(ptr(preds), ptr(offsets), B, n, self.boundary, self.discretization,
+                                           self.T, self.P, ptr(px), ptr(all8), ptr(c3),
+                                           stream if stream is not None else _lib.stream_ptr(dev)),
+              "sfa_argo_project_boxes")
+        return px, all8, c3
+
+    def project_points(self, points: torch.Tensor) -> torch.Tensor:
+        """project_to_image (:324-353): (n, 3) f32 or f64 GPU points -> (n, 2) f32 pixels (NaN rows
+        for points at camera Z <= 0.1)."""
+        if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
+            raise TypeError("project_to_image: expected a float32 or float64 tensor")
+        points = _require_gpu_tensor(points, "project_to_image", points.dtype)
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"project_to_image: points must be (n, 3), got {tuple(points.shape)}")
+        n = int(points.shape[0])
+        out = torch.empty((n, 2), dtype=torch.float32, device=points.device)
+        check(lib().sfa_argo_project_points(points.data_ptr() if n else None, 1 if points.dtype == torch.float64 else 0,
+                                            n, self.T, self.P, out.data_ptr() if n else None,
+                                            _lib.stream_ptr(points.device)), "sfa_argo_project_points")
+        return out
 
 
 # ------------------------------------------------------- fused LiDAR + camera

@@ -74,7 +74,7 @@ int main(int argc, char** argv) {
   });
 #define BAND(ABL)                                                                                       \
   time("band_topk<" #ABL ">", [&] {                                                                     \
-    hipLaunchKernelGGL(decode_band_topk_kernel<ABL>, dim3(S, C, B), dim3(kBandThreads), 0, 0, hm, C, H, W, K, R, 1, bk, bi); \
+    hipLaunchKernelGGL(decode_band_topk_kernel<ABL>, dim3(S, C, B), dim3(kBandThreads), 0, 0, hm, C, H, W, K, R, 1, bk, bi, TileGeo<false>{}); \
   })
   BAND(0);
   BAND(1);
@@ -83,7 +83,7 @@ int main(int argc, char** argv) {
   BAND(8);
   BAND(15);
   // valid band lists for the merge (the ablations above leave garbage behind)
-  hipLaunchKernelGGL(decode_band_topk_kernel<0>, dim3(S, C, B), dim3(kBandThreads), 0, 0, hm, C, H, W, K, R, 1, bk, bi);
+  hipLaunchKernelGGL(decode_band_topk_kernel<0>, dim3(S, C, B), dim3(kBandThreads), 0, 0, hm, C, H, W, K, R, 1, bk, bi, TileGeo<false>{});
   CK(hipDeviceSynchronize());
   time("band_merge_gather", [&] {
     hipLaunchKernelGGL(decode_band_merge_gather_kernel, dim3(B), dim3(1024), 0, 0, bk, bi, C, S, K, H, W, 1, off, dr,
