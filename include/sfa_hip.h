@@ -578,6 +578,77 @@ int sfa_fuse_detections(int batch, const int32_t* yolo_boxes, const double* yolo
                         int32_t* out_origin, int32_t* out_match, int32_t* out_count,
                         int32_t* out_keep, int32_t* out_keep_count, void* stream);
 
+/* ------------------------------------------------- validation: targets + loss --
+ * The reference's only quality figure is the validation loss (train.py:250-275 validate): the val
+ * loader's targets, the model, losses.losses.Compute_Loss, averaged.  Evaluation only: no
+ * gradient is formed anywhere.
+ *
+ * sfa_build_targets replaces data_process/kitti_dataset.py:157-244 KittiDataset.build_targets (with
+ * kitti_data_utils.py:176-225 compute_radius, gaussian2D, gen_hm_radius) for a batch of label lists.
+ *   labels         DEVICE f32 [total_rows][8] = cls, x, y, z, h, w, l, yaw, in label order
+ *   frame_offsets  DEVICE int64 [batch + 1] (in rows; frame b = rows [off[b], off[b+1]), clamped to
+ *                  [0, total_rows]); only the first max_objects rows of a frame are read (:165)
+ *   params         boundary = minX, maxX, minY, maxY, minZ, maxZ; hm_h x hm_w the heat map
+ *                  (configs.hm_size), num_classes <= 16, max_objects 1..256; bit b of the h-flip mask
+ *                  (lo: frames 0..31, hi: 32..63) = frame b is flipped (:196, :225), so batch <= 64;
+ *                  reserved words zero
+ * Outputs, all DEVICE and all written in full by the call (nothing needs zeroing; graph-capturable):
+ *   hm_cen (B, C, H, W) f32, cen_offset (B, M, 2) f32, direction (B, M, 2) f32, z_coor (B, M, 1) f32,
+ *   dim (B, M, 3) f32, indices_center (B, M) int64, obj_mask (B, M) uint8, status uint32 [B].
+ * Semantics are the reference's loop, label by label: yaw = -yaw; the boundary test and the
+ * h, w, l <= 0 test leave the slot zero; radius = max(0, int(compute_radius(ceil(l'), ceil(w'))));
+ * centre, its h-flip, center_int = trunc; the gaussian of diameter 2r + 1 and sigma = diameter / 6 in
+ * float64, clipped at the map edges, combined with max; a label with cls < 0 (-1: every class,
+ * otherwise class -cls - 2) draws its gaussian at center_int, then ASSIGNS 0.9999 at the centre cell
+ * and fills no slot.  The assignment makes the map depend on the label order; each cell is computed
+ * by walking the labels in that order, so any order is exact.  Float dtypes follow numpy >= 2 (a
+ * float32 scalar combined with a Python number stays float32; tests/loss_restatement.py states every
+ * step); the float64 exp / sin / cos may differ from libm's by an ulp, i.e. in the float32 result
+ * only at a rounding midpoint.
+ * status bit 0: a centre fell outside the map (x == maxX gives center_int[1] == hm_h; a flipped
+ * y == maxY gives center_int[0] == -1): the gaussian is clipped like the reference's slices, the index
+ * the reference computes is stored, the 0.9999 of an ignore label (where the reference raises or
+ * wraps) is not written, nothing is written out of bounds.  bit 1: a class id >= num_classes or
+ * < -num_classes - 1 (the reference raises IndexError); the row is skipped.
+ * SFA_E_INVALID before any launch: batch, classes, H or W <= 0, classes > 16, max_objects outside
+ * 1..256, batch > 64, H*W > 2^24, nonzero reserved words, a NULL pointer. */
+typedef struct sfa_target_params {
+  double boundary[6];
+  int hm_h, hm_w, num_classes, max_objects;
+  uint32_t hflip_mask_lo, hflip_mask_hi;
+  int reserved[6];
+} sfa_target_params;
+int sfa_build_targets(const float* labels, const int64_t* frame_offsets, int64_t total_rows, int batch,
+                      const sfa_target_params* params, float* hm_cen, float* cen_offset,
+                      float* direction, float* z_coor, float* dim, int64_t* indices_center,
+                      uint8_t* obj_mask, uint32_t* status, void* stream);
+
+/* sfa_compute_loss replaces losses/losses.py:128-163 Compute_Loss.forward (FocalLoss / _neg_loss
+ * :44-69, L1Loss :83-92, L1Loss_Balanced :95-125 with alpha 0.5, gamma 1.5, beta 1; unit weights).
+ * The five head maps are DEVICE f32 NCHW as sfa_model_forward writes them ((B, C | 2 | 2 | 1 | 3, H, W));
+ * the targets are sfa_build_targets' tensors.  apply_sigmoid as in sfa_decode: 1 applies _sigmoid
+ * (sigmoid, clamp to [1e-4, 1 - 1e-4], sfa_sigmoid_clamp_inplace's arithmetic) to hm_cen and
+ * cen_offset on the fly without writing them back, 0 takes them as clamped probabilities.
+ *   loss    DEVICE f32 [6] = total, hm_cen, cen_offset, dim, direction, z_coor (the loss_stats order)
+ *   sums    DEVICE f64 [8] = focal positive sum, negative sum, num_pos, the masked sums of
+ *           cen_offset, dim, direction, z_coor, and the mask sum (objects)
+ *   status  DEVICE uint32 [1]: bit 0 = a slot with a set mask has an index outside [0, H*W) (the
+ *           reference's gather raises); the slot contributes nothing
+ * Every term is evaluated in float64 from the float32 operands and summed in float64 in an order
+ * fixed by the shape (per-block partials in the workspace, one folding launch; no floating-point
+ * atomics): runs are bit-identical.  hm_cen = -neg when num_pos == 0, else -(pos + neg) / num_pos;
+ * an L1 term = sum / (mask sum * channels + 1e-4); the six values are rounded to float32 once.
+ * workspace: DEVICE, 8-byte aligned, sfa_compute_loss_workspace_size(B, C, H, W, M) bytes (0 for a
+ * shape out of range: B 1..64, C 1..16, M 1..256, H*W <= 2^24), SFA_E_WORKSPACE when smaller. */
+size_t sfa_compute_loss_workspace_size(int batch, int num_classes, int height, int width, int max_objects);
+int sfa_compute_loss(const float* hm_cen, const float* cen_offset, const float* direction,
+                     const float* z_coor, const float* dim, const float* t_hm_cen,
+                     const float* t_cen_offset, const float* t_direction, const float* t_z_coor,
+                     const float* t_dim, const int64_t* indices_center, const uint8_t* obj_mask, int batch,
+                     int num_classes, int height, int width, int max_objects, int apply_sigmoid,
+                     float* loss, double* sums, uint32_t* status, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,22 @@ _PROTOS["sfa_argo_project_boxes"] = (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.P
                                               ctypes.POINTER(ctypes.c_double), _vp, _vp, _vp, _vp])
 _PROTOS["sfa_argo_project_points"] = (_c_int, [_vp, _c_int, _c_i64, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double), _vp, _vp])
+
+
+# validation: targets + loss (include/sfa_hip.h)
+class SfaTargetParams(ctypes.Structure):
+    _fields_ = [("boundary", ctypes.c_double * 6), ("hm_h", ctypes.c_int), ("hm_w", ctypes.c_int),
+                ("num_classes", ctypes.c_int), ("max_objects", ctypes.c_int),
+                ("hflip_mask_lo", ctypes.c_uint32), ("hflip_mask_hi", ctypes.c_uint32),
+                ("reserved", ctypes.c_int * 6)]
+
+
+TARGET_MAX_BATCH, TARGET_MAX_CLASSES, TARGET_MAX_OBJECTS = 64, 16, 256
+STATUS_INDEX_OUT_OF_MAP, STATUS_BAD_CLASS = 1, 2
+_PROTOS["sfa_build_targets"] = (_c_int, [_vp, _vp, _c_i64, _c_int, ctypes.POINTER(SfaTargetParams), _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp])
+_PROTOS["sfa_compute_loss_workspace_size"] = (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int])
+_PROTOS["sfa_compute_loss"] = (_c_int, [_vp] * 12 + [_c_int] * 6 + [_vp, _vp, _vp, _vp, _c_size, _vp])
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
 _lib = None

@@ -1179,3 +1179,139 @@ class FusionPipeline:
             kp = np.arange(max(n, 0), dtype=keep.dtype) if self.nms == "gaussian" else keep[base:base + int(kc[b])]
             out.append((fb[base:base + n], fc[base:base + n], fk[base:base + n], fs[base:base + n], kp))
         return out
+
+
+# ------------------------------------------------------- validation: targets + loss
+TARGET_KEYS = ("hm_cen", "cen_offset", "direction", "z_coor", "dim", "indices_center", "obj_mask")
+LOSS_KEYS = ("total_loss", "hm_cen_loss", "cen_offset_loss", "dim_loss", "direction_loss", "z_coor_loss")
+
+
+class TargetBuilder:
+    """KittiDataset.build_targets (kitti_dataset.py:157-244) for a batch of label lists on the device
+    (sfa_build_targets).  ``labels``: (N, 8) float32 rows [cls, x, y, z, h, w, l, yaw] of all frames, in
+    label order; ``offsets``: B + 1 row offsets (a sequence, or an int64 GPU tensor); ``hflipped``: one
+    bool per frame.  Returns the reference's dict of GPU tensors, batched as its collate stacks them.
+    ``status`` (uint32 per frame, bit 0: a centre outside the map, bit 1: a class id the reference
+    raises on) is kept on the builder; with ``verify`` (the default) bit 1 raises IndexError, which
+    synchronises.  With ``out`` (a dict from :meth:`alloc`), ``verify=False`` and device offsets the call
+    only enqueues one launch and can be captured into a HIP graph."""
+
+    def __init__(self, device, boundary=DEFAULT_BOUNDARY, hm_size=(152, 152), num_classes: int = 3,
+                 max_objects: int = 50):
+        self.dev = torch.device(device)
+        self.boundary = dict(boundary)
+        self.hm_size = (int(hm_size[0]), int(hm_size[1]))
+        self.num_classes, self.max_objects = int(num_classes), int(max_objects)
+        self.status = None
+
+    def alloc(self, B: int) -> dict:
+        (H, W), C, M, dev = self.hm_size, self.num_classes, self.max_objects, self.dev
+        f32 = torch.float32
+        return {"hm_cen": torch.empty((B, C, H, W), dtype=f32, device=dev),
+                "cen_offset": torch.empty((B, M, 2), dtype=f32, device=dev),
+                "direction": torch.empty((B, M, 2), dtype=f32, device=dev),
+                "z_coor": torch.empty((B, M, 1), dtype=f32, device=dev),
+                "dim": torch.empty((B, M, 3), dtype=f32, device=dev),
+                "indices_center": torch.empty((B, M), dtype=torch.int64, device=dev),
+                "obj_mask": torch.empty((B, M), dtype=torch.uint8, device=dev)}
+
+    def params(self, hflipped, B: int) -> "_lib.SfaTargetParams":
+        p = _lib.SfaTargetParams()
+        p.boundary = _boundary_arr(self.boundary)
+        p.hm_h, p.hm_w = self.hm_size
+        p.num_classes, p.max_objects = self.num_classes, self.max_objects
+        mask = 0
+        if hflipped is not None:
+            flips = [bool(f) for f in hflipped]
+            if len(flips) != B:
+                raise ValueError(f"build_targets: {len(flips)} hflipped flags for {B} frames")
+            mask = sum(1 << b for b, f in enumerate(flips) if f)
+        p.hflip_mask_lo, p.hflip_mask_hi = mask & 0xFFFFFFFF, mask >> 32
+        return p
+
+    def __call__(self, labels, offsets, hflipped=None, out: dict = None, verify: bool = True) -> dict:
+        if isinstance(labels, np.ndarray):
+            labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float32).reshape(-1, 8)).to(self.dev)
+        labels = _require_gpu_tensor(labels, "build_targets")
+        if labels.dim() != 2 or labels.shape[1] != 8:
+            raise ValueError(f"build_targets: labels {tuple(labels.shape)}, expected (N, 8)")
+        if not isinstance(offsets, torch.Tensor):
+            offsets = torch.tensor([int(o) for o in offsets], dtype=torch.int64).to(self.dev)
+        offsets = _require_gpu_tensor(offsets, "build_targets offsets", torch.int64)
+        B = int(offsets.numel()) - 1
+        if B < 1 or B > _lib.TARGET_MAX_BATCH:
+            raise ValueError(f"build_targets: {B} frames; 1..{_lib.TARGET_MAX_BATCH} per call")
+        n = int(labels.shape[0])
+        rows = labels if n else torch.zeros((1, 8), dtype=torch.float32, device=self.dev)
+        out = self.alloc(B) if out is None else out
+        if self.status is None or self.status.numel() != B:
+            self.status = torch.empty(B, dtype=torch.int32, device=self.dev)  # the uint32 words
+        p = self.params(hflipped, B)
+        check_rc = lib().sfa_build_targets(
+            rows.data_ptr(), offsets.data_ptr(), n, B, ctypes.byref(p), out["hm_cen"].data_ptr(),
+            out["cen_offset"].data_ptr(), out["direction"].data_ptr(), out["z_coor"].data_ptr(),
+            out["dim"].data_ptr(), out["indices_center"].data_ptr(), out["obj_mask"].data_ptr(),
+            self.status.data_ptr(), _lib.stream_ptr(self.dev))
+        check(check_rc, "sfa_build_targets")
+        if verify:
+            bad = [b for b, s in enumerate(self.status.cpu().tolist()) if s & _lib.STATUS_BAD_CLASS]
+            if bad:
+                raise IndexError(f"build_targets: frames {bad} hold a class id outside "
+                                 f"[-{self.num_classes + 1}, {self.num_classes})")
+        return out
+
+
+class LossEvaluator:
+    """Compute_Loss.forward (losses/losses.py:138-163) on the device (sfa_compute_loss): owns the
+    workspace and the output words.  ``__call__`` returns the float32 [6] GPU tensor
+    [total, hm_cen, cen_offset, dim, direction, z_coor] (LOSS_KEYS order); ``sums`` holds the float64
+    pieces, ``status`` the bad-index word.  ``verify`` (default) reads the status word back and raises
+    IndexError as the reference's gather does; with ``verify=False`` the call only enqueues its three
+    launches and can be captured into a HIP graph."""
+
+    def __init__(self, device):
+        self.dev = torch.device(device)
+        self.loss = torch.empty(6, dtype=torch.float32, device=self.dev)
+        self.sums = torch.empty(8, dtype=torch.float64, device=self.dev)
+        self.status = torch.empty(1, dtype=torch.int32, device=self.dev)
+        self._ws = {}
+
+    @staticmethod
+    def workspace_bytes(B, C, H, W, M) -> int:
+        return int(lib().sfa_compute_loss_workspace_size(B, C, H, W, M))
+
+    def __call__(self, outputs: dict, targets: dict, apply_sigmoid: bool = False, verify: bool = True):
+        heads = [_require_gpu_tensor(outputs[k], f"Compute_Loss outputs[{k!r}]") for k in DEFAULT_HEADS]
+        tg = [_require_gpu_tensor(targets[k], f"Compute_Loss targets[{k!r}]") for k in TARGET_KEYS[:5]]
+        ind = _require_gpu_tensor(targets["indices_center"], "Compute_Loss indices_center", torch.int64)
+        msk = targets["obj_mask"]
+        if isinstance(msk, torch.Tensor) and msk.dtype == torch.bool:
+            msk = msk.to(torch.uint8)
+        msk = _require_gpu_tensor(msk, "Compute_Loss obj_mask", torch.uint8)
+        if heads[0].dim() != 4:
+            raise ValueError(f"Compute_Loss: hm_cen {tuple(heads[0].shape)}, expected (B, C, H, W)")
+        B, C, H, W = (int(v) for v in heads[0].shape)
+        if ind.dim() != 2 or int(ind.shape[0]) != B:
+            raise ValueError(f"Compute_Loss: indices_center {tuple(ind.shape)} for a batch of {B}")
+        M = int(ind.shape[1])
+        for t, c in zip(heads, (C, 2, 2, 1, 3)):
+            if tuple(t.shape) != (B, c, H, W):
+                raise ValueError(f"Compute_Loss: map shape {tuple(t.shape)} != {(B, c, H, W)}")
+        for t, s in zip(tg + [ind, msk], ((B, C, H, W), (B, M, 2), (B, M, 2), (B, M, 1), (B, M, 3), (B, M), (B, M))):
+            if tuple(t.shape) != s:
+                raise ValueError(f"Compute_Loss: target shape {tuple(t.shape)} != {s}")
+        need = self.workspace_bytes(B, C, H, W, M)
+        if need == 0:
+            raise ValueError(f"Compute_Loss: shape B={B}, C={C}, H={H}, W={W}, M={M} outside the kernels' range")
+        sp = _lib.stream_ptr(self.dev)
+        ws = self._ws.get((sp, need))
+        if ws is None:
+            ws = self._ws[(sp, need)] = torch.empty(need // 8, dtype=torch.float64, device=self.dev)
+        check_rc = lib().sfa_compute_loss(*(t.data_ptr() for t in heads), *(t.data_ptr() for t in tg), ind.data_ptr(),
+                                          msk.data_ptr(), B, C, H, W, M, 1 if apply_sigmoid else 0,
+                                          self.loss.data_ptr(), self.sums.data_ptr(), self.status.data_ptr(),
+                                          ws.data_ptr(), need, sp)
+        check(check_rc, "sfa_compute_loss")
+        if verify and int(self.status.item()) & _lib.STATUS_INDEX_OUT_OF_MAP:
+            raise IndexError(f"Compute_Loss: an indices_center entry under a set obj_mask is outside [0, {H * W})")
+        return self.loss

@@ -147,3 +147,24 @@ def synthetic_argoverse_sweep(seed: int = 1, n: int = 100_000) -> np.ndarray:
     c[:, 1] *= np.float32(0.5)
     c[:, 3] = np.floor(c[:, 3] * np.float32(256.0))
     return c
+
+
+def synthetic_labels(n_frames: int, seed: int = 1, max_per_frame: int = 12):
+    """KITTI-like label lists for the validation tier: (labels (N, 8) float32 rows
+    [cls, x, y, z, h, w, l, yaw] in the lidar frame, offsets int64 (n_frames + 1)).  A frame holds 3 to
+    max_per_frame labels inside the front boundary: classes 0..2 with their usual sizes, every fifth
+    label an ignore one (DontCare -1 or Truck -3, config/kitti_config.py:7-17)."""
+    sizes = {0: (1.75, 0.6, 0.8), 1: (1.5, 1.6, 3.9), 2: (1.7, 0.6, 1.8)}  # h, w, l
+    rows, offsets = [], [0]
+    for b in range(n_frames):
+        n = 3 + (b * 5 + seed) % (max_per_frame - 2)
+        u = hash_uniform(seed, 1000 + b, n * 8).reshape(n, 8)
+        for k in range(n):
+            cls = int(u[k, 0] * 3)
+            h, w, l = (s * (0.8 + 0.4 * u[k, 4 + j]) for j, s in enumerate(sizes[cls]))
+            if k % 5 == 4:
+                cls = -1 if u[k, 7] < 0.5 else -3
+            rows.append([cls, 1.0 + 48.0 * u[k, 1], -24.0 + 48.0 * u[k, 2], -2.2 + 1.5 * u[k, 3], h, w, l,
+                         -np.pi + 2 * np.pi * u[k, 7]])
+        offsets.append(len(rows))
+    return np.array(rows, dtype=np.float32).reshape(-1, 8), np.array(offsets, dtype=np.int64)

@@ -1,0 +1,202 @@
+#!/usr/bin/env python3
+"""The reference's validation loop (train.py:250-275 validate) on the HIP path: targets built on the GPU from
+the labels (sfa_build_targets), the forward, the loss (sfa_compute_loss), the AverageMeter average of
+total_loss over the frames, one JSON line.
+
+  tools/validate.py --synthetic 16                     synthetic weights, frames and labels (no data set)
+  tools/validate.py --dataset_dir D --pretrained_path P   KITTI val split through create_val_dataloader
+  --math fp16      also runs SFA_MATH_FP16 on the same frames and reports its loss next to fp16x3's
+  --timing         median microseconds of target build + loss for 16 frames on a captured HIP graph
+
+Evaluation only: there is no backward pass.  With a data set, the labels of a batch are read with the
+data set's own helpers (get_label, camera_to_lidar_box, filter_labels: a reference tree on sys.path or in
+SFA_REFERENCE_ROOT serves get_label), the maps come from the drop-in loader.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SFA_ROOT = os.path.join(REPO, "lidar-image_object-detection_-fpn_resnet-yolov8_amd", "sfa")
+for p in (REPO, SFA_ROOT):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from sfa_hip import runtime, synthetic  # noqa: E402
+
+
+class Cfg(dict):
+    __getattr__ = dict.__getitem__
+    __setattr__ = dict.__setitem__
+
+
+class AverageMeter:
+    """utils/misc.py:20-41, the part validate uses."""
+
+    def __init__(self):
+        self.sum, self.count = 0.0, 0
+
+    def update(self, val, n=1):
+        self.sum += val * n
+        self.count += n
+
+    @property
+    def avg(self):
+        return self.sum / max(self.count, 1)
+
+
+def make_model(args, device):
+    from models.model_utils import create_model
+    model = create_model(Cfg(arch=args.arch, heads=dict(runtime.DEFAULT_HEADS), head_conv=64,
+                             imagenet_pretrained=False))
+    if args.pretrained_path:
+        model.load_state_dict(torch.load(args.pretrained_path, map_location="cpu"))
+    else:
+        spec = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]
+        sd = synthetic.synthetic_state_dict(spec, args.seed)
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    return model.to(device).eval()
+
+
+def synthetic_batches(args, device):
+    """(maps (B, 3, H, W) on the device, labels (N, 8), offsets, hflipped) per batch."""
+    H = W = args.input_size
+    for start in range(0, args.synthetic, args.batch_size):
+        B = min(args.batch_size, args.synthetic - start)
+        x = synthetic.synthetic_bev(B, H, W, seed=args.seed + start)
+        labels, offsets = synthetic.synthetic_labels(B, seed=args.seed + start)
+        yield torch.from_numpy(x).to(device), labels, offsets, [False] * B
+
+
+def dataset_batches(args, device):
+    import config.kitti_config as cnf
+    from data_process import transformation
+    from data_process.kitti_data_utils import filter_labels
+    from data_process.kitti_dataloader import create_val_dataloader
+    H = W = args.input_size
+    configs = Cfg(dataset_dir=args.dataset_dir, input_size=(H, W), hm_size=(H // 4, W // 4), num_classes=3,
+                  max_objects=args.max_objects, num_samples=args.num_samples, distributed=False,
+                  batch_size=args.batch_size, num_workers=args.num_workers, pin_memory=True)
+    loader = create_val_dataloader(configs)
+    ds = loader.dataset
+    index = 0
+    for metadatas, bev_maps, _targets in loader:  # the val loader is not shuffled: batch i = the next B samples
+        B = int(bev_maps.shape[0])
+        rows, offsets = [], [0]
+        for i in range(index, index + B):
+            sample_id = int(ds.sample_id_list[i])
+            labels, has = ds.get_label(sample_id)
+            if has:
+                calib = ds.get_calib(sample_id)
+                labels[:, 1:] = transformation.camera_to_lidar_box(labels[:, 1:], calib.V2C, calib.R0, calib.P2)
+            labels = filter_labels(labels, cnf.boundary)
+            rows.append(np.asarray(labels, np.float32).reshape(-1, 8))
+            offsets.append(offsets[-1] + rows[-1].shape[0])
+        index += B
+        flips = [bool(f) for f in metadatas["hflipped"]]
+        yield bev_maps.to(device).float(), np.concatenate(rows), np.int64(offsets), flips
+
+
+def evaluate(model, batches, args, device):
+    from losses.losses import Compute_Loss
+    criterion = Compute_Loss(device)
+    hm = args.input_size // 4
+    builder = runtime.TargetBuilder(device, runtime.DEFAULT_BOUNDARY, (hm, hm), 3, args.max_objects)
+    losses, parts, frames = AverageMeter(), {}, 0
+    with torch.no_grad():
+        for x, labels, offsets, flips in batches:
+            B = int(x.shape[0])
+            targets = builder(labels, [int(o) for o in offsets], flips)
+            outputs = model(x)
+            total, stats = criterion(outputs, targets)
+            losses.update(stats["total_loss"], B)  # train.py:268 reduced_loss.item(), batch_size
+            for k, v in stats.items():
+                parts[k] = parts.get(k, 0.0) + v * B
+            frames += B
+    return losses.avg, {k: v / max(frames, 1) for k, v in parts.items()}, frames
+
+
+def timing(device, args, frames=16, reps=50):
+    """Median microseconds of sfa_build_targets + sfa_compute_loss for ``frames`` frames, one HIP graph."""
+    hm = args.input_size // 4
+    labels, offsets = synthetic.synthetic_labels(frames, seed=args.seed)
+    builder = runtime.TargetBuilder(device, runtime.DEFAULT_BOUNDARY, (hm, hm), 3, args.max_objects)
+    ev = runtime.LossEvaluator(device)
+    d_labels = torch.from_numpy(labels).to(device)
+    d_offsets = torch.from_numpy(offsets).to(device)
+    outs = {h: torch.from_numpy(synthetic.synthetic_logits((frames, c, hm, hm), args.seed, 60 + i)).to(device)
+            for i, (h, c) in enumerate(runtime.DEFAULT_HEADS.items())}
+    tg = builder.alloc(frames)
+
+    def step():
+        builder(d_labels, d_offsets, None, out=tg, verify=False)
+        ev(outs, tg, apply_sigmoid=True, verify=False)
+
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        step()
+    torch.cuda.current_stream().wait_stream(s)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step()
+    for _ in range(5):
+        graph.replay()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        graph.replay()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1e3)
+    return {"frames": frames, "reps": reps, "median_us": float(np.median(times)), "min_us": float(np.min(times))}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--arch", default="fpn_resnet_18", choices=["fpn_resnet_18", "resnet_18"])
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N synthetic frames instead of a data set")
+    ap.add_argument("--dataset_dir", default=None)
+    ap.add_argument("--pretrained_path", default=None)
+    ap.add_argument("--num_samples", type=int, default=None)
+    ap.add_argument("--batch_size", type=int, default=4)
+    ap.add_argument("--num_workers", type=int, default=2)
+    ap.add_argument("--input_size", type=int, default=608)
+    ap.add_argument("--max_objects", type=int, default=50)
+    ap.add_argument("--math", default=None, choices=["fp16"], help="also report the loss under SFA_MATH_FP16")
+    ap.add_argument("--timing", action="store_true")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--gpu_idx", type=int, default=0)
+    args = ap.parse_args(argv)
+    if not args.synthetic and not args.dataset_dir:
+        ap.error("give --synthetic N or --dataset_dir")
+    if args.input_size % 32:
+        ap.error("--input_size must be a multiple of 32")
+    device = torch.device("cuda", args.gpu_idx)
+    model = make_model(args, device)
+    source = synthetic_batches if args.synthetic else dataset_batches
+    t0 = time.time()
+    avg, parts, frames = evaluate(model, source(args, device), args, device)
+    result = {"arch": args.arch, "frames": frames, "math": "fp16x3", "val_loss": avg, "loss_stats": parts,
+              "seconds": round(time.time() - t0, 3)}
+    if args.math == "fp16":
+        model.set_math("fp16")
+        avg16, parts16, _ = evaluate(model, source(args, device), args, device)
+        result["fp16"] = {"val_loss": avg16, "loss_stats": parts16, "delta_vs_fp16x3": avg16 - avg}
+    if args.timing:
+        result["targets_plus_loss_graph"] = timing(device, args)
+    print(json.dumps(result))
+    return result
+
+
+if __name__ == "__main__":
+    main()
