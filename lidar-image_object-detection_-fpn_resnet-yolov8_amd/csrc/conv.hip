@@ -124,33 +124,49 @@ static int launch_fpn(const ConvArgs& a, hipStream_t st) {
   return SFA_E_UNSUPPORTED;
 }
 
-static int launch_conv_h3(const ConvArgs& a, int epilogue, hipStream_t st) {
+// The fp16 dispatch rules, once for both modes: TERMS = 2 is fp16x3 (two fp16 terms per operand, three
+// products per MAC), TERMS = 1 is SFA_MATH_FP16 (one product per MAC) on the TERMS = 1
+// instances of the three MFMA-bound kernel families. One rule table, so a shape takes the same tiles, K
+// order and split-K slices in both modes. What only fp16x3 has sits under `if constexpr (TERMS == 2)`:
+// other head counts and the other conv_x6g fallbacks, K-sliced weights / upsampled residuals (the FPN
+// convs stay fp16x3), 16-wide K-tiles. For those the one-product mode returns SFA_E_UNSUPPORTED and
+// launch_conv runs the fp16x3 path.
+template <int TERMS>
+static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
+  static_assert(TERMS == 1 || TERMS == 2, "fp16 terms per operand");
   if (!a.wh || !a.winv) return SFA_E_UNSUPPORTED;
+  const bool sliced = a.wstride || a.wk0 || a.res_up;  // conv_h3_kernel reads these; the others do not
+  if (TERMS == 1 && sliced) return SFA_E_UNSUPPORTED;
   auto ok = [](int rc) { return rc != SFA_E_UNSUPPORTED; };
   int rc = SFA_E_UNSUPPORTED;
-  const bool sliced = a.wstride || a.wk0 || a.res_up;  // conv_h3_kernel reads these; the others do not
   const bool strip = strip_ok(a) && !sliced;
   if (epilogue == EPI_HEAD) {
-    if (a.N == 320) rc = launch_conv_r3_cfg<256, 320, 32, EPI_HEAD, 1, 3, R3_HEAD_STAG>(a, st);
-    if (!ok(rc)) rc = launch_conv_x6g_cfg<256, 64, 32, EPI_HEAD, 1, 16, 3, 0, 64, 1>(a, st);  // other head counts
+    if (a.N == 320) rc = launch_conv_r3_cfg<256, 320, 32, EPI_HEAD, 1, 3, R3_HEAD_STAG, TERMS>(a, st);
+    if constexpr (TERMS == 2)
+      if (!ok(rc)) rc = launch_conv_x6g_cfg<256, 64, 32, EPI_HEAD, 1, 16, 3, 0, 64, 1>(a, st);  // other head counts
     return rc;
   }
-  if (a.fpn_gemm && sliced && a.nseg == 1 && a.seg[0].KH == 1 && a.seg[0].KW == 1 && a.seg[0].stride == 1) {
-    rc = launch_fpn(a, st);  // the FPN 1x1 convs (commuted)
-    if (ok(rc)) return rc;
-  }
-  if (a.res_up) {  // FPN skip convs of other widths: conv_r3, transposed float4 epilogue, float4 taps
-    if (a.N == 64)
-      rc = launch_conv_r3_cfg<128, 64, 32, EPI_STD, 4, 2, R3_FPN>(a, st);
-    else if (a.N % 128 == 0)
-      rc = launch_conv_r3_cfg<128, 128, 32, EPI_STD, 2, 2, R3_FPN>(a, st);
-    return rc;
+  if constexpr (TERMS == 2) {
+    if (a.fpn_gemm && sliced && a.nseg == 1 && a.seg[0].KH == 1 && a.seg[0].KW == 1 && a.seg[0].stride == 1) {
+      rc = launch_fpn(a, st);  // the FPN 1x1 convs (commuted)
+      if (ok(rc)) return rc;
+    }
+    if (a.res_up) {  // FPN skip convs of other widths: conv_r3, transposed float4 epilogue, float4 taps
+      if (a.N == 64)
+        rc = launch_conv_r3_cfg<128, 64, 32, EPI_STD, 4, 2, R3_FPN>(a, st);
+      else if (a.N % 128 == 0)
+        rc = launch_conv_r3_cfg<128, 128, 32, EPI_STD, 2, 2, R3_FPN>(a, st);
+      return rc;
+    }
   }
   if (a.N == 64) {
-    if (strip) rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64>(a, st);
-    if (!ok(rc) && a.Kpad >= 256) rc = launch_conv_h3_cfg<256, 64, 32, EPI_STD, 1, 32, 2, false, 0, 1>(a, st);
-    if (!ok(rc)) rc = launch_conv_h3_cfg<128, 64, 32, EPI_STD, 2, 16, 3, false, 0>(a, st);
-    if (!ok(rc) && !sliced) rc = launch_conv_x6g_cfg<256, 64, 32, EPI_STD, 1, 16, 3, 0, 64, 1>(a, st);
+    if (strip) rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64, TERMS>(a, st);
+    if (!ok(rc) && a.Kpad >= 256)
+      rc = launch_conv_h3_cfg<256, 64, 32, EPI_STD, 1, 32, 2, false, 0, 1, 64, TERMS>(a, st);
+    if constexpr (TERMS == 2) {
+      if (!ok(rc)) rc = launch_conv_h3_cfg<128, 64, 32, EPI_STD, 2, 16, 3, false, 0>(a, st);
+      if (!ok(rc) && !sliced) rc = launch_conv_x6g_cfg<256, 64, 32, EPI_STD, 1, 16, 3, 0, 64, 1>(a, st);
+    }
     return rc;
   }
   if (a.N % 128 == 0) {
@@ -160,68 +176,31 @@ static int launch_conv_h3(const ConvArgs& a, int epilogue, hipStream_t st) {
       // layer3 (362 128-row tiles for 512 block slots): 64 x 128 tiles at 3 blocks / CU fill the
       // chip; same per-element K order, so the same bits (tools/convbench4: 97.7 vs 102.0 us,
       // profiles/r04a_convbench4_stem_regw_tiles.txt)
-      rc = launch_conv_h3s_cfg<64, 128, 16, EPI_STD, 3, H3S_128>(b, st);
+      rc = launch_conv_h3s_cfg<64, 128, 16, EPI_STD, 3, H3S_128, TERMS>(b, st);
     else if (strip && b.ksplit == 2 && a.N == 512 && tile_rows(a) < 50000)
       // layer4 (184 128 x 128 tiles x 2 slices for 512 block slots): the 64-wide layer1 form, 128 x 64
       // tiles at 3 blocks / CU (736 blocks for 768 slots); same slices and per-element K order, so the
       // same bits (tools/convbench4: 102.4-105.0 vs 107.4-110.7 us, profiles/r04o_convbench4_layer4_splits.txt)
-      rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64>(b, st);
+      rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64, TERMS>(b, st);
     else if (strip && (3 * (a.seg[0].C >> 5)) % b.ksplit == 0)
-      rc = launch_conv_h3s_cfg<128, 128, 32, EPI_STD, 3, H3S_128W>(b, st);
+      rc = launch_conv_h3s_cfg<128, 128, 32, EPI_STD, 3, H3S_128W, TERMS>(b, st);
     else if (!strip && tile_rows(a) >= 50000)  // big-M stride-2 / two-segment: A from registers
       // (3 blocks / CU, late round 5: 150-153 VGPRs, 722 tiles in one round; per launch within 1 %, bench
       // +0.9 % with two steps in flight, bit-identical: profiles/r05bp_*)
-      rc = launch_conv_r3_cfg<128, 128, 32, EPI_STD, 3, 2, R3_BODY>(b, st);
+      rc = launch_conv_r3_cfg<128, 128, 32, EPI_STD, 3, 2, R3_BODY, TERMS>(b, st);
     if (!ok(rc)) {
       b.tile_cnt = nullptr;  // conv_h3: the reduce launch (conv_h3_kernel.h splitk_ticket)
       if ((a.Kpad / 32) % b.ksplit != 0) b.ksplit = 1;  // K not divisible into the slices: no split
       // the FPN low-resolution 1x1 convs left on conv_h3 (level 1's at mask 61): 64 x 128 tiles, 2 x 2 waves,
       // 3 blocks / CU, same K order (late round 5: 23.4 -> 18.0 us, bit-identical, profiles/r05bo_*; the
       // layer3 / 4 convs on the same tiles were slower, r05bn_*)
-      if (sliced && a.seg[0].KH == 1 && a.seg[0].KW == 1)
-        rc = launch_conv_h3_cfg<64, 128, 32, EPI_STD, 3, 32, 2, false, 2, 1, 64>(b, st);
-      if (!ok(rc)) rc = launch_conv_h3_cfg<128, 128, 32, EPI_STD, 2, 32, 2, false, 2, 1>(b, st);
+      if constexpr (TERMS == 2)
+        if (sliced && a.seg[0].KH == 1 && a.seg[0].KW == 1)
+          rc = launch_conv_h3_cfg<64, 128, 32, EPI_STD, 3, 32, 2, false, 2, 1, 64>(b, st);
+      if (!ok(rc)) rc = launch_conv_h3_cfg<128, 128, 32, EPI_STD, 2, 32, 2, false, 2, 1, 128, TERMS>(b, st);
     }
-    if (!ok(rc) && !sliced) rc = launch_conv_x6g_cfg<128, 128, 32, EPI_STD, 2, 16, 3, 0, 128, 1>(b, st);
-  }
-  return rc;
-}
-
-// SFA_MATH_FP16 (one fp16 product per MAC): the TERMS = 1 instances of the three MFMA-bound
-// fp16x3 kernel families, with launch_conv_h3's shape rules and tile choices, so a shape takes the same
-// tiles, K order and split-K slices in both modes. SFA_E_UNSUPPORTED for everything else (other head
-// counts, K-sliced weights / upsampled residuals — the FPN convs stay fp16x3 —, shapes on the conv_x6g
-// fallback, 16-wide K-tiles): launch_conv then runs the fp16x3 path.
-static int launch_conv_h1(const ConvArgs& a, int epilogue, hipStream_t st) {
-  if (!a.wh || !a.winv || a.wstride || a.wk0 || a.res_up) return SFA_E_UNSUPPORTED;
-  auto ok = [](int rc) { return rc != SFA_E_UNSUPPORTED; };
-  int rc = SFA_E_UNSUPPORTED;
-  const bool strip = strip_ok(a);
-  if (epilogue == EPI_HEAD) {
-    if (a.N == 320) rc = launch_conv_r3_cfg<256, 320, 32, EPI_HEAD, 1, 3, R3_HEAD_STAG, 1>(a, st);
-    return rc;
-  }
-  if (a.N == 64) {
-    if (strip) rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64, 1>(a, st);
-    if (!ok(rc) && a.Kpad >= 256) rc = launch_conv_h3_cfg<256, 64, 32, EPI_STD, 1, 32, 2, false, 0, 1, 64, 1>(a, st);
-    return rc;
-  }
-  if (a.N % 128 == 0) {
-    ConvArgs b = a;
-    b.ksplit = pick_ksplit(a);
-    if (strip && b.ksplit == 1 && a.N == 256 && tile_rows(a) < 50000)
-      rc = launch_conv_h3s_cfg<64, 128, 16, EPI_STD, 3, H3S_128, 1>(b, st);
-    else if (strip && b.ksplit == 2 && a.N == 512 && tile_rows(a) < 50000)
-      rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64, 1>(b, st);
-    else if (strip && (3 * (a.seg[0].C >> 5)) % b.ksplit == 0)
-      rc = launch_conv_h3s_cfg<128, 128, 32, EPI_STD, 3, H3S_128W, 1>(b, st);
-    else if (!strip && tile_rows(a) >= 50000)
-      rc = launch_conv_r3_cfg<128, 128, 32, EPI_STD, 3, 2, R3_BODY, 1>(b, st);
-    if (!ok(rc)) {
-      b.tile_cnt = nullptr;  // conv_h3: the reduce launch
-      if ((a.Kpad / 32) % b.ksplit != 0) b.ksplit = 1;
-      rc = launch_conv_h3_cfg<128, 128, 32, EPI_STD, 2, 32, 2, false, 2, 1, 128, 1>(b, st);
-    }
+    if constexpr (TERMS == 2)
+      if (!ok(rc) && !sliced) rc = launch_conv_x6g_cfg<128, 128, 32, EPI_STD, 2, 16, 3, 0, 128, 1>(b, st);
   }
   return rc;
 }
@@ -260,15 +239,15 @@ int launch_conv(const ConvArgs& a, int epilogue, int math, hipStream_t st) {
       set_error("conv: upsampled residual needs even output dims and no full-res residual");
       return SFA_E_UNSUPPORTED;
     }
-    return launch_conv_h3(a, epilogue, st);
+    return launch_conv_h<2>(a, epilogue, st);
   }
   if (math == SFA_MATH_FP16) {  // never fails where fp16x3 succeeds: shapes without a one-product kernel run fp16x3
-    const int rc = launch_conv_h1(a, epilogue, st);
+    const int rc = launch_conv_h<1>(a, epilogue, st);
     if (rc != SFA_E_UNSUPPORTED) return rc;
     math = SFA_MATH_FP16X3;
   }
   if (math == SFA_MATH_FP16X3) {
-    const int rc = launch_conv_h3(a, epilogue, st);
+    const int rc = launch_conv_h<2>(a, epilogue, st);
     if (rc != SFA_E_UNSUPPORTED) return rc;
   }
   if (math == SFA_MATH_BF16X6 || math == SFA_MATH_FP16X3) {

@@ -879,385 +879,356 @@ extern "C" int64_t sfa_forward_buffer_offset(const sfa_model* m, int batch, int 
     if (rc_ != SFA_OK) return rc_; \
   } while (0)
 
-// One pass over B <= forward_max_batch(H, W) frames (arguments checked by sfa_model_forward).
-static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B, int H, int W,
-                        float* const* head_out, void* workspace, void* stream) {
-  const Bufs bf = plan_bufs(&m->arch, m->backbone, B, H, W);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  char* ws = reinterpret_cast<char*>(workspace);
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  const float* wb = m->w;
-  const Plan& p = m->plan;
+namespace sfa {
 
-  // fp16x3: every conv input's max |x| is recorded by its producer (slots zeroed here)
+// A map that a conv reads: NHWC (B, h, w, c) and the amax slot of its producer.
+struct Map {
+  const float* x;
+  int h, w, c, slot;
+};
+
+static int blk_slot(int li, int bi, int ci) { return AM_BLK + 4 * li + 2 * bi + ci; }
+
+// One level of the FPN top-down path (Pass::fpn_row).
+struct FpnRow {
+  Map lo;         // the low-resolution input
+  float* up;      // lo upsampled x2: what the concat form reads
+  float* lo_out;  // W_a . lo at the low resolution: what the commuted form adds, upsampled, in its epilogue
+  Map skip;       // the skip map, at twice lo's dims
+  float* out;
+  int out_slot;
+};
+
+// One forward pass over B frames: what its stages share, and the stages in the order they run.
+struct Pass {
+  const sfa_model* m;
+  const float* wb;
+  const Plan& p;
+  const Bufs bf;
+  char* ws;
+  hipStream_t st;  // the caller's stream
+  int B, H, W;
+  // fp16x3: every conv input's max |x| is recorded by its producer (slots zeroed by forward_pass)
   // SFA_MATH_FP16: the fp16x3 plumbing (scales, amax words, tickets, patch stem, commuted FPN) with one
   // product per MAC in the body convs and the heads; the stem and the FPN convs stay fp16x3 (math_sf)
-  const bool h3 = m->math == SFA_MATH_FP16X3 || m->math == SFA_MATH_FP16;
-  const int math_sf = m->math == SFA_MATH_FP16 ? SFA_MATH_FP16X3 : m->math;
-  auto AM = [&](int slot) -> unsigned* {
+  bool h3;
+  int math_sf;
+
+  Pass(const sfa_model* model, int B_, int H_, int W_, void* workspace, void* stream)
+      : m(model), wb(model->w), p(model->plan), bf(plan_bufs(&model->arch, model->backbone, B_, H_, W_)),
+        ws(reinterpret_cast<char*>(workspace)), st(reinterpret_cast<hipStream_t>(stream)), B(B_), H(H_), W(W_),
+        h3(model->math == SFA_MATH_FP16X3 || model->math == SFA_MATH_FP16),
+        math_sf(model->math == SFA_MATH_FP16 ? SFA_MATH_FP16X3 : model->math) {}
+
+  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+  unsigned* AM(int slot) const {
     return h3 ? reinterpret_cast<unsigned*>(ws + bf.amax) + (size_t)slot * B * SFA_AMAX_WORDS : nullptr;
-  };
-  auto blk_slot = [](int li, int bi, int ci) { return AM_BLK + 4 * li + 2 * bi + ci; };
-  if (h3)  // the amax words and the split-K tickets after them
-    SFA_RC(launch_zero_words(ws + bf.amax, bf.tick + 4 * bf.tick_words * 4 - bf.amax, st));
-  auto io = [&](ConvArgs& a, int in0, int in1, int out) {
+  }
+  // split-K tickets of the layer4 convs (the only split ones, conv.hip pick_ksplit): the slice that
+  // finishes last combines the partials in the conv kernel (no reduce launch); fp16x3 only
+  unsigned* TK(int li, int ci) const {
+    return h3 && li == 3 && m->splitk_tickets ? reinterpret_cast<unsigned*>(ws + bf.tick) + (size_t)ci * bf.tick_words
+                                              : nullptr;
+  }
+  void io(ConvArgs& a, int in0, int in1, int out) const {
     a.amax_in[0] = in0 >= 0 ? AM(in0) : nullptr;
     a.amax_in[1] = in1 >= 0 ? AM(in1) : nullptr;
     a.amax_out = out >= 0 ? AM(out) : nullptr;
     a.part = F(bf.part);
     a.part_floats = bf.part_floats;
-  };
-
-  const int H2 = H / 2, W2 = W / 2;
-  // The patch stem (fp16x3) reads the caller's layout itself, scales every tile by its own max |x|
-  // and max-pools in its epilogue: no layout conversion, no input amax pass, no max-pool launch
-  // (stem_patch_kernel.h).
-  const bool patch_stem = h3 && m->stem_patch && H2 % 16 == 0 && W2 % 16 == 0;
-  const float* xin = x;
-  if (patch_stem) {
-  } else if (in_layout != SFA_IN_NHWC4) {
-    SFA_RC(launch_nchw3_to_nhwc4(x, F(bf.xin), B, H, W, in_layout == SFA_IN_NCHW3_FLIP_HW,
-                                 AM(AM_INPUT), st));
-    xin = F(bf.xin);
-  } else if (h3) {
-    SFA_RC(launch_amax_nhwc4(x, B, H, W, AM(AM_INPUT), st));
   }
-  // stem conv7x7/s2/p3 + BN + ReLU (fpn_resnet.py:179-181) + max-pool (:182): the patch stem sends
-  // the tile-border cells' parts through a side buffer and a merge pass; otherwise the conv and the
-  // max-pool kernel.
-  {
+
+  // Timing events 2 pair, 2 pair + 1 around one launch on stream s (sfa_model_set_probe), never while s
+  // is being captured.
+  template <class Launch>
+  int probed(int pair, hipStream_t s, Launch launch) const {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool probe = (m->probe & SFA_PROBE_HEADS) && hipStreamIsCapturing(s, &cap) == hipSuccess &&
+                       cap == hipStreamCaptureStatusNone;
+    if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[2 * pair], s));
+    SFA_RC(launch());
+    if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[2 * pair + 1], s));
+    return SFA_OK;
+  }
+
+  // stem conv7x7/s2/p3 + BN + ReLU (fpn_resnet.py:179-181) + max-pool (:182) -> p0
+  int stem(const float* x, int in_layout) const {
+    const int H2 = H / 2, W2 = W / 2;
+    // The patch stem (fp16x3) reads the caller's layout itself, scales every tile by its own max |x|
+    // and max-pools in its epilogue: no layout conversion, no input amax pass, no max-pool launch
+    // (stem_patch_kernel.h).
+    const bool patch_stem = h3 && m->stem_patch && H2 % 16 == 0 && W2 % 16 == 0;
+    const float* xin = x;
+    if (patch_stem) {
+    } else if (in_layout != SFA_IN_NHWC4) {
+      SFA_RC(launch_nchw3_to_nhwc4(x, F(bf.xin), B, H, W, in_layout == SFA_IN_NCHW3_FLIP_HW, AM(AM_INPUT), st));
+      xin = F(bf.xin);
+    } else if (h3) {
+      SFA_RC(launch_amax_nhwc4(x, B, H, W, AM(AM_INPUT), st));
+    }
     ConvArgs a = conv_args(wb, p.stem, B, H2, W2, patch_stem ? F(bf.p0) : F(bf.s0), nullptr, 1);
     a.seg[0] = seg(xin, B, H, W, 4, 7, 2, 3);  // the patch stem reads NCHW3 planes through it too
     io(a, AM_INPUT, -1, AM_STEM);
-    if (patch_stem) {
+    if (patch_stem) {  // the tile-border cells' parts go through a side buffer and a merge pass
       a.amax_in[0] = nullptr;  // per-tile scales
       a.stem_in = in_layout == SFA_IN_NHWC4 ? STEM_IN_NHWC4
                                              : (in_layout == SFA_IN_NCHW3_FLIP_HW ? STEM_IN_NCHW3_FLIP : STEM_IN_NCHW3);
       a.part = F(bf.s0);  // the (here unused) unfused stem buffer
       a.part_floats = (size_t)B * H2 * W2 * 64;
-      SFA_RC(launch_stem_patch(a, st));
-    } else {
-      SFA_RC(launch_conv(a, EPI_STD, math_sf, st));
+      return launch_stem_patch(a, st);
     }
+    SFA_RC(launch_conv(a, EPI_STD, math_sf, st));
+    return launch_maxpool3s2(F(bf.s0), F(bf.p0), B, H2, W2, 64, st);
   }
-  if (!patch_stem) SFA_RC(launch_maxpool3s2(F(bf.s0), F(bf.p0), B, H2, W2, 64, st));  // :182
-  // residual layers (fpn_resnet.py:184-187)
-  const float* xcur = F(bf.p0);
-  int xslot = AM_STEM;  // maxpool keeps the stem's max
-  int h = H / 4, w = W / 4, cin = 64;
-  // split-K tickets of the layer4 convs (the only split ones, conv.hip pick_ksplit): the slice that
-  // finishes last combines the partials in the conv kernel (no reduce launch); fp16x3 only
-  auto TK = [&](int li, int ci) -> unsigned* {
-    return h3 && li == 3 && m->splitk_tickets ? reinterpret_cast<unsigned*>(ws + bf.tick) + (size_t)ci * bf.tick_words : nullptr;
-  };
-  for (int li = 0; li < 4; ++li) {
-    const int planes = 64 << li;
-    const int stride = li == 0 ? 1 : 2;
-    const int oh = h / stride, ow = w / stride;
-    float* t = F(bf.t[li]);
-    float* av = F(bf.a[li]);
-    float* lv = F(bf.l[li]);
-    // block 0: conv1 (stride) ; conv2 (+ fused 1x1/s2 downsample for li > 0)
-    {
-      ConvArgs a = conv_args(wb, p.blk[li][0][0], B, oh, ow, t, nullptr, 1);
-      a.seg[0] = seg(xcur, B, h, w, cin, 3, stride, 1);
-      io(a, xslot, -1, blk_slot(li, 0, 0));
-      a.tile_cnt = TK(li, 0);
-      a.tile_cnt_words = (int)bf.tick_words;
-      SFA_RC(launch_conv(a, EPI_STD, m->math, st));
-    }
-    {
-      ConvArgs a = conv_args(wb, p.blk[li][0][1], B, oh, ow, av, li == 0 ? xcur : nullptr, 1);
-      a.seg[0] = seg(t, B, oh, ow, planes, 3, 1, 1);
-      if (li > 0) {
-        a.nseg = 2;
-        a.kseg1 = 9 * planes;
-        a.seg[1] = seg(xcur, B, h, w, cin, 1, stride, 0);
+
+  // residual layers (fpn_resnet.py:184-187), p0 -> l[0..3]. Per layer, block 0: conv1 (stride), conv2 + the
+  // block's input (li > 0: through the fused 1x1 / stride-2 downsample, a second K-segment); block 1: conv1,
+  // conv2 + block 0's output. Conv k's ticket index and output slot are k.
+  int layers() const {
+    Map x = {F(bf.p0), H / 4, W / 4, 64, AM_STEM};  // maxpool keeps the stem's max
+    for (int li = 0; li < 4; ++li) {
+      const int planes = 64 << li, stride = li == 0 ? 1 : 2;
+      const int oh = x.h / stride, ow = x.w / stride;
+      float *t = F(bf.t[li]), *av = F(bf.a[li]), *lv = F(bf.l[li]);
+      const struct {
+        Map in;
+        int stride;
+        float* y;
+        const float* res;
+        bool downsample;  // x as the second segment
+      } convs[4] = {{x, stride, t, nullptr, false},
+                    {{t, oh, ow, planes, blk_slot(li, 0, 0)}, 1, av, li == 0 ? x.x : nullptr, li > 0},
+                    {{av, oh, ow, planes, blk_slot(li, 0, 1)}, 1, t, nullptr, false},
+                    {{t, oh, ow, planes, blk_slot(li, 1, 0)}, 1, lv, av, false}};
+      for (int k = 0; k < 4; ++k) {
+        const auto& cv = convs[k];
+        ConvArgs a = conv_args(wb, p.blk[li][k >> 1][k & 1], B, oh, ow, cv.y, cv.res, 1);
+        a.seg[0] = seg(cv.in.x, B, cv.in.h, cv.in.w, cv.in.c, 3, cv.stride, 1);
+        if (cv.downsample) {
+          a.nseg = 2;
+          a.kseg1 = 9 * planes;
+          a.seg[1] = seg(x.x, B, x.h, x.w, x.c, 1, stride, 0);
+        }
+        io(a, cv.in.slot, cv.downsample ? x.slot : -1, blk_slot(li, k >> 1, k & 1));
+        a.tile_cnt = TK(li, k);
+        a.tile_cnt_words = (int)bf.tick_words;
+        SFA_RC(launch_conv(a, EPI_STD, m->math, st));
       }
-      io(a, blk_slot(li, 0, 0), li > 0 ? xslot : -1, blk_slot(li, 0, 1));
-      a.tile_cnt = TK(li, 1);
-      a.tile_cnt_words = (int)bf.tick_words;
-      SFA_RC(launch_conv(a, EPI_STD, m->math, st));
+      x = {lv, oh, ow, planes, blk_slot(li, 1, 1)};
     }
-    // block 1
-    {
-      ConvArgs a = conv_args(wb, p.blk[li][1][0], B, oh, ow, t, nullptr, 1);
-      a.seg[0] = seg(av, B, oh, ow, planes, 3, 1, 1);
-      io(a, blk_slot(li, 0, 1), -1, blk_slot(li, 1, 0));
-      a.tile_cnt = TK(li, 2);
-      a.tile_cnt_words = (int)bf.tick_words;
-      SFA_RC(launch_conv(a, EPI_STD, m->math, st));
-    }
-    {
-      ConvArgs a = conv_args(wb, p.blk[li][1][1], B, oh, ow, lv, av, 1);
-      a.seg[0] = seg(t, B, oh, ow, planes, 3, 1, 1);
-      io(a, blk_slot(li, 1, 0), -1, blk_slot(li, 1, 1));
-      a.tile_cnt = TK(li, 3);
-      a.tile_cnt_words = (int)bf.tick_words;
-      SFA_RC(launch_conv(a, EPI_STD, m->math, st));
-    }
-    xcur = lv;
-    xslot = blk_slot(li, 1, 1);
-    h = oh;
-    w = ow;
-    cin = planes;
+    return SFA_OK;
   }
-  const int H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16;
-  if (m->backbone == SFA_BACKBONE_DECONV) {
-    // Plain resnet_18 (resnet.py:230-234): three ConvTranspose2d(4, s2, p1) + BN + ReLU, layer4 ->
-    // (H/4, W/4, 256), one launch each (deconv_h3_kernel.h); then every head in one fused launch
-    // (conv3x3 -> ReLU -> conv1x1, the KFPN level-0 heads kernel's shape) into a channel-planar block,
-    // and its relayout into the caller's per-head buffers.  All on the caller's stream.
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool probe = (m->probe & SFA_PROBE_HEADS) && hipStreamIsCapturing(st, &cap) == hipSuccess &&
-                       cap == hipStreamCaptureStatusNone;
-    const float* dx = F(bf.l[3]);
-    int dslot = blk_slot(3, 1, 1), dh = H / 32, dw = W / 32;
+
+  // Where each head's channels sit in a channel-planar level block, and the caller's buffers.
+  KfpnOut head_layout(float* const* head_out) const {
+    KfpnOut ko;
+    memset(&ko, 0, sizeof ko);
+    for (int j = 0; j < m->arch.num_heads; ++j) {
+      ko.ptr[j] = head_out[j];
+      ko.ch[j] = m->arch.head_channels[j];
+      ko.off[j] = ko.total_ch;
+      ko.total_ch += ko.ch[j];
+    }
+    ko.num_heads = m->arch.num_heads;
+    return ko;
+  }
+
+  // Detection heads (fpn_resnet.py:219-233): all heads of one level in one launch, conv3x3 -> ReLU ->
+  // conv1x1 fused, into the channel-planar block `out`.
+  ConvArgs head_args(const Map& in, const PHeads& hp, const KfpnOut& ko, float* out) const {
+    ConvArgs a;
+    memset(&a, 0, sizeof a);
+    a.nseg = 1;
+    a.seg[0] = seg(in.x, B, in.h, in.w, in.c, 3, 1, 1);
+    a.Kpad = hp.K;
+    a.w = wb + hp.w3;
+    a.wx = reinterpret_cast<const uint16_t*>(wb + hp.wx);
+    a.wh = reinterpret_cast<const uint16_t*>(wb + hp.wh);
+    a.winv = wb + hp.winv;
+    a.amax_in[0] = AM(in.slot);
+    a.bias = wb + hp.b3;
+    a.M = B * in.h * in.w;
+    a.N = hp.N;
+    a.OH = in.h;
+    a.OW = in.w;
+    a.relu = 1;
+    a.hw1 = wb + hp.w1;
+    a.hb1 = wb + hp.b1;
+    for (int j = 0; j < ko.num_heads; ++j) {
+      a.hch[j] = ko.ch[j];
+      a.hoff[j] = ko.off[j];
+    }
+    a.hout = out;
+    return a;
+  }
+
+  // Plain resnet_18 (resnet.py:230-234): three ConvTranspose2d(4, s2, p1) + BN + ReLU, layer4 ->
+  // (H/4, W/4, 256), one launch each (deconv_h3_kernel.h); then every head in one fused launch (the KFPN
+  // level-0 heads kernel's shape) into a channel-planar block, and its relayout into the caller's per-head
+  // buffers.  All on the caller's stream; probe pairs 0..2 around the transposed convs, 3 around the heads.
+  int deconv_tail(float* const* head_out) const {
+    Map x = {F(bf.l[3]), H / 32, W / 32, 512, blk_slot(3, 1, 1)};
     for (int i = 0; i < 3; ++i) {
       const PDeconv& pd = p.dec[i];
       DeconvArgs d;
       memset(&d, 0, sizeof d);
-      d.x = dx;
-      d.H = dh;
-      d.W = dw;
+      d.x = x.x;
+      d.H = x.h;
+      d.W = x.w;
       d.C = pd.C;
       d.logC = ilog2(pd.C);
-      d.bytes = (unsigned)((size_t)B * dh * dw * pd.C * 4);  // <= 16 H W bytes per frame: inside the pass limit
+      d.bytes = (unsigned)((size_t)B * x.h * x.w * pd.C * 4);  // <= 16 H W bytes per frame: inside the pass limit
       d.wh = reinterpret_cast<const uint16_t*>(wb + pd.wh);
       d.winv = wb + pd.winv;
       d.bias = wb + pd.b;
-      d.amax_in = AM(dslot);
+      d.amax_in = AM(x.slot);
       d.amax_out = AM(AM_DECONV + i);
       d.y = F(bf.d[i]);
-      d.M = B * dh * dw;
+      d.M = B * x.h * x.w;
       d.N = pd.N;
       d.K = pd.K;
-      if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[2 * i], st));
-      SFA_RC(launch_deconv(d, B, st));
-      if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[2 * i + 1], st));
-      dx = F(bf.d[i]);
-      dslot = AM_DECONV + i;
-      dh *= 2;
-      dw *= 2;
+      SFA_RC(probed(i, st, [&] { return launch_deconv(d, B, st); }));
+      x = {F(bf.d[i]), 2 * x.h, 2 * x.w, pd.N, AM_DECONV + i};
     }
-    int hoff[SFA_MAX_HEADS] = {0};
-    int nch = 0;
-    for (int j = 0; j < m->arch.num_heads; ++j) {
-      hoff[j] = nch;
-      nch += m->arch.head_channels[j];
-    }
-    const PHeads& hp = p.heads[0];
-    ConvArgs a;
-    memset(&a, 0, sizeof a);
-    a.nseg = 1;
-    a.seg[0] = seg(dx, B, H4, W4, 256, 3, 1, 1);
-    a.Kpad = hp.K;
-    a.w = wb + hp.w3;
-    a.wx = reinterpret_cast<const uint16_t*>(wb + hp.wx);
-    a.wh = reinterpret_cast<const uint16_t*>(wb + hp.wh);
-    a.winv = wb + hp.winv;
-    a.amax_in[0] = AM(AM_DECONV + 2);
-    a.bias = wb + hp.b3;
-    a.M = B * H4 * W4;
-    a.N = hp.N;
-    a.OH = H4;
-    a.OW = W4;
-    a.relu = 1;
-    a.hw1 = wb + hp.w1;
-    a.hb1 = wb + hp.b1;
-    KfpnOut ko;
-    memset(&ko, 0, sizeof ko);
-    for (int j = 0; j < m->arch.num_heads; ++j) {
-      a.hch[j] = ko.ch[j] = m->arch.head_channels[j];
-      a.hoff[j] = ko.off[j] = hoff[j];
-      ko.ptr[j] = head_out[j];
-    }
-    ko.num_heads = m->arch.num_heads;
-    ko.total_ch = nch;
-    a.hout = F(bf.L0);
-    if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[6], st));
-    SFA_RC(launch_conv(a, EPI_HEAD, m->math, st));
-    if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[7], st));
-    return launch_heads_relayout(F(bf.L0), ko, B, H4, W4, st);
+    const KfpnOut ko = head_layout(head_out);
+    const ConvArgs a = head_args(x, p.heads[0], ko, F(bf.L0));
+    SFA_RC(probed(3, st, [&] { return launch_conv(a, EPI_HEAD, m->math, st); }));
+    return launch_heads_relayout(F(bf.L0), ko, B, x.h, x.w, st);
   }
-  // FPN top-down (fpn_resnet.py:197-210): bilinear x2 (align_corners) + channel
-  // concat, read by the 1x1 conv as two K-segments (no concat buffer).
-  // fp16x3: each FPN 1x1 conv over cat(up(x), skip) runs as two convs on K-slices of its
-  // packed weights, W_a up(x) + W_b skip + b = up(W_a x) + W_b skip + b (bilinear resize and a
-  // 1x1 conv commute; the interpolation weights sum to 1): W_a x at the LOW resolution into a
-  // half-res buffer (no bias), then W_b skip + b with that buffer added bilinearly upsampled in
-  // the epilogue. A quarter of W_a's MACs, and up_level1 is never materialised.
-  auto commute_at = [&](int f) { return h3 && ((m->fpn_commute >> f) & 1); };
-  float* fpn_lo[3] = {F(bf.up1), F(bf.up1) + (size_t)B * (H / 32) * (W / 32) * 256,
-                      F(bf.up1) + (size_t)B * (H / 32) * (W / 32) * 256 + (size_t)B * H16 * W16 * 128};
-  auto fpn_pair = [&](int f, const float* x, int xh, int xw, int xc, int xslot_in, const float* skip, int sc,
-                      int skip_slot, float* out, int out_slot, hipStream_t fs) -> int {
+
+  // FPN top-down (fpn_resnet.py:197-210), level f = conv_up_level(f + 1) over cat(up(lo), skip).
+  FpnRow fpn_row(int f) const {
+    const int H16 = H / 16, W16 = W / 16, H8 = H / 8, W8 = W / 8;
+    float* lo1 = F(bf.up1) + (size_t)B * (H / 32) * (W / 32) * 256;  // the three lo_out share up1's buffer
+    const FpnRow rows[3] = {
+        {{F(bf.l[3]), H / 32, W / 32, 512, blk_slot(3, 1, 1)}, F(bf.up1), F(bf.up1),
+         {F(bf.l[2]), H16, W16, 256, blk_slot(2, 1, 1)}, F(bf.c1), AM_FPN + 0},
+        {{F(bf.c1), H16, W16, 256, AM_FPN + 0}, F(bf.up2), lo1,
+         {F(bf.l[1]), H8, W8, 128, blk_slot(1, 1, 1)}, F(bf.c2), AM_FPN + 1},
+        {{F(bf.c2), H8, W8, 128, AM_FPN + 1}, F(bf.up3), lo1 + (size_t)B * H16 * W16 * 128,
+         {F(bf.l[0]), H / 4, W / 4, 64, blk_slot(0, 1, 1)}, F(bf.up4), AM_FPN + 2}};
+    return rows[f];
+  }
+
+  // One FPN level on stream fs. Concat form: bilinear x2 (align_corners) + channel concat, read by the
+  // 1x1 conv as two K-segments (no concat buffer).
+  // Commuted form (fp16x3, m->fpn_commute bit f): the conv runs as two convs on K-slices of its packed
+  // weights, W_a up(x) + W_b skip + b = up(W_a x) + W_b skip + b (bilinear resize and a 1x1 conv commute;
+  // the interpolation weights sum to 1): W_a x at the LOW resolution into a half-res buffer (no bias),
+  // then W_b skip + b with that buffer added bilinearly upsampled in the epilogue. A quarter of W_a's
+  // MACs, and up_level1 is never materialised.
+  int fpn_level(int f, hipStream_t fs) const {
+    const FpnRow r = fpn_row(f);
     const PConv& pc = p.fpn[f];
-    {
-      ConvArgs a = conv_args(wb, pc, B, xh, xw, fpn_lo[f], nullptr, 0);
-      a.bias = nullptr;
-      a.Kpad = xc;
-      a.wstride = pc.Kpad;
-      a.wk0 = 0;
-      a.seg[0] = seg(x, B, xh, xw, xc, 1, 1, 0);
-      a.fpn_gemm = (m->fpn_gemm >> f) & 1;
-      io(a, xslot_in, -1, -1);
-      SFA_RC(launch_conv(a, EPI_STD, math_sf, fs));
-    }
-    ConvArgs a = conv_args(wb, pc, B, 2 * xh, 2 * xw, out, nullptr, 0);
-    a.Kpad = sc;
-    a.wstride = pc.Kpad;
-    a.wk0 = xc;
-    a.seg[0] = seg(skip, B, 2 * xh, 2 * xw, sc, 1, 1, 0);
-    a.res_up = fpn_lo[f];
-    a.res_sh = xh > 1 ? (float)(xh - 1) / (float)(2 * xh - 1) : 0.f;
-    a.res_sw = xw > 1 ? (float)(xw - 1) / (float)(2 * xw - 1) : 0.f;
-    a.fpn_gemm = (m->fpn_gemm >> (3 + f)) & 1;
-    io(a, skip_slot, -1, out_slot);
-    return launch_conv(a, EPI_STD, math_sf, fs);
-  };
-  if (commute_at(0)) {
-    SFA_RC(fpn_pair(0, F(bf.l[3]), H / 32, W / 32, 512, blk_slot(3, 1, 1), F(bf.l[2]), 256, blk_slot(2, 1, 1),
-                    F(bf.c1), AM_FPN + 0, st));
-  } else {
-    SFA_RC(launch_upsample2x(F(bf.l[3]), F(bf.up1), B, H / 32, W / 32, 512, st));
-    {
-      ConvArgs a = conv_args(wb, p.fpn[0], B, H16, W16, F(bf.c1), nullptr, 0);
+    ConvArgs a = conv_args(wb, pc, B, r.skip.h, r.skip.w, r.out, nullptr, 0);
+    if (!(h3 && ((m->fpn_commute >> f) & 1))) {
+      // levels 1 and 2 find lo upsampled already (their heads' input); level 0's has no other reader
+      if (f == 0) SFA_RC(launch_upsample2x(r.lo.x, r.up, B, r.lo.h, r.lo.w, r.lo.c, fs));
       a.nseg = 2;
-      a.kseg1 = 512;
-      a.seg[0] = seg(F(bf.up1), B, H16, W16, 512, 1, 1, 0);
-      a.seg[1] = seg(F(bf.l[2]), B, H16, W16, 256, 1, 1, 0);
-      io(a, blk_slot(3, 1, 1), blk_slot(2, 1, 1), AM_FPN + 0);  // up1 = upsample(layer4)
-      SFA_RC(launch_conv(a, EPI_STD, math_sf, st));
+      a.kseg1 = r.lo.c;
+      a.seg[0] = seg(r.up, B, r.skip.h, r.skip.w, r.lo.c, 1, 1, 0);
+      a.seg[1] = seg(r.skip.x, B, r.skip.h, r.skip.w, r.skip.c, 1, 1, 0);
+      io(a, r.lo.slot, r.skip.slot, r.out_slot);
+      return launch_conv(a, EPI_STD, math_sf, fs);
     }
-  }
-  SFA_RC(launch_upsample2x(F(bf.c1), F(bf.up2), B, H16, W16, 256, st));
-  // Detection heads (fpn_resnet.py:219-233): per level all heads in one launch,
-  // conv3x3 -> ReLU -> conv1x1 fused; channel-planar level outputs.
-  int hoff[SFA_MAX_HEADS] = {0};
-  int nch = 0;
-  for (int j = 0; j < m->arch.num_heads; ++j) {
-    hoff[j] = nch;
-    nch += m->arch.head_channels[j];
-  }
-  const float* lin[3] = {F(bf.up2), F(bf.up3), F(bf.up4)};
-  const int lh[3] = {H8, H4, H4}, lw[3] = {W8, W4, W4};
-  float* lout[3] = {F(bf.L0), F(bf.L1), F(bf.L2)};
-  auto head_args = [&](int f) -> ConvArgs {
-    const PHeads& hp = p.heads[f];
-    ConvArgs a;
-    memset(&a, 0, sizeof a);
-    a.nseg = 1;
-    a.seg[0] = seg(lin[f], B, lh[f], lw[f], kFpnC[f], 3, 1, 1);
-    a.Kpad = hp.K;
-    a.w = wb + hp.w3;
-    a.wx = reinterpret_cast<const uint16_t*>(wb + hp.wx);
-    a.wh = reinterpret_cast<const uint16_t*>(wb + hp.wh);
-    a.winv = wb + hp.winv;
-    a.amax_in[0] = AM(AM_FPN + f);  // up2 / up3 / up4 come from conv_up_level1/2/3
-    a.bias = wb + hp.b3;
-    a.M = B * lh[f] * lw[f];
-    a.N = hp.N;
-    a.OH = lh[f];
-    a.OW = lw[f];
-    a.relu = 1;
-    a.hw1 = wb + hp.w1;
-    a.hb1 = wb + hp.b1;
-    for (int j = 0; j < m->arch.num_heads; ++j) {
-      a.hch[j] = m->arch.head_channels[j];
-      a.hoff[j] = hoff[j];
+    {
+      ConvArgs lo = conv_args(wb, pc, B, r.lo.h, r.lo.w, r.lo_out, nullptr, 0);
+      lo.bias = nullptr;
+      lo.Kpad = r.lo.c;
+      lo.wstride = pc.Kpad;
+      lo.wk0 = 0;
+      lo.seg[0] = seg(r.lo.x, B, r.lo.h, r.lo.w, r.lo.c, 1, 1, 0);
+      lo.fpn_gemm = (m->fpn_gemm >> f) & 1;
+      io(lo, r.lo.slot, -1, -1);
+      SFA_RC(launch_conv(lo, EPI_STD, math_sf, fs));
     }
-    a.hout = lout[f];
-    return a;
-  };
-  auto probing = [&](hipStream_t hs) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    return (m->probe & SFA_PROBE_HEADS) && hipStreamIsCapturing(hs, &cap) == hipSuccess &&
-           cap == hipStreamCaptureStatusNone;
-  };
-  auto launch_head = [&](int f, hipStream_t hs) -> int {
-    const bool probe = probing(hs);
-    if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[2 * f], hs));
-    SFA_RC(launch_conv(head_args(f), EPI_HEAD, m->math, hs));
-    if (probe) SFA_HIP_TRY(hipEventRecord(m->probe_ev[2 * f + 1], hs));
-    return SFA_OK;
-  };
-  // (m->side is read under fork_mu below, as the overlap decision)
-  // level 0 needs only up_level2: fork it onto the side stream (graph capture follows
-  // the event edges), join before apply_kfpn
-  // m->side is read under fork_mu: sfa_model_set_side_streams destroys it under the same lock,
-  // so a concurrent call cannot pull a stream out from under this forward
-  std::unique_lock<std::mutex> fork_lock(const_cast<sfa_model*>(m)->fork_mu);
-  int sdev = -1;
-  const bool overlap = m->side && !(m->probe & SFA_PROBE_SERIAL) &&
-                       hipStreamGetDevice(st, &sdev) == hipSuccess && sdev == m->device;
-  if (overlap) {
-    SFA_HIP_TRY(hipEventRecord(m->fork, st));
-    SFA_HIP_TRY(hipStreamWaitEvent(m->side, m->fork, 0));
-  }
-  // Everything between the fork and the join: any failure inside returns from this lambda
-  // only, so the side stream is still joined below (a graph capture stays valid, no work is
-  // left orphaned on the side stream).
-  auto forked = [&]() -> int {
-  SFA_RC(launch_head(0, overlap ? m->side : st));
-  if (commute_at(1)) {
-    SFA_RC(fpn_pair(1, F(bf.c1), H16, W16, 256, AM_FPN + 0, F(bf.l[1]), 128, blk_slot(1, 1, 1), F(bf.c2),
-                    AM_FPN + 1, st));
-  } else
-  {
-    ConvArgs a = conv_args(wb, p.fpn[1], B, H8, W8, F(bf.c2), nullptr, 0);
-    a.nseg = 2;
-    a.kseg1 = 256;
-    a.seg[0] = seg(F(bf.up2), B, H8, W8, 256, 1, 1, 0);
-    a.seg[1] = seg(F(bf.l[1]), B, H8, W8, 128, 1, 1, 0);
-    io(a, AM_FPN + 0, blk_slot(1, 1, 1), AM_FPN + 1);
-    SFA_RC(launch_conv(a, EPI_STD, math_sf, st));
-  }
-  SFA_RC(launch_upsample2x(F(bf.c2), F(bf.up3), B, H8, W8, 128, st));
-  // FPN level 3 (-> up_level4) on stream fs
-  auto fpn3 = [&](hipStream_t fs) -> int {
-    if (commute_at(2))
-      return fpn_pair(2, F(bf.c2), H8, W8, 128, AM_FPN + 1, F(bf.l[0]), 64, blk_slot(0, 1, 1), F(bf.up4),
-                      AM_FPN + 2, fs);
-    ConvArgs a = conv_args(wb, p.fpn[2], B, H4, W4, F(bf.up4), nullptr, 0);
-    a.nseg = 2;
-    a.kseg1 = 128;
-    a.seg[0] = seg(F(bf.up3), B, H4, W4, 128, 1, 1, 0);
-    a.seg[1] = seg(F(bf.l[0]), B, H4, W4, 64, 1, 1, 0);
-    io(a, AM_FPN + 1, blk_slot(0, 1, 1), AM_FPN + 2);
+    a.Kpad = r.skip.c;
+    a.wstride = pc.Kpad;
+    a.wk0 = r.lo.c;
+    a.seg[0] = seg(r.skip.x, B, r.skip.h, r.skip.w, r.skip.c, 1, 1, 0);
+    a.res_up = r.lo_out;
+    a.res_sh = r.lo.h > 1 ? (float)(r.lo.h - 1) / (float)(2 * r.lo.h - 1) : 0.f;
+    a.res_sw = r.lo.w > 1 ? (float)(r.lo.w - 1) / (float)(2 * r.lo.w - 1) : 0.f;
+    a.fpn_gemm = (m->fpn_gemm >> (3 + f)) & 1;
+    io(a, r.skip.slot, -1, r.out_slot);
     return launch_conv(a, EPI_STD, math_sf, fs);
-  };
-  SFA_RC(fpn3(st));
-  // level 2 (needs up_level4, just written) on the side stream after level 0, level 1 here:
-  // the two 1,444-tile launches run side by side, so neither one's last partial wave of tiles
-  // leaves CUs idle
-  if (overlap) {
-    SFA_HIP_TRY(hipEventRecord(m->mid, st));
-    SFA_HIP_TRY(hipStreamWaitEvent(m->side, m->mid, 0));
-    SFA_RC(launch_head(2, m->side));
   }
-  SFA_RC(launch_head(1, st));
-  if (!overlap) SFA_RC(launch_head(2, st));
-  return SFA_OK;
-  };
-  const int frc = forked();
-  if (overlap) {  // the join, on success and on failure alike
-    SFA_HIP_TRY(hipEventRecord(m->join, m->side));
-    SFA_HIP_TRY(hipStreamWaitEvent(st, m->join, 0));
+
+  // The heads of KFPN level f on stream hs; probe pair f.
+  int launch_heads(int f, const KfpnOut& ko, hipStream_t hs) const {
+    const Map in[3] = {{F(bf.up2), H / 8, W / 8, kFpnC[0], AM_FPN + 0},  // up_level2 / 3 / 4, from
+                       {F(bf.up3), H / 4, W / 4, kFpnC[1], AM_FPN + 1},  // conv_up_level1 / 2 / 3
+                       {F(bf.up4), H / 4, W / 4, kFpnC[2], AM_FPN + 2}};
+    float* out[3] = {F(bf.L0), F(bf.L1), F(bf.L2)};
+    const ConvArgs a = head_args(in[f], p.heads[f], ko, out[f]);
+    return probed(f, hs, [&] { return launch_conv(a, EPI_HEAD, m->math, hs); });
   }
-  SFA_RC(frc);
-  // apply_kfpn (fpn_resnet.py:248-254)
-  KfpnOut ko;
-  memset(&ko, 0, sizeof ko);
-  for (int j = 0; j < m->arch.num_heads; ++j) {
-    ko.ptr[j] = head_out[j];
-    ko.ch[j] = m->arch.head_channels[j];
-    ko.off[j] = hoff[j];
+
+  // What runs between the fork and the join, with up_level2 written. The level-0 heads need only that, so
+  // they go to the side stream; level 2 (needs up_level4) follows them there and level 1 runs here: the
+  // two 1,444-tile launches run side by side, so neither one's last partial wave of tiles leaves CUs idle.
+  // Without a side stream: heads 0, FPN, heads 1, heads 2 on the caller's stream.
+  int forked_section(const KfpnOut& ko, hipStream_t side) const {
+    SFA_RC(launch_heads(0, ko, side ? side : st));
+    SFA_RC(fpn_level(1, st));
+    SFA_RC(launch_upsample2x(F(bf.c2), F(bf.up3), B, H / 8, W / 8, 128, st));
+    SFA_RC(fpn_level(2, st));
+    if (side) {
+      SFA_HIP_TRY(hipEventRecord(m->mid, st));
+      SFA_HIP_TRY(hipStreamWaitEvent(side, m->mid, 0));
+      SFA_RC(launch_heads(2, ko, side));
+    }
+    SFA_RC(launch_heads(1, ko, st));
+    if (!side) SFA_RC(launch_heads(2, ko, st));
+    return SFA_OK;
   }
-  ko.num_heads = m->arch.num_heads;
-  ko.total_ch = nch;
-  SFA_RC(launch_kfpn(F(bf.L0), F(bf.L1), F(bf.L2), ko, B, H4, W4, st));
-  return SFA_OK;
+
+  // Fork the side stream off the caller's, run forked_section, join. Two invariants, both carried by this
+  // function's shape:
+  //  * fork_mu is taken before m->side is read and held until after the join: sfa_model_set_side_streams
+  //    destroys the stream under the same lock, so a concurrent call cannot pull it out from under this
+  //    forward, and one forward's fork ... join is not interleaved with another's;
+  //  * the join runs whatever forked_section returns: a failure inside leaves a graph capture valid (it
+  //    follows the event edges) and no work orphaned on the side stream.
+  int fork_join_heads(const KfpnOut& ko) const {
+    std::lock_guard<std::mutex> fork_lock(const_cast<sfa_model*>(m)->fork_mu);
+    int sdev = -1;
+    const bool overlap = m->side && !(m->probe & SFA_PROBE_SERIAL) && hipStreamGetDevice(st, &sdev) == hipSuccess &&
+                         sdev == m->device;
+    if (overlap) {
+      SFA_HIP_TRY(hipEventRecord(m->fork, st));
+      SFA_HIP_TRY(hipStreamWaitEvent(m->side, m->fork, 0));
+    }
+    const int rc = forked_section(ko, overlap ? m->side : nullptr);
+    if (overlap) {
+      SFA_HIP_TRY(hipEventRecord(m->join, m->side));
+      SFA_HIP_TRY(hipStreamWaitEvent(st, m->join, 0));
+    }
+    return rc;
+  }
+
+  // KFPN: FPN level 0 and its upsample, the three head levels around FPN levels 1 and 2, apply_kfpn
+  // (fpn_resnet.py:248-254).
+  int kfpn_tail(float* const* head_out) const {
+    const KfpnOut ko = head_layout(head_out);
+    SFA_RC(fpn_level(0, st));
+    SFA_RC(launch_upsample2x(F(bf.c1), F(bf.up2), B, H / 16, W / 16, 256, st));
+    SFA_RC(fork_join_heads(ko));
+    return launch_kfpn(F(bf.L0), F(bf.L1), F(bf.L2), ko, B, H / 4, W / 4, st);
+  }
+};
+
+}  // namespace sfa
+
+// One pass over B <= forward_max_batch(H, W) frames (arguments checked by sfa_model_forward).
+static int forward_pass(const sfa_model* m, const float* x, int in_layout, int B, int H, int W,
+                        float* const* head_out, void* workspace, void* stream) {
+  const Pass c(m, B, H, W, workspace, stream);
+  if (c.h3)  // the amax words and the split-K tickets after them
+    SFA_RC(launch_zero_words(c.ws + c.bf.amax, c.bf.tick + 4 * c.bf.tick_words * 4 - c.bf.amax, c.st));
+  SFA_RC(c.stem(x, in_layout));
+  SFA_RC(c.layers());
+  return m->backbone == SFA_BACKBONE_DECONV ? c.deconv_tail(head_out) : c.kfpn_tail(head_out);
 }
 
 extern "C" int sfa_model_forward(const sfa_model* m, const float* x, int in_layout, int B, int H,

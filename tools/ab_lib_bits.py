@@ -3,10 +3,13 @@
     SFA_HIP_LIB=<lib> [SFA_ABI_EXPECT=1] python tools/ab_lib_bits.py run out.npz
     python tools/ab_lib_bits.py compare a.npz b.npz
 
-`run` packs the synthetic weights, runs the fp16x3 forward (default options) at a few sizes that
-cover every kernel path of the bench (608 x 608 with 10 frames: r3 heads, strip convs, r3 body
-convs, FPN skip convs, split-K layer4, the patch stem) and saves every head map; `compare`
-asserts the two files are bit-identical."""
+`run` packs the synthetic weights and saves every head map of the forward under each configuration of
+CONFIGS below: every math mode, every kernel-choice option off, no side streams, the serial probe, the
+three input layouts and the resnet_18 family, at sizes with more than one tile per map at every level;
+and fp16x3 / fp16 with default options at 608 x 608 with 10 frames, which covers every kernel path of the
+bench (r3 heads, strip convs, r3 body convs, FPN skip convs, split-K layer4, the patch stem). A
+configuration that the library lacks (an older build) is reported and left out. `compare` asserts that
+the two files hold the same maps, bit-identical."""
 import os
 import sys
 
@@ -15,7 +18,29 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "lidar-image_object-detection_-fpn_resnet-yolov8_amd", "sfa"))
 
-CASES = [(2, 96, 96), (3, 160, 192), (10, 608, 608)]
+SMALL = [(2, 96, 96), (3, 160, 192)]  # multiples of 32 with more than one tile per map at every level
+BIG = (10, 608, 608)  # the big-M conv_r3 body tiles and the tile_rows >= 50000 branches
+# (tag, setup, cases): setup is a list of (what, argument), applied to a fresh engine through the
+# runtime's public setters. The default-option fp16x3 maps keep their bare keys.
+CONFIGS = [
+    ("", [], SMALL + [BIG]),
+    ("fp16/", [("math", "MATH_FP16")], SMALL + [BIG]),
+    ("bf16x6/", [("math", "MATH_BF16X6")], SMALL),
+    ("f32/", [("math", "MATH_F32")], SMALL),
+    ("stem_patch=0/", [("option", ("OPT_STEM_PATCH", 0))], SMALL),
+    ("fpn_commute=0/", [("option", ("OPT_FPN_COMMUTE", 0))], SMALL),
+    ("fpn_commute=5/", [("option", ("OPT_FPN_COMMUTE", 5))], SMALL),  # a commuted and a concat level in one pass
+    ("fpn_gemm=0/", [("option", ("OPT_FPN_GEMM", 0))], SMALL),
+    ("splitk_tickets=0/", [("option", ("OPT_SPLITK_TICKETS", 0))], SMALL),
+    ("side_streams=0/", [("side_streams", False)], SMALL[1:]),
+    ("probe_serial/", [("probe", ("PROBE_HEADS", "PROBE_SERIAL"))], SMALL[1:]),
+    ("nhwc4/", [("layout", "IN_NHWC4")], SMALL[:1]),
+    ("flip_hw/", [("layout", "IN_NCHW3_FLIP_HW")], SMALL[:1]),
+    ("stem_patch=0,nhwc4/", [("option", ("OPT_STEM_PATCH", 0)), ("layout", "IN_NHWC4")], SMALL[:1]),
+    ("stem_patch=0,flip_hw/", [("option", ("OPT_STEM_PATCH", 0)), ("layout", "IN_NCHW3_FLIP_HW")], SMALL[:1]),
+    ("resnet_18/", [("deconv", None)], SMALL),
+    ("resnet_18,probe/", [("deconv", None), ("probe", ("PROBE_HEADS",))], SMALL[:1]),
+]
 
 
 def run(out):
@@ -28,21 +53,59 @@ def run(out):
         print("not in", _lib.LIB_PATH, ":", name)
         del _lib._PROTOS[name]
     dev = torch.device("cuda", 0)
-    arch = _lib.make_arch(runtime.DEFAULT_HEADS)
-    sd = synthetic.synthetic_state_dict(_lib.state_layout(arch), 0)
-    eng = runtime.KfpnEngine(arch, runtime.pack_state_dict(sd, arch), dev, math=_lib.MATH_FP16X3)
+    inputs, packed = {}, {}
+
+    def bev(case):
+        if case not in inputs:
+            B, H, W = case
+            inputs[case] = torch.from_numpy(synthetic.synthetic_bev(B, H, W, seed=B + H)).to(dev)
+        return inputs[case]
+
+    def engine(setup):
+        """(engine, input layout, probe pairs to read) of one configuration."""
+        what = dict(setup)
+        backbone = _lib.BACKBONE_DECONV if "deconv" in what else None
+        if backbone not in packed:
+            arch = _lib.make_arch(runtime.DEFAULT_HEADS, backbone=backbone)
+            sd = synthetic.synthetic_state_dict(_lib.state_layout(arch), 0)
+            packed[backbone] = (arch, runtime.pack_state_dict(sd, arch))
+        eng = runtime.KfpnEngine(*packed[backbone], dev, math=getattr(_lib, what.get("math", "MATH_FP16X3")))
+        if "option" in what:
+            eng.set_option(getattr(_lib, what["option"][0]), what["option"][1])
+        if "side_streams" in what:
+            eng.set_side_streams(what["side_streams"])
+        if "probe" in what:
+            eng.set_probe(sum(getattr(_lib, f) for f in what["probe"]))
+        return eng, getattr(_lib, what.get("layout", "IN_NCHW3")), (4 if backbone else 3) if "probe" in what else 0
+
     res = {}
-    for B, H, W in CASES:
-        x = torch.from_numpy(synthetic.synthetic_bev(B, H, W, seed=B + H)).to(dev)
-        o = eng.forward(x)
-        for h, v in o.items():
-            res[f"{B}x{H}x{W}/{h}"] = v.cpu().numpy()
+    for tag, setup, cases in CONFIGS:
+        try:
+            eng, layout, pairs = engine(setup)
+        except (AttributeError, _lib.SfaNativeError) as e:
+            print("not in", _lib.LIB_PATH, ":", tag, setup, "--", e)
+            continue
+        for case in cases:
+            x = bev(case)
+            if layout == _lib.IN_NHWC4:
+                x4 = torch.zeros((x.shape[0], x.shape[2], x.shape[3], 4), dtype=torch.float32, device=dev)
+                x4[..., :3] = x.permute(0, 2, 3, 1)
+                x = x4
+            elif layout == _lib.IN_NCHW3_FLIP_HW:
+                x = torch.flip(x, [2, 3]).contiguous()
+            o = eng.forward(x, layout)
+            if pairs:  # every probe event of the forward was recorded
+                assert all(t > 0 for t in eng.probe_times(pairs)), tag
+            for h, v in o.items():
+                res["%s%dx%dx%d/%s" % ((tag,) + case + (h,))] = v.cpu().numpy()
     np.savez(out, **res)
     print("saved", out, len(res))
 
 
 def compare(a, b):
     A, Bz = np.load(a), np.load(b)
+    for k in sorted(set(A.files) ^ set(Bz.files)):
+        print("MISSING in", a if k not in A.files else b, ":", k)
     assert sorted(A.files) == sorted(Bz.files)
     bad = [k for k in A.files if not np.array_equal(A[k], Bz[k])]
     for k in bad:
