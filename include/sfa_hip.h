@@ -649,6 +649,35 @@ int sfa_compute_loss(const float* hm_cen, const float* cen_offset, const float* 
                      float* loss, double* sums, uint32_t* status, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* sfa_compute_loss_grad: the gradient of sfa_compute_loss's total (unit weights) with respect to the
+ * five head maps; what total_loss.backward() leaves at the heads (train.py:190-247).  Inputs and
+ * shape limits are sfa_compute_loss's.  Outputs: five DEVICE f32 NCHW maps of the inputs' shapes,
+ * every byte written by the call (a cell no slot points at gets 0.0; nothing needs zeroing).
+ * apply_sigmoid 1: g_hm_cen and g_cen_offset are taken with respect to the logits (the focal / L1
+ * derivative times s (1 - s) where 1e-4 <= s <= 1 - 1e-4, both ends included, 0 elsewhere, s being
+ * sfa_sigmoid_clamp_inplace's float32 sigmoid); 0: with respect to the clamped probabilities.
+ * With p the probability, k = -1 / num_pos (-1 when num_pos == 0), m the slot's mask, d = pred m - t m
+ * and S the mask sum (slots with an index inside the map):
+ *   hm_cen      gt == 1: k [(1-p)^2 / p - 2 (1-p) log p];  gt < 1: k (1-gt)^4 [2 p log(1-p) - p^2 / (1-p)]
+ *   cen_offset, direction   sign(d) m / (2 S + 1e-4) at the slot's cell, sign(0) = 0
+ *   z_coor, dim             sign(d) m (0.5 log((e^3 - 1) |d| + 1) if |d| < 1 else 1.5) / (c S + 1e-4), c = 1, 3
+ * Slots of one frame that share a cell add up, in slot order.  Evaluated in float64 from the float32
+ * operands, rounded to float32 once per element; no floating-point atomics: runs are bit-identical.
+ *   status  DEVICE uint32 [1], bit 0 as in sfa_compute_loss (the slot contributes nothing)
+ * workspace: DEVICE, 8-byte aligned, sfa_compute_loss_grad_workspace_size(B, C, H, W, M) bytes (0 for
+ * a shape out of range), SFA_E_WORKSPACE when smaller.  Three launches on the caller's stream, no
+ * allocation, no synchronisation: graph-capturable. */
+size_t sfa_compute_loss_grad_workspace_size(int batch, int num_classes, int height, int width,
+                                            int max_objects);
+int sfa_compute_loss_grad(const float* hm_cen, const float* cen_offset, const float* direction,
+                          const float* z_coor, const float* dim, const float* t_hm_cen,
+                          const float* t_cen_offset, const float* t_direction, const float* t_z_coor,
+                          const float* t_dim, const int64_t* indices_center, const uint8_t* obj_mask,
+                          int batch, int num_classes, int height, int width, int max_objects,
+                          int apply_sigmoid, float* g_hm_cen, float* g_cen_offset, float* g_direction,
+                          float* g_z_coor, float* g_dim, uint32_t* status, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

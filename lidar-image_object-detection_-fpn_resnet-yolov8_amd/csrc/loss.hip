@@ -1,7 +1,8 @@
 // Validation tier on device: the training targets of a batch of label lists
 // (data_process/kitti_dataset.py:157-244 build_targets with compute_radius, gaussian2D and
 // gen_hm_radius, kitti_data_utils.py:176-225) and the loss of the five head maps against them
-// (losses/losses.py:44-163 Compute_Loss).  Evaluation only: no gradient of anything is formed.
+// (losses/losses.py:44-163 Compute_Loss), and the gradient of that loss at the five head maps
+// (sfa_compute_loss_grad, at the end of the file).  Nothing is differentiated past the head maps.
 //
 // build_targets is a GATHER.  The reference draws the labels one after the other and an ignore
 // label ASSIGNS 0.9999 at its centre, so the map depends on the label order: a later ignore label
@@ -374,6 +375,211 @@ bool loss_plan(int B, int C, int H, int W, int M, LossPlan* p) {
   return true;
 }
 
+// ------------------------------------------------------------ loss gradient --
+// d total / d (the five head maps), unit weights.  Three launches: gt == 1 is counted per 4096-cell
+// chunk, one block folds the counts and the mask sum into the two scalars every gradient needs
+// (the focal scale and the object count), and a gather pass writes every cell of the five maps.
+// gather's backward is a scatter-add; here, as in build_targets_kernel, each thread owns cells and
+// walks the frame's slot rows in slot order from LDS, so duplicates add up in a fixed order, cells
+// no slot points at get 0.0, every output byte is written and there are no atomics.
+constexpr int kGradThreads = 256;
+constexpr int kGradPix = 4;                             // pixels per thread: one float4 per channel
+constexpr int kGradTile = kGradThreads * kGradPix;      // pixels of one frame per block
+constexpr size_t kGradScalarBytes = 256;                // workspace head: double {focal scale, mask sum}
+
+template <bool VEC>
+__global__ void __launch_bounds__(kFocalThreads)
+    grad_count_kernel(const float* __restrict__ gt, int64_t n, uint32_t* __restrict__ counts) {
+  __shared__ double lds[kFocalThreads / 64];
+  int c = 0;
+  const int64_t base = (int64_t)blockIdx.x * kFocalChunk;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int64_t i = base + ((int64_t)it * kFocalThreads + threadIdx.x) * 4;
+    if (i >= n) break;
+    if (VEC && i + 4 <= n) {
+      const float4 t = *reinterpret_cast<const float4*>(gt + i);
+      c += (t.x == 1.f) + (t.y == 1.f) + (t.z == 1.f) + (t.w == 1.f);
+    } else {
+      for (int j = 0; j < 4 && i + j < n; ++j) c += gt[i + j] == 1.f;
+    }
+  }
+  const double s = block_sum<kFocalThreads>((double)c, lds);  // integers: exact in any order
+  if (threadIdx.x == 0) counts[blockIdx.x] = (uint32_t)s;
+}
+
+// One block.  scal[0] = -1 / num_pos (-1 when num_pos == 0), scal[1] = the mask sum over the slots
+// whose index is inside the map, as sfa_compute_loss counts it.
+__global__ void __launch_bounds__(256)
+    grad_fold_kernel(const uint32_t* __restrict__ counts, int n_counts, const int64_t* __restrict__ ind,
+                     const uint8_t* __restrict__ mask, int rows, int64_t HW, double* __restrict__ scal,
+                     uint32_t* __restrict__ status) {
+  __shared__ double lds[4];
+  double npos = 0, msum = 0;
+  bool bad = false;
+  for (int i = threadIdx.x; i < n_counts; i += 256) npos += (double)counts[i];
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    const unsigned mk = mask[r];
+    if (mk == 0) continue;
+    const int64_t idx = ind[r];
+    if (idx < 0 || idx >= HW)
+      bad = true;
+    else
+      msum += (double)mk;
+  }
+  npos = block_sum<256>(npos, lds);
+  msum = block_sum<256>(msum, lds);
+  const unsigned any = __syncthreads_or(bad);
+  if (threadIdx.x != 0) return;
+  scal[0] = npos == 0 ? -1.0 : -1.0 / npos;
+  scal[1] = msum;
+  *status = any ? kStatusIndex : 0u;
+}
+
+// _sigmoid's backward (utils/torch_utils.py:44-45): sigmoid' = s (1 - s), and clamp passes the
+// gradient where min <= s <= max, both ends included.  s is sigmoid_clamp_f's float32 value.
+__device__ __forceinline__ double sigmoid_chain(float x) {
+  const float s = 1.0f / (1.0f + expf(-x));
+  const double sd = (double)s;
+  return (s >= 1e-4f && s <= 1.0f - 1e-4f) ? sd * (1 - sd) : 0.0;
+}
+
+// d hm_cen_loss / d pred of one cell (losses.py:44-69); k = -1 / num_pos
+__device__ __forceinline__ float focal_grad(float pred, float gt, int apply_sigmoid, double k) {
+  const double p = (double)(apply_sigmoid ? sigmoid_clamp_f(pred) : pred);
+  double g = 0;
+  if (gt == 1.f) {
+    const double q = 1 - p;
+    g = k * (q * q / p - 2 * q * log(p));
+  } else if (gt < 1.f) {
+    const double w = 1 - (double)gt, w2 = w * w;
+    g = k * (w2 * w2) * (2 * p * log1p(-p) - p * p / (1 - p));
+  }
+  if (apply_sigmoid) g *= sigmoid_chain(pred);
+  return (float)g;
+}
+
+__device__ __forceinline__ double sign_of(double d) { return d > 0 ? 1.0 : (d < 0 ? -1.0 : 0.0); }
+
+struct GradMaps {
+  float *hm, *off, *dir, *z, *dim;
+};
+
+// grid (ceil(HW / kGradTile), B).  Slot gradient columns: 0-1 cen_offset, 2-3 direction, 4 z_coor, 5-7 dim.
+template <bool VEC>
+__global__ void __launch_bounds__(kGradThreads)
+    loss_grad_kernel(const float* __restrict__ hm, const float* __restrict__ t_hm, LossMaps m, GradMaps g, int C,
+                     int M, int HW, int apply_sigmoid, double bb, const double* __restrict__ scal) {
+  __shared__ double s_g[8][kMaxObjects];
+  __shared__ int s_idx[kMaxObjects];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const double k = scal[0], msum = scal[1];
+  const double den1 = msum * 1 + 1e-4, den2 = msum * 2 + 1e-4, den3 = msum * 3 + 1e-4;
+
+  for (int s = tid; s < M; s += kGradThreads) {
+    const int64_t row = (int64_t)b * M + s;
+    const double mk = (double)m.mask[row];
+    const int64_t idx = m.ind[row];
+    const bool live = mk != 0 && idx >= 0 && idx < (int64_t)HW;
+    double v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = 0;
+    if (live) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const float pv = m.off[((size_t)b * 2 + c) * HW + idx];
+        const double p = (double)(apply_sigmoid ? sigmoid_clamp_f(pv) : pv);
+        double go = sign_of(p * mk - (double)m.t_off[row * 2 + c] * mk) * mk / den2;
+        if (apply_sigmoid) go *= sigmoid_chain(pv);
+        v[c] = go;
+        v[2 + c] =
+            sign_of((double)m.dir[((size_t)b * 2 + c) * HW + idx] * mk - (double)m.t_dir[row * 2 + c] * mk) * mk / den2;
+      }
+      {
+        const double d = (double)m.z[(size_t)b * HW + idx] * mk - (double)m.t_z[row] * mk, a = fabs(d);
+        v[4] = sign_of(d) * mk * (a < 1.0 ? 0.5 * log(bb * a + 1) : 1.5) / den1;
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double d = (double)m.dim[((size_t)b * 3 + c) * HW + idx] * mk - (double)m.t_dim[row * 3 + c] * mk;
+        const double a = fabs(d);
+        v[5 + c] = sign_of(d) * mk * (a < 1.0 ? 0.5 * log(bb * a + 1) : 1.5) / den3;
+      }
+    }
+    s_idx[s] = live ? (int)idx : -1;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) s_g[c][s] = v[c];
+  }
+  __syncthreads();
+
+  const int p0 = ((int)blockIdx.x * kGradThreads + tid) * kGradPix;
+  if (p0 >= HW) return;
+  const int np = HW - p0 < kGradPix ? HW - p0 : kGradPix;
+
+  // the focal gradient of this thread's pixels, class by class
+  for (int c = 0; c < C; ++c) {
+    const size_t o = ((size_t)b * C + c) * HW + p0;
+    if (VEC && np == kGradPix) {
+      const float4 p = *reinterpret_cast<const float4*>(hm + o);
+      const float4 t = *reinterpret_cast<const float4*>(t_hm + o);
+      float4 r;
+      r.x = focal_grad(p.x, t.x, apply_sigmoid, k);
+      r.y = focal_grad(p.y, t.y, apply_sigmoid, k);
+      r.z = focal_grad(p.z, t.z, apply_sigmoid, k);
+      r.w = focal_grad(p.w, t.w, apply_sigmoid, k);
+      *reinterpret_cast<float4*>(g.hm + o) = r;
+    } else {
+      for (int j = 0; j < np; ++j) g.hm[o + j] = focal_grad(hm[o + j], t_hm[o + j], apply_sigmoid, k);
+    }
+  }
+
+  // the regression heads: the slots of this frame that point at one of the pixels, in slot order
+  double acc[kGradPix][8];
+#pragma unroll
+  for (int j = 0; j < kGradPix; ++j)
+#pragma unroll
+    for (int c = 0; c < 8; ++c) acc[j][c] = 0;
+  for (int s = 0; s < M; ++s) {
+    const unsigned rel = (unsigned)(s_idx[s] - p0);
+    if (rel >= (unsigned)kGradPix) continue;
+#pragma unroll
+    for (int j = 0; j < kGradPix; ++j)
+      if (rel == (unsigned)j) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) acc[j][c] += s_g[c][s];
+      }
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    float* out = c < 2 ? g.off + ((size_t)b * 2 + c) * HW
+                       : c < 4 ? g.dir + ((size_t)b * 2 + (c - 2)) * HW
+                               : c < 5 ? g.z + (size_t)b * HW : g.dim + ((size_t)b * 3 + (c - 5)) * HW;
+    if (VEC && np == kGradPix) {
+      *reinterpret_cast<float4*>(out + p0) =
+          make_float4((float)acc[0][c], (float)acc[1][c], (float)acc[2][c], (float)acc[3][c]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < kGradPix; ++j)
+        if (j < np) out[p0 + j] = (float)acc[j][c];
+    }
+  }
+}
+
+struct GradPlan {
+  int64_t cells;
+  int n_counts;
+  size_t bytes;
+};
+
+bool grad_plan(int B, int C, int H, int W, int M, GradPlan* p) {
+  LossPlan lp;
+  if (!loss_plan(B, C, H, W, M, &lp)) return false;
+  p->cells = lp.cells;
+  p->n_counts = lp.n_focal;
+  p->bytes = kGradScalarBytes + align_up((size_t)p->n_counts * sizeof(uint32_t), 256);
+  return true;
+}
+
 }  // namespace
 
 }  // namespace sfa
@@ -466,6 +672,66 @@ extern "C" int sfa_compute_loss(const float* hm_cen, const float* cen_offset, co
                      (int64_t)height * width, apply_sigmoid ? 1 : 0, exp(1.5 / 0.5) - 1, rows);
   SFA_LAUNCH_CHECK();
   hipLaunchKernelGGL(loss_fold_kernel, dim3(1), dim3(256), 0, st, focal, p.n_focal, rows, p.n_rows, loss, sums, status);
+  SFA_LAUNCH_CHECK();
+  return SFA_OK;
+}
+
+extern "C" size_t sfa_compute_loss_grad_workspace_size(int batch, int num_classes, int height, int width,
+                                                       int max_objects) {
+  GradPlan p;
+  return grad_plan(batch, num_classes, height, width, max_objects, &p) ? p.bytes : 0;
+}
+
+extern "C" int sfa_compute_loss_grad(const float* hm_cen, const float* cen_offset, const float* direction,
+                                     const float* z_coor, const float* dim, const float* t_hm_cen,
+                                     const float* t_cen_offset, const float* t_direction, const float* t_z_coor,
+                                     const float* t_dim, const int64_t* indices_center, const uint8_t* obj_mask,
+                                     int batch, int num_classes, int height, int width, int max_objects,
+                                     int apply_sigmoid, float* g_hm_cen, float* g_cen_offset, float* g_direction,
+                                     float* g_z_coor, float* g_dim, uint32_t* status, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  GradPlan p;
+  SFA_CHECK_ARG(grad_plan(batch, num_classes, height, width, max_objects, &p),
+                "compute_loss_grad: batch %d (1..64), classes %d (1..%d), map %d x %d, max_objects %d (1..%d)", batch,
+                num_classes, kMaxClasses, height, width, max_objects, kMaxObjects);
+  SFA_CHECK_ARG(hm_cen && cen_offset && direction && z_coor && dim && t_hm_cen && t_cen_offset && t_direction &&
+                    t_z_coor && t_dim && indices_center && obj_mask && g_hm_cen && g_cen_offset && g_direction &&
+                    g_z_coor && g_dim && status && workspace,
+                "compute_loss_grad: null buffer");
+  SFA_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "compute_loss_grad: workspace not 8-byte aligned");
+  if (workspace_bytes < p.bytes) {
+    set_error("compute_loss_grad: workspace %zu < %zu bytes", workspace_bytes, p.bytes);
+    return SFA_E_WORKSPACE;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  double* scal = reinterpret_cast<double*>(workspace);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + kGradScalarBytes);
+  const int HW = height * width;
+  if (reinterpret_cast<uintptr_t>(t_hm_cen) % 16 == 0)
+    hipLaunchKernelGGL(grad_count_kernel<true>, dim3(p.n_counts), dim3(kFocalThreads), 0, st, t_hm_cen, p.cells,
+                       counts);
+  else
+    hipLaunchKernelGGL(grad_count_kernel<false>, dim3(p.n_counts), dim3(kFocalThreads), 0, st, t_hm_cen, p.cells,
+                       counts);
+  SFA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_fold_kernel, dim3(1), dim3(256), 0, st, counts, p.n_counts, indices_center, obj_mask,
+                     batch * max_objects, (int64_t)HW, scal, status);
+  SFA_LAUNCH_CHECK();
+  LossMaps m{cen_offset, direction, z_coor, dim, t_cen_offset, t_direction, t_z_coor, t_dim, indices_center, obj_mask};
+  GradMaps g{g_hm_cen, g_cen_offset, g_direction, g_z_coor, g_dim};
+  // 128-bit loads and stores need every channel plane 16-byte aligned: the bases and H*W % 4 == 0
+  const uintptr_t bases = reinterpret_cast<uintptr_t>(hm_cen) | reinterpret_cast<uintptr_t>(t_hm_cen) |
+                          reinterpret_cast<uintptr_t>(g_hm_cen) | reinterpret_cast<uintptr_t>(g_cen_offset) |
+                          reinterpret_cast<uintptr_t>(g_direction) | reinterpret_cast<uintptr_t>(g_z_coor) |
+                          reinterpret_cast<uintptr_t>(g_dim);
+  const dim3 grid((unsigned)((HW + kGradTile - 1) / kGradTile), (unsigned)batch);
+  const double bb = exp(1.5 / 0.5) - 1;
+  if (bases % 16 == 0 && HW % 4 == 0)
+    hipLaunchKernelGGL(loss_grad_kernel<true>, grid, dim3(kGradThreads), 0, st, hm_cen, t_hm_cen, m, g, num_classes,
+                       max_objects, HW, apply_sigmoid ? 1 : 0, bb, scal);
+  else
+    hipLaunchKernelGGL(loss_grad_kernel<false>, grid, dim3(kGradThreads), 0, st, hm_cen, t_hm_cen, m, g, num_classes,
+                       max_objects, HW, apply_sigmoid ? 1 : 0, bb, scal);
   SFA_LAUNCH_CHECK();
   return SFA_OK;
 }

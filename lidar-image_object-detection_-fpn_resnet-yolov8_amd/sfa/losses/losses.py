@@ -1,11 +1,14 @@
-"""Drop-in for the reference's losses/losses.py (:44-163), evaluation only.
+"""Drop-in for the reference's losses/losses.py (:44-163): evaluation, and on request the gradient at
+the five head maps.
 
 ``Compute_Loss(device).forward(outputs, tg)`` returns ``(total_loss, loss_stats)`` like the
 reference — a 0-dim GPU tensor and the six-key dict — and leaves ``outputs['hm_cen']`` and
 ``outputs['cen_offset']`` holding the clamped sigmoid (:140-141).  Every term is evaluated by the HIP
 library (sfa_compute_loss: float64 terms from the float32 operands, float64 sums in a fixed order,
-rounded to float32 once); nothing here is differentiable: a tensor with ``requires_grad`` raises
-NotImplementedError, CPU tensors are refused like in the rest of the drop-in.
+rounded to float32 once).  By default nothing here is differentiable: a tensor with ``requires_grad``
+raises NotImplementedError, CPU tensors are refused like in the rest of the drop-in.
+``Compute_Loss(device, differentiable=True)`` makes ``total_loss.backward()`` work for the five logit
+maps (sfa_compute_loss_grad); see the class.
 
 ``FocalLoss``, ``L1Loss``, ``L1Loss_Balanced`` and ``_neg_loss`` keep the reference's names and
 signatures; each runs the same kernels with the other terms' inputs absent and returns its own
@@ -112,10 +115,44 @@ class L1Loss_Balanced(nn.Module):
         return _masked(output, mask, ind, target, "z_coor" if one else "dim", 5 if one else 3)
 
 
+class _LossAtHeads(torch.autograd.Function):
+    """total_loss of the five logit maps with its gradient at those maps, both from the HIP library.
+    forward evaluates the loss on the raw logits (apply_sigmoid = 1) and, when a map requires grad,
+    sfa_compute_loss_grad; the five gradient maps are what is saved (never the logits, which the caller
+    may overwrite).  backward scales them by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, evaluator, tg, *logits):
+        outs = dict(zip(_rt.DEFAULT_HEADS, logits))
+        stats = evaluator(outs, tg, apply_sigmoid=True).clone()
+        ctx.have = any(ctx.needs_input_grad[2:])
+        if ctx.have:
+            grads = evaluator.grad(outs, tg, apply_sigmoid=True)
+            ctx.save_for_backward(*(grads[k] for k in _rt.DEFAULT_HEADS))
+        ctx.mark_non_differentiable(stats)
+        return stats[0].clone(), stats
+
+    @staticmethod
+    def backward(ctx, upstream, _stats):
+        if not ctx.have:
+            return (None,) * 7
+        return (None, None) + tuple(g * upstream if need else None
+                                    for g, need in zip(ctx.saved_tensors, ctx.needs_input_grad[2:]))
+
+
 class Compute_Loss(nn.Module):
-    def __init__(self, device):
+    """The reference's Compute_Loss (:128-163).  ``differentiable=False`` (the default) is evaluation
+    only.  With ``differentiable=True`` ``total_loss`` carries a grad_fn and ``total_loss.backward()``
+    leaves d total / d logits at the five head maps (sfa_compute_loss_grad; unit weights only); nothing
+    behind the head maps is part of this module.  Departure from :140-141 in that mode:
+    ``outputs['hm_cen']`` and ``outputs['cen_offset']`` still hold the clamped sigmoid afterwards, but as
+    new, detached tensors (the logits are left untouched for autograd), so a later use of those two
+    entries does not back-propagate."""
+
+    def __init__(self, device, differentiable=False):
         super().__init__()
         self.device = device
+        self.differentiable = bool(differentiable)
         self.focal_loss = FocalLoss()
         self.l1_loss = L1Loss()
         self.l1_loss_balanced = L1Loss_Balanced(alpha=0.5, gamma=1.5, beta=1.0)
@@ -123,12 +160,22 @@ class Compute_Loss(nn.Module):
         self.weight_z_coor, self.weight_cenoff, self.weight_dim, self.weight_direction = 1., 1., 1., 1.
 
     def forward(self, outputs, tg):
-        _no_grad(*outputs.values(), *tg.values())
+        if self.differentiable:
+            _no_grad(*tg.values())
+        else:
+            _no_grad(*outputs.values(), *tg.values())
         for k in _rt.DEFAULT_HEADS:
             _gpu(outputs[k], f"Compute_Loss outputs[{k!r}]")
         weights = (self.weight_hm_cen, self.weight_cenoff, self.weight_dim, self.weight_direction, self.weight_z_coor)
         if any(w != 1. for w in weights):
             raise NotImplementedError("Compute_Loss: the kernel sums the terms with the reference's unit weights")
+        if self.differentiable:
+            logits = [outputs[k] for k in _rt.DEFAULT_HEADS]
+            total, loss = _LossAtHeads.apply(_evaluator(logits[0].device), tg, *logits)
+            for k in ('hm_cen', 'cen_offset'):
+                outputs[k] = _sigmoid(outputs[k].detach().clone(memory_format=torch.contiguous_format))
+            host = to_cpu(loss).tolist()
+            return total, dict(zip(_rt.LOSS_KEYS, host))
         outputs['hm_cen'] = _sigmoid(outputs['hm_cen'])
         outputs['cen_offset'] = _sigmoid(outputs['cen_offset'])
         loss = _evaluator(outputs['hm_cen'].device)(outputs, tg).clone()

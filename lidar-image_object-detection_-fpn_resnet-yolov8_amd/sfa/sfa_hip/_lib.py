@@ -220,6 +220,8 @@ _PROTOS["sfa_build_targets"] = (_c_int, [_vp, _vp, _c_i64, _c_int, ctypes.POINTE
                                          _vp, _vp, _vp, _vp, _vp, _vp])
 _PROTOS["sfa_compute_loss_workspace_size"] = (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int])
 _PROTOS["sfa_compute_loss"] = (_c_int, [_vp] * 12 + [_c_int] * 6 + [_vp, _vp, _vp, _vp, _c_size, _vp])
+_PROTOS["sfa_compute_loss_grad_workspace_size"] = (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int])
+_PROTOS["sfa_compute_loss_grad"] = (_c_int, [_vp] * 12 + [_c_int] * 6 + [_vp] * 5 + [_vp, _vp, _c_size, _vp])
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
 _lib = None

@@ -1267,20 +1267,22 @@ class LossEvaluator:
     [total, hm_cen, cen_offset, dim, direction, z_coor] (LOSS_KEYS order); ``sums`` holds the float64
     pieces, ``status`` the bad-index word.  ``verify`` (default) reads the status word back and raises
     IndexError as the reference's gather does; with ``verify=False`` the call only enqueues its three
-    launches and can be captured into a HIP graph."""
+    launches and can be captured into a HIP graph.  :meth:`grad` gives the gradient of the total at the
+    five head maps."""
 
     def __init__(self, device):
         self.dev = torch.device(device)
         self.loss = torch.empty(6, dtype=torch.float32, device=self.dev)
         self.sums = torch.empty(8, dtype=torch.float64, device=self.dev)
         self.status = torch.empty(1, dtype=torch.int32, device=self.dev)
+        self.grad_status = torch.empty(1, dtype=torch.int32, device=self.dev)
         self._ws = {}
 
     @staticmethod
     def workspace_bytes(B, C, H, W, M) -> int:
         return int(lib().sfa_compute_loss_workspace_size(B, C, H, W, M))
 
-    def __call__(self, outputs: dict, targets: dict, apply_sigmoid: bool = False, verify: bool = True):
+    def _operands(self, outputs: dict, targets: dict):
         heads = [_require_gpu_tensor(outputs[k], f"Compute_Loss outputs[{k!r}]") for k in DEFAULT_HEADS]
         tg = [_require_gpu_tensor(targets[k], f"Compute_Loss targets[{k!r}]") for k in TARGET_KEYS[:5]]
         ind = _require_gpu_tensor(targets["indices_center"], "Compute_Loss indices_center", torch.int64)
@@ -1300,13 +1302,23 @@ class LossEvaluator:
         for t, s in zip(tg + [ind, msk], ((B, C, H, W), (B, M, 2), (B, M, 2), (B, M, 1), (B, M, 3), (B, M), (B, M))):
             if tuple(t.shape) != s:
                 raise ValueError(f"Compute_Loss: target shape {tuple(t.shape)} != {s}")
-        need = self.workspace_bytes(B, C, H, W, M)
+        return heads, tg, ind, msk, (B, C, H, W, M)
+
+    def _workspace(self, tag: str, need: int, shape):
         if need == 0:
+            B, C, H, W, M = shape
             raise ValueError(f"Compute_Loss: shape B={B}, C={C}, H={H}, W={W}, M={M} outside the kernels' range")
         sp = _lib.stream_ptr(self.dev)
-        ws = self._ws.get((sp, need))
+        ws = self._ws.get((tag, sp, need))
         if ws is None:
-            ws = self._ws[(sp, need)] = torch.empty(need // 8, dtype=torch.float64, device=self.dev)
+            ws = self._ws[(tag, sp, need)] = torch.empty(need // 8, dtype=torch.float64, device=self.dev)
+        return ws, sp
+
+    def __call__(self, outputs: dict, targets: dict, apply_sigmoid: bool = False, verify: bool = True):
+        heads, tg, ind, msk, shape = self._operands(outputs, targets)
+        B, C, H, W, M = shape
+        need = self.workspace_bytes(B, C, H, W, M)
+        ws, sp = self._workspace("loss", need, shape)
         check_rc = lib().sfa_compute_loss(*(t.data_ptr() for t in heads), *(t.data_ptr() for t in tg), ind.data_ptr(),
                                           msk.data_ptr(), B, C, H, W, M, 1 if apply_sigmoid else 0,
                                           self.loss.data_ptr(), self.sums.data_ptr(), self.status.data_ptr(),
@@ -1315,3 +1327,35 @@ class LossEvaluator:
         if verify and int(self.status.item()) & _lib.STATUS_INDEX_OUT_OF_MAP:
             raise IndexError(f"Compute_Loss: an indices_center entry under a set obj_mask is outside [0, {H * W})")
         return self.loss
+
+    @staticmethod
+    def grad_workspace_bytes(B, C, H, W, M) -> int:
+        return int(lib().sfa_compute_loss_grad_workspace_size(B, C, H, W, M))
+
+    def grad(self, outputs: dict, targets: dict, apply_sigmoid: bool = False, verify: bool = True,
+             out: dict = None) -> dict:
+        """d total_loss / d (the five head maps) (sfa_compute_loss_grad): a dict of float32 GPU tensors of
+        the heads' shapes under the heads' keys, every element written by the call.  With
+        ``apply_sigmoid`` hm_cen and cen_offset are logits and their gradients are taken with respect to
+        the logits, otherwise with respect to the clamped probabilities.  ``out`` (a dict of contiguous
+        tensors) receives the maps instead of fresh tensors; with it and ``verify=False`` the call only
+        enqueues its three launches and can be captured into a HIP graph.  ``grad_status`` holds the
+        bad-index word; ``verify`` reads it back and raises IndexError like ``__call__``."""
+        heads, tg, ind, msk, shape = self._operands(outputs, targets)
+        B, C, H, W, M = shape
+        need = self.grad_workspace_bytes(B, C, H, W, M)
+        ws, sp = self._workspace("grad", need, shape)
+        if out is None:
+            out = {k: torch.empty_like(t) for k, t in zip(DEFAULT_HEADS, heads)}
+        grads = [_require_gpu_tensor(out[k], f"Compute_Loss grad out[{k!r}]") for k in DEFAULT_HEADS]
+        for k, t, h in zip(DEFAULT_HEADS, grads, heads):
+            if t.shape != h.shape or t.data_ptr() != out[k].data_ptr():
+                raise ValueError(f"Compute_Loss grad out[{k!r}]: a contiguous tensor of shape {tuple(h.shape)} is needed")
+        check_rc = lib().sfa_compute_loss_grad(*(t.data_ptr() for t in heads), *(t.data_ptr() for t in tg),
+                                               ind.data_ptr(), msk.data_ptr(), B, C, H, W, M,
+                                               1 if apply_sigmoid else 0, *(t.data_ptr() for t in grads),
+                                               self.grad_status.data_ptr(), ws.data_ptr(), need, sp)
+        check(check_rc, "sfa_compute_loss_grad")
+        if verify and int(self.grad_status.item()) & _lib.STATUS_INDEX_OUT_OF_MAP:
+            raise IndexError(f"Compute_Loss: an indices_center entry under a set obj_mask is outside [0, {H * W})")
+        return dict(zip(DEFAULT_HEADS, grads))

@@ -7,8 +7,9 @@ total_loss over the frames, one JSON line.
   tools/validate.py --dataset_dir D --pretrained_path P   KITTI val split through create_val_dataloader
   --math fp16      also runs SFA_MATH_FP16 on the same frames and reports its loss next to fp16x3's
   --timing         median microseconds of target build + loss for 16 frames on a captured HIP graph
+  --timing --grad  also targets + loss + gradient (sfa_compute_loss_grad) on one graph, then bench.py
 
-Evaluation only: there is no backward pass.  With a data set, the labels of a batch are read with the
+The loop is evaluation only (the gradient at the heads is only timed).  With a data set, the labels of a batch are read with the
 data set's own helpers (get_label, camera_to_lidar_box, filter_labels: a reference tree on sys.path or in
 SFA_REFERENCE_ROOT serves get_label), the maps come from the drop-in loader.
 """
@@ -123,8 +124,9 @@ def evaluate(model, batches, args, device):
     return losses.avg, {k: v / max(frames, 1) for k, v in parts.items()}, frames
 
 
-def timing(device, args, frames=16, reps=50):
-    """Median microseconds of sfa_build_targets + sfa_compute_loss for ``frames`` frames, one HIP graph."""
+def timing(device, args, frames=16, reps=50, grad=False):
+    """Median microseconds of sfa_build_targets + sfa_compute_loss (with ``grad`` also sfa_compute_loss_grad)
+    for ``frames`` frames, one HIP graph."""
     hm = args.input_size // 4
     labels, offsets = synthetic.synthetic_labels(frames, seed=args.seed)
     builder = runtime.TargetBuilder(device, runtime.DEFAULT_BOUNDARY, (hm, hm), 3, args.max_objects)
@@ -134,10 +136,13 @@ def timing(device, args, frames=16, reps=50):
     outs = {h: torch.from_numpy(synthetic.synthetic_logits((frames, c, hm, hm), args.seed, 60 + i)).to(device)
             for i, (h, c) in enumerate(runtime.DEFAULT_HEADS.items())}
     tg = builder.alloc(frames)
+    grads = {h: torch.empty_like(t) for h, t in outs.items()}
 
     def step():
         builder(d_labels, d_offsets, None, out=tg, verify=False)
         ev(outs, tg, apply_sigmoid=True, verify=False)
+        if grad:
+            ev.grad(outs, tg, apply_sigmoid=True, verify=False, out=grads)
 
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -161,6 +166,17 @@ def timing(device, args, frames=16, reps=50):
     return {"frames": frames, "reps": reps, "median_us": float(np.median(times)), "min_us": float(np.min(times))}
 
 
+def run_bench():
+    """``python bench.py`` in a child process, after this one's GPU work: its JSON line (the inference path)."""
+    import subprocess
+    torch.cuda.synchronize()
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")], capture_output=True, text=True, cwd=REPO)
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    if out.returncode != 0 or not lines:
+        return {"error": f"bench.py exited with {out.returncode}", "stderr": out.stderr[-500:]}
+    return json.loads(lines[-1])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--arch", default="fpn_resnet_18", choices=["fpn_resnet_18", "resnet_18"])
@@ -174,6 +190,8 @@ def main(argv=None):
     ap.add_argument("--max_objects", type=int, default=50)
     ap.add_argument("--math", default=None, choices=["fp16"], help="also report the loss under SFA_MATH_FP16")
     ap.add_argument("--timing", action="store_true")
+    ap.add_argument("--grad", action="store_true",
+                    help="with --timing: also time targets + loss + gradient on one graph, then run bench.py")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gpu_idx", type=int, default=0)
     args = ap.parse_args(argv)
@@ -194,6 +212,9 @@ def main(argv=None):
         result["fp16"] = {"val_loss": avg16, "loss_stats": parts16, "delta_vs_fp16x3": avg16 - avg}
     if args.timing:
         result["targets_plus_loss_graph"] = timing(device, args)
+        if args.grad:
+            result["targets_plus_loss_plus_grad_graph"] = timing(device, args, grad=True)
+            result["bench"] = run_bench()
     print(json.dumps(result))
     return result
 
