@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "conv.h"
+#include "dispatch.h"
 
 namespace sfa {
 
@@ -207,14 +208,10 @@ int launch_nchw3_to_nhwc4(const float* x, float* y, int B, int H, int W, bool fl
     set_error("nchw3_to_nhwc4: batch %d too large", B);
     return SFA_E_INVALID;
   }
-  if (flip)
-    hipLaunchKernelGGL(nchw3_to_nhwc4_kernel<true>, frame_grid(B, (long long)H * W), dim3(256), 0, st,
-                       x, reinterpret_cast<float4*>(y), H * W, amax);
-  else
-    hipLaunchKernelGGL(nchw3_to_nhwc4_kernel<false>, frame_grid(B, (long long)H * W), dim3(256), 0,
-                       st, x, reinterpret_cast<float4*>(y), H * W, amax);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return with_bool(flip, [&](auto FLIP) {
+    return launch({frame_grid(B, (long long)H * W), dim3(256), st}, nchw3_to_nhwc4_kernel<FLIP.value>, x,
+                  reinterpret_cast<float4*>(y), H * W, amax);
+  });
 }
 
 int launch_amax_nhwc4(const float* x, int B, int H, int W, unsigned* amax, hipStream_t st) {

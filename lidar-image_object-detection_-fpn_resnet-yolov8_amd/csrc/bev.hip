@@ -3,32 +3,36 @@
 // Reference: data_process/kitti_data_utils.py:228-251 (filter),
 //            data_process/kitti_bev_utils.py:22-55 (makeBEVMap).
 //
-// Default: the binned path (count / scan / bin / strip kernels below): points binned by 8-row
-// strips of the map, each strip's top keys and counts reduced in LDS. For batches whose points
-// do not fit the scratch as records, and as SFA_BEV_ATOMIC=1, the global-atomic path:
-// two passes, HBM/atomic bound (SURVEY §8(a) row a1'):
-//   pass 1 (one thread per point): inclusive f32 box test, z' = z - minZ (f32),
-//     cell = (floor(x/D), trunc(floor(y/D) + 304.5)) with IEEE f32 division,
-//     atomicMax of a 64-bit key (bits(z') << 32 | ~index) — z' >= +0 so the
-//     float bits are monotone; the max key is the max z with ties broken by the
-//     FIRST point in input order, exactly the row np.unique(return_index) picks
-//     after the stable lexsort((-z, col, row)) — and atomicAdd of the count.
-//   pass 2 (one thread per BEV cell): intensity = i[top], height = z'/4.0 (f32),
-//     density = min(1, ln(count+1)/ln 64) (f64 table), written in the requested
-//     layout; the scratch cell is re-zeroed for the next call.
+// Three paths, tried in this order (bev_plan.h chooses one and places its scratch regions); all
+// give the same bits:
+//   blocked  the default: one pass over the points.  Each 1024-point block writes its records,
+//            grouped by 4-row strips (8-row with SFA_BEV_STRIP8), into its own region, and one block
+//            per (frame, strip) reduces them in LDS.  Taken when no frame has more regions than a
+//            strip block indexes (1024; 2048 with 8-row strips) and records + table fit the scratch.
+//   binned   with SFA_BEV_FORCE_BINNED, or when the blocked form does not fit: the count / scan /
+//            bin / strip kernels, points binned by 8-row strips through global reservations.  Taken
+//            when the batch's points fit the scratch as 16-B records.
+//   atomic   with SFA_BEV_FORCE_ATOMIC, or when neither fits: two passes, HBM/atomic bound
+//            (SURVEY §8(a) row a1'):
+//     pass 1 (one thread per point): inclusive f32 box test, z' = z - minZ (f32),
+//       cell = (floor(x/D), trunc(floor(y/D) + 304.5)) with IEEE f32 division,
+//       atomicMax of a 64-bit key (bits(z') << 32 | ~index) — z' >= +0 so the
+//       float bits are monotone; the max key is the max z with ties broken by the
+//       FIRST point in input order, exactly the row np.unique(return_index) picks
+//       after the stable lexsort((-z, col, row)) — and atomicAdd of the count.
+//     pass 2 (one thread per BEV cell): intensity = i[top], height = z'/4.0 (f32),
+//       density = min(1, ln(count+1)/ln 64) (f64 table), written in the requested
+//       layout; the scratch cell is re-zeroed for the next call.
 // The result is independent of atomic arrival order: bit-exact.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 #include "aux_kernels.h"
-#include "common.h"
+#include "bev_plan.h"
+#include "dispatch.h"
 
 namespace sfa {
-
-constexpr int kBevH = 608;
-constexpr int kBevW = 608;
-constexpr int kBevCells = kBevH * kBevW;
 
 struct BevArgs {
   int64_t start[SFA_BEV_MAX_BATCH + 1];
@@ -149,7 +153,7 @@ __global__ void __launch_bounds__(256) bev_gather_kernel(const float4* __restric
 }
 
 // ------------------------------------------------------------ binned path --
-// The default when the batch's points fit the scratch as records (any KITTI-sized sweep).
+// Round 2's default, now the second choice: when the batch's points fit the scratch as records.
 // The atomic path above does two device-scope atomics per kept point on a 12-B-per-cell
 // scratch spread over the whole map: each is an L2 miss on its own line (the scatter was
 // 58 us for 16 sweeps, the gather 38 us). Here the points are binned by 8-row strips of
@@ -164,9 +168,7 @@ __global__ void __launch_bounds__(256) bev_gather_kernel(const float4* __restric
 // atomic path. Self-cleaning like it: the strip pass zeroes its strip's counters. The records
 // have their own region after the atomic path's keys / counts (round 3: they used to overlap
 // them, so every record read was written back as zero — 16 B per point of extra traffic).
-constexpr int kStripRows = 8;
-constexpr int kStripCells = kStripRows * kBevW;   // 4,864
-constexpr int kStrips = kBevH / kStripRows;       // 76
+constexpr int kStripCells = kStripRows * kBevW;   // 4,864 (kStripRows = 8, kStrips = 76: bev_plan.h)
 constexpr int kStripThreads = 512;
 
 struct BinScratch {
@@ -317,16 +319,15 @@ __global__ void __launch_bounds__(kStripThreads) bev_strip_kernel(const float4* 
 // the region is the one the strip block found the record in, so the 64-bit key (z bits << 32 |
 // ~frame index) is rebuilt exactly (round 3a's 16-B records also carried the cell and the
 // intensity, which the strip pass takes from the top point).
-constexpr int kBlkPts = 1024;
-constexpr int kBlkThreads = 256;
+constexpr int kBlkThreads = 256;                // kBlkPts = 1024: bev_plan.h
 constexpr int kBlkPPT = kBlkPts / kBlkThreads;  // 4
 
 template <int SR>
 struct BlkGeom {
-  static constexpr int strips = kBevH / SR;         // 152 / 76
+  static constexpr int strips = blk_strips(SR);     // 152 / 76
   static constexpr int cells = SR * kBevW;          // 2,432 / 4,864
   static constexpr int threads = SR == 8 ? 512 : 256;
-  static constexpr int max_regions = SR == 8 ? 2048 : 1024;  // regions of one frame a strip block indexes
+  static constexpr int max_regions = blk_max_regions(SR);  // regions of one frame a strip block indexes
 };
 
 constexpr int kBlkCellBits = 13;  // cell within a strip (< 4,864)
@@ -506,28 +507,130 @@ __global__ void __launch_bounds__(BlkGeom<SR>::threads) bev_blk_strip_kernel(con
 
 using namespace sfa;
 
-// atomic path: keys + counts per cell; binned path: its counters + records (12 B per cell of
-// room: ~277 k points per frame) after them
-static size_t bev_atomic_bytes(int batch) {
-  return align_up((size_t)batch * kBevCells * sizeof(unsigned long long), 256) +
-         align_up((size_t)batch * kBevCells * sizeof(unsigned), 256);
+extern "C" size_t sfa_bev_scratch_size(int batch) { return bev_scratch_size(batch); }
+
+namespace {
+
+// What the launches of every path share.
+struct BevCall {
+  const float4* pts;
+  BevArgs a;
+  int batch, layout;
+  int64_t max_n;  // points of the largest frame
+  bool raw, flip;
+  void* out;
+  char* scratch;
+  hipStream_t st;
+  template <typename T>
+  T* at(const Region& r) const { return reinterpret_cast<T*>(scratch + r.off); }
+};
+
+// f(layout, flip) with both as compile-time values
+template <typename F>
+int with_layout_flip(const BevCall& c, F&& f) {
+  return with_bev_layout(c.layout, [&](auto L) { return with_bool(c.flip, [&](auto FLIP) { return f(L, FLIP); }); });
 }
 
-extern "C" size_t sfa_bev_scratch_size(int batch) {
-  if (batch <= 0) return 0;
-  return 2 * bev_atomic_bytes(batch);
+// The frames' starts, the largest frame and the f32 constants of the reference.
+int bev_fill_args(const float* points, const int64_t* frame_offsets, int batch, const double* boundary, BevArgs* a,
+                  int64_t* max_n) {
+  *max_n = 0;
+  for (int b = 0; b <= batch; ++b) {
+    a->start[b] = frame_offsets[b];
+    if (b > 0) {
+      const int64_t n = frame_offsets[b] - frame_offsets[b - 1];
+      SFA_CHECK_ARG(n >= 0, "bev: frame_offsets not monotone at %d", b);
+      SFA_CHECK_ARG(n < (int64_t)0xffffffff, "bev: frame %d has too many points", b - 1);
+      if (n > *max_n) *max_n = n;
+    }
+  }
+  SFA_CHECK_ARG(frame_offsets[0] >= 0, "bev: negative frame offset");
+  SFA_CHECK_ARG(*max_n == 0 || points, "bev: null points");
+  // Python floats -> f32 as numpy does for f32-array ops (NEP 50 / numpy 1.18 agree).
+  a->minX = (float)boundary[0];
+  a->maxX = (float)boundary[1];
+  a->minY = (float)boundary[2];
+  a->maxY = (float)boundary[3];
+  a->minZ = (float)boundary[4];
+  a->maxZ = (float)boundary[5];
+  a->disc = (float)(50.0 / 608.0);  // config/kitti_config.py:47
+  a->half_w = 304.5f;
+  a->max_height = (float)std::fabs(boundary[5] - boundary[4]);
+  for (int c = 0; c < 64; ++c) {
+    double v = std::log((double)c + 1.0) / std::log(64.0);
+    a->density[c] = c == 0 ? 0.0 : (v < 1.0 ? v : 1.0);
+  }
+  return SFA_OK;
 }
 
-// The scratch layout is fixed by the scratch's CAPACITY (the largest batch it was sized for), never
-// by the batch of the call: keys / counts (atomic path, zero between calls) and the binned path's
-// counters (zero between calls) sit at the same offsets for every call, and the record regions
-// (written before they are read, left dirty) always lie after them.  A layout by the call's batch
-// let a small-batch call's records land inside a later larger call's zero areas.
-static int bev_capacity_batch(size_t scratch_bytes) {
-  int cap = 0;
-  while (cap < SFA_BEV_MAX_BATCH && sfa_bev_scratch_size(cap + 1) <= scratch_bytes) ++cap;
-  return cap;
+// f(SR) with the blocked path's strip rows as a compile-time value
+template <typename F>
+int with_strip_rows(BevPath path, F&& f) {
+  return path == BevPath::kBlocked8 ? f(int_c<8>{}) : f(int_c<4>{});
 }
+
+int bev_blocked(const BevCall& c, const BevPlan& p) {
+  BlkScratch bk;
+  bk.rec = c.at<uint2>(p.blk_rec);
+  bk.tab = c.at<unsigned>(p.blk_tab);
+  bk.nblk_total = p.nblk_total;
+  std::copy(p.blk0, p.blk0 + c.batch + 1, bk.blk0);
+  if (c.max_n > 0) {
+    const dim3 g1((unsigned)((c.max_n + kBlkPts - 1) / kBlkPts), c.batch);
+    if (int rc = with_bool(c.raw, [&](auto RAW) {
+          return with_strip_rows(p.path, [&](auto SR) {
+            return launch({g1, dim3(kBlkThreads), c.st}, bev_blk_bin_kernel<RAW.value, SR.value>, c.pts, c.a, bk);
+          });
+        }))
+      return rc;
+  }
+  return with_layout_flip(c, [&](auto L, auto FLIP) {
+    return with_strip_rows(p.path, [&](auto SR) {
+      using G = BlkGeom<SR.value>;
+      return launch({dim3(G::strips, c.batch), dim3(G::threads), c.st},
+                    bev_blk_strip_kernel<L.value, FLIP.value, SR.value>, c.pts, c.a, bk, c.out);
+    });
+  });
+}
+
+int bev_binned(const BevCall& c, const BevPlan& p) {
+  const BinScratch bs{c.at<unsigned>(p.bin_count), c.at<unsigned>(p.bin_offset), c.at<unsigned>(p.bin_cursor),
+                      c.at<uint4>(p.bin_rec)};
+  if (c.max_n > 0) {
+    const dim3 g1((unsigned)((c.max_n + 256 * kBinPPT - 1) / (256 * kBinPPT)), c.batch);
+    if (int rc = with_bool(c.raw, [&](auto RAW) {
+          return launch({g1, dim3(256), c.st}, bev_bin_count_kernel<RAW.value>, c.pts, c.a, bs);
+        }))
+      return rc;
+    if (int rc = launch({dim3(1), dim3(kScanThreads), c.st}, bev_bin_scan_kernel, bs, c.batch)) return rc;
+    if (int rc = with_bool(c.raw, [&](auto RAW) {
+          return launch({g1, dim3(256), c.st}, bev_bin_kernel<RAW.value>, c.pts, c.a, bs);
+        }))
+      return rc;
+  }
+  const dim3 g3(kStrips, c.batch);
+  return with_layout_flip(c, [&](auto L, auto FLIP) {
+    return launch({g3, dim3(kStripThreads), c.st}, bev_strip_kernel<L.value, FLIP.value>, c.pts, c.a, bs, c.out);
+  });
+}
+
+int bev_atomic(const BevCall& c, const BevPlan& p) {
+  auto* keys = c.at<unsigned long long>(p.keys);
+  auto* counts = c.at<unsigned>(p.counts);
+  if (c.max_n > 0) {
+    const dim3 g1((unsigned)((c.max_n + 255) / 256), c.batch);
+    if (int rc = with_bool(c.raw, [&](auto RAW) {
+          return launch({g1, dim3(256), c.st}, bev_scatter_kernel<RAW.value>, c.pts, c.a, keys, counts);
+        }))
+      return rc;
+  }
+  const dim3 g2((unsigned)ceil_div(kBevCells, 256), c.batch);
+  return with_layout_flip(c, [&](auto L, auto FLIP) {
+    return launch({g2, dim3(256), c.st}, bev_gather_kernel<L.value, FLIP.value>, c.pts, c.a, keys, counts, c.out);
+  });
+}
+
+}  // namespace
 
 extern "C" int sfa_bev_voxelize(const float* points, const int64_t* frame_offsets, int batch,
                                 const double* boundary, int flags, int out_layout, void* out,
@@ -545,169 +648,23 @@ extern "C" int sfa_bev_voxelize(const float* points, const int64_t* frame_offset
   SFA_CHECK_ARG((flags & ~(SFA_BEV_PREFILTERED | SFA_BEV_FLIP_HW | SFA_BEV_FORCE_ATOMIC | SFA_BEV_FORCE_BINNED |
                            SFA_BEV_STRIP8)) == 0,
                 "bev: bad flags %d", flags);
-  const int flags_in = flags;
-  const bool flip = (flags & SFA_BEV_FLIP_HW) != 0;
-  const bool force_atomic = (flags & SFA_BEV_FORCE_ATOMIC) != 0;  // the atomic path (A/B, the equivalence test)
-  flags &= SFA_BEV_PREFILTERED;
-  BevArgs a;
-  int64_t max_n = 0;
-  for (int b = 0; b <= batch; ++b) {
-    a.start[b] = frame_offsets[b];
-    if (b > 0) {
-      const int64_t n = frame_offsets[b] - frame_offsets[b - 1];
-      SFA_CHECK_ARG(n >= 0, "bev: frame_offsets not monotone at %d", b);
-      SFA_CHECK_ARG(n < (int64_t)0xffffffff, "bev: frame %d has too many points", b - 1);
-      if (n > max_n) max_n = n;
-    }
+  BevCall c;
+  if (int rc = bev_fill_args(points, frame_offsets, batch, boundary, &c.a, &c.max_n)) return rc;
+  c.pts = reinterpret_cast<const float4*>(points);
+  c.batch = batch;
+  c.layout = out_layout;
+  c.raw = (flags & SFA_BEV_PREFILTERED) == 0;
+  c.flip = (flags & SFA_BEV_FLIP_HW) != 0;
+  c.out = out;
+  c.scratch = reinterpret_cast<char*>(scratch);
+  c.st = reinterpret_cast<hipStream_t>(stream);
+  const BevPlan p = bev_plan(scratch_bytes, batch, frame_offsets, flags);
+  switch (p.path) {
+    case BevPath::kBlocked4:
+    case BevPath::kBlocked8: return bev_blocked(c, p);
+    case BevPath::kBinned: return bev_binned(c, p);
+    default: return bev_atomic(c, p);
   }
-  SFA_CHECK_ARG(frame_offsets[0] >= 0, "bev: negative frame offset");
-  SFA_CHECK_ARG(max_n == 0 || points, "bev: null points");
-  // Python floats -> f32 as numpy does for f32-array ops (NEP 50 / numpy 1.18 agree).
-  a.minX = (float)boundary[0];
-  a.maxX = (float)boundary[1];
-  a.minY = (float)boundary[2];
-  a.maxY = (float)boundary[3];
-  a.minZ = (float)boundary[4];
-  a.maxZ = (float)boundary[5];
-  a.disc = (float)(50.0 / 608.0);  // config/kitti_config.py:47
-  a.half_w = 304.5f;
-  a.max_height = (float)std::fabs(boundary[5] - boundary[4]);
-  for (int c = 0; c < 64; ++c) {
-    double v = std::log((double)c + 1.0) / std::log(64.0);
-    a.density[c] = c == 0 ? 0.0 : (v < 1.0 ? v : 1.0);
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  auto* keys = reinterpret_cast<unsigned long long*>(scratch);
-  auto* counts = reinterpret_cast<unsigned*>(
-      reinterpret_cast<char*>(scratch) +
-      align_up((size_t)cap * kBevCells * sizeof(unsigned long long), 256));
-  const float4* p4 = reinterpret_cast<const float4*>(points);
-  // blocked-bin path (default) when the batch's regions and table fit the binned scratch
-  {
-    const bool s8 = (flags_in & SFA_BEV_STRIP8) != 0;
-    const int nstrips = s8 ? BlkGeom<8>::strips : BlkGeom<4>::strips;
-    const int maxr = s8 ? BlkGeom<8>::max_regions : BlkGeom<4>::max_regions;
-    BlkScratch bk;
-    int64_t nblk_total = 0;
-    for (int b = 0; b < batch; ++b) {
-      bk.blk0[b] = (int)nblk_total;
-      nblk_total += (frame_offsets[b + 1] - frame_offsets[b] + kBlkPts - 1) / kBlkPts;
-    }
-    bk.blk0[batch] = (int)nblk_total;
-    bk.nblk_total = (int)nblk_total;
-    const size_t rec_bytes = align_up((size_t)nblk_total * kBlkPts * sizeof(uint2), 256);
-    const size_t tab_bytes = (size_t)nblk_total * nstrips * sizeof(unsigned);
-    // after the binned path's (zero) counters, which it must not touch
-    const size_t cnt_bytes = 3 * align_up((size_t)cap * kStrips * sizeof(unsigned), 256);
-    int max_regions = 0;
-    for (int b = 0; b < batch; ++b) max_regions = std::max(max_regions, bk.blk0[b + 1] - bk.blk0[b]);
-    if (!force_atomic && !(flags_in & SFA_BEV_FORCE_BINNED) && max_regions <= maxr &&
-        cnt_bytes + rec_bytes + tab_bytes <= bev_atomic_bytes(cap)) {
-      char* sb = reinterpret_cast<char*>(scratch) + bev_atomic_bytes(cap) + cnt_bytes;
-      bk.rec = reinterpret_cast<uint2*>(sb);
-      bk.tab = reinterpret_cast<unsigned*>(sb + rec_bytes);
-      if (max_n > 0) {
-        dim3 g1((unsigned)((max_n + kBlkPts - 1) / kBlkPts), batch);
-        if (flags == SFA_BEV_RAW) {
-          if (s8) hipLaunchKernelGGL((bev_blk_bin_kernel<true, 8>), g1, dim3(kBlkThreads), 0, st, p4, a, bk);
-          else hipLaunchKernelGGL((bev_blk_bin_kernel<true, 4>), g1, dim3(kBlkThreads), 0, st, p4, a, bk);
-        } else {
-          if (s8) hipLaunchKernelGGL((bev_blk_bin_kernel<false, 8>), g1, dim3(kBlkThreads), 0, st, p4, a, bk);
-          else hipLaunchKernelGGL((bev_blk_bin_kernel<false, 4>), g1, dim3(kBlkThreads), 0, st, p4, a, bk);
-        }
-        SFA_LAUNCH_CHECK();
-      }
-      dim3 g3(nstrips, batch);
-#define SFA_BEV_BLK(L, F)                                                                                    \
-  do {                                                                                                      \
-    if (s8)                                                                                                 \
-      hipLaunchKernelGGL((bev_blk_strip_kernel<L, F, 8>), g3, dim3(BlkGeom<8>::threads), 0, st, p4, a, bk, out); \
-    else                                                                                                    \
-      hipLaunchKernelGGL((bev_blk_strip_kernel<L, F, 4>), g3, dim3(BlkGeom<4>::threads), 0, st, p4, a, bk, out); \
-  } while (0)
-      switch (out_layout) {
-        case SFA_BEV_NCHW3_F32:
-          if (flip) SFA_BEV_BLK(SFA_BEV_NCHW3_F32, true); else SFA_BEV_BLK(SFA_BEV_NCHW3_F32, false);
-          break;
-        case SFA_BEV_NCHW3_F64:
-          if (flip) SFA_BEV_BLK(SFA_BEV_NCHW3_F64, true); else SFA_BEV_BLK(SFA_BEV_NCHW3_F64, false);
-          break;
-        default:
-          if (flip) SFA_BEV_BLK(SFA_BEV_NHWC4_F32, true); else SFA_BEV_BLK(SFA_BEV_NHWC4_F32, false);
-      }
-#undef SFA_BEV_BLK
-      SFA_LAUNCH_CHECK();
-      return SFA_OK;
-    }
-  }
-  // binned path (round 2) when forced or when the blocked regions do not fit
-  const size_t bin_bytes = align_up((size_t)cap * kStrips * sizeof(unsigned), 256);
-  const size_t binned_bytes = bev_atomic_bytes(cap);  // the binned path's region
-  const int64_t total = frame_offsets[batch] - frame_offsets[0];
-  if (!force_atomic && 3 * bin_bytes < binned_bytes &&
-      (uint64_t)total <= (uint64_t)((binned_bytes - 3 * bin_bytes) / sizeof(uint4)) && total < (int64_t)0xffffffff) {
-    char* sb = reinterpret_cast<char*>(scratch) + bev_atomic_bytes(cap);
-    BinScratch bs;
-    bs.count = reinterpret_cast<unsigned*>(sb);
-    bs.offset = reinterpret_cast<unsigned*>(sb + bin_bytes);
-    bs.cursor = reinterpret_cast<unsigned*>(sb + 2 * bin_bytes);
-    bs.rec = reinterpret_cast<uint4*>(sb + 3 * bin_bytes);
-    if (max_n > 0) {
-      dim3 g1((unsigned)((max_n + 256 * kBinPPT - 1) / (256 * kBinPPT)), batch);
-      if (flags == SFA_BEV_RAW)
-        hipLaunchKernelGGL(bev_bin_count_kernel<true>, g1, dim3(256), 0, st, p4, a, bs);
-      else
-        hipLaunchKernelGGL(bev_bin_count_kernel<false>, g1, dim3(256), 0, st, p4, a, bs);
-      SFA_LAUNCH_CHECK();
-      hipLaunchKernelGGL(bev_bin_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, bs, batch);
-      SFA_LAUNCH_CHECK();
-      if (flags == SFA_BEV_RAW)
-        hipLaunchKernelGGL(bev_bin_kernel<true>, g1, dim3(256), 0, st, p4, a, bs);
-      else
-        hipLaunchKernelGGL(bev_bin_kernel<false>, g1, dim3(256), 0, st, p4, a, bs);
-      SFA_LAUNCH_CHECK();
-    }
-    dim3 g3(kStrips, batch);
-#define SFA_BEV_STRIP(L, F) \
-  hipLaunchKernelGGL((bev_strip_kernel<L, F>), g3, dim3(kStripThreads), 0, st, p4, a, bs, out)
-    switch (out_layout) {
-      case SFA_BEV_NCHW3_F32:
-        if (flip) SFA_BEV_STRIP(SFA_BEV_NCHW3_F32, true); else SFA_BEV_STRIP(SFA_BEV_NCHW3_F32, false);
-        break;
-      case SFA_BEV_NCHW3_F64:
-        if (flip) SFA_BEV_STRIP(SFA_BEV_NCHW3_F64, true); else SFA_BEV_STRIP(SFA_BEV_NCHW3_F64, false);
-        break;
-      default:
-        if (flip) SFA_BEV_STRIP(SFA_BEV_NHWC4_F32, true); else SFA_BEV_STRIP(SFA_BEV_NHWC4_F32, false);
-    }
-#undef SFA_BEV_STRIP
-    SFA_LAUNCH_CHECK();
-    return SFA_OK;
-  }
-  if (max_n > 0) {
-    dim3 g1((unsigned)((max_n + 255) / 256), batch);
-    if (flags == SFA_BEV_RAW)
-      hipLaunchKernelGGL(bev_scatter_kernel<true>, g1, dim3(256), 0, st, p4, a, keys, counts);
-    else
-      hipLaunchKernelGGL(bev_scatter_kernel<false>, g1, dim3(256), 0, st, p4, a, keys, counts);
-    SFA_LAUNCH_CHECK();
-  }
-  dim3 g2((unsigned)ceil_div(kBevCells, 256), batch);
-#define SFA_BEV_GATHER(L, F) \
-  hipLaunchKernelGGL((bev_gather_kernel<L, F>), g2, dim3(256), 0, st, p4, a, keys, counts, out)
-  switch (out_layout) {
-    case SFA_BEV_NCHW3_F32:
-      if (flip) SFA_BEV_GATHER(SFA_BEV_NCHW3_F32, true); else SFA_BEV_GATHER(SFA_BEV_NCHW3_F32, false);
-      break;
-    case SFA_BEV_NCHW3_F64:
-      if (flip) SFA_BEV_GATHER(SFA_BEV_NCHW3_F64, true); else SFA_BEV_GATHER(SFA_BEV_NCHW3_F64, false);
-      break;
-    default:
-      if (flip) SFA_BEV_GATHER(SFA_BEV_NHWC4_F32, true); else SFA_BEV_GATHER(SFA_BEV_NHWC4_F32, false);
-  }
-#undef SFA_BEV_GATHER
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
 }
 
 // ---------------------------------------------------------------- filter --
@@ -844,14 +801,11 @@ extern "C" int sfa_filter_points(const float* points, int64_t n_points, const do
   if (nb == 0) {
     return launch_zero_words(out_count, sizeof(int64_t), st);  // a kernel node, not a memset (aux_kernels.h)
   }
-  hipLaunchKernelGGL(filter_count_kernel, dim3(nb), dim3(kFiltThreads), 0, st, p4,
-                     (long long)n_points, f, bcount);
-  SFA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(1024), 0, st, bcount, nb,
-                     reinterpret_cast<long long*>(out_count));
-  SFA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(filter_scatter_kernel, dim3(nb), dim3(kFiltThreads), 0, st, p4,
-                     (long long)n_points, f, bcount, reinterpret_cast<float4*>(out));
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  if (int rc = launch({dim3(nb), dim3(kFiltThreads), st}, filter_count_kernel, p4, (long long)n_points, f, bcount))
+    return rc;
+  if (int rc = launch({dim3(1), dim3(1024), st}, filter_scan_kernel, bcount, nb,
+                      reinterpret_cast<long long*>(out_count)))
+    return rc;
+  return launch({dim3(nb), dim3(kFiltThreads), st}, filter_scatter_kernel, p4, (long long)n_points, f, bcount,
+                reinterpret_cast<float4*>(out));
 }

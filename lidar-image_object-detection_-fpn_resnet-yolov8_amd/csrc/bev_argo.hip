@@ -30,21 +30,15 @@
 #include <cstdint>
 
 #include "aux_kernels.h"
-#include "common.h"
+#include "bev_plan.h"
+#include "dispatch.h"
 
 namespace sfa {
 
-constexpr int kArgoMaxDim = SFA_ARGO_BEV_MAX_DIM;  // H, W <= 2048
-constexpr int kArgoStripCells = 4096;              // cells of a strip at most: 3 LDS words each, 48 KiB
-constexpr int kArgoMaxStripRows = 8;
-constexpr int kArgoMaxStrips = 1024;               // H <= 2048 and SR >= 2 whenever W <= 2048
-constexpr int kArgoBlkPts = 1024;
+// the limits the scratch plan uses (strip cells, rows and count, points and regions): bev_plan.h
 constexpr int kArgoBlkThreads = 256;
 constexpr int kArgoPPT = kArgoBlkPts / kArgoBlkThreads;  // 4
 constexpr int kArgoStripThreads = 512;
-constexpr int kArgoMaxRegions = 1024;  // regions of one frame a strip block indexes (1 Mi points)
-constexpr size_t kArgoHeaderBytes = 256;  // the frames' intensity maxima, SFA_BEV_MAX_BATCH words
-static_assert(SFA_BEV_MAX_BATCH * sizeof(unsigned) <= kArgoHeaderBytes, "header");
 static_assert(kArgoMaxStrips == kArgoPPT * kArgoBlkThreads, "the bin pass scans 4 strips per thread");
 
 struct ArgoArgs {
@@ -341,10 +335,6 @@ static int argo_shape(const double* bnd, double d, int* H, int* W) {
   return SFA_OK;
 }
 
-static size_t argo_atomic_bytes(int batch, int H, int W) {
-  return kArgoHeaderBytes + align_up((size_t)batch * H * W * 3 * sizeof(unsigned), 256);
-}
-
 }  // namespace sfa
 
 using namespace sfa;
@@ -353,14 +343,88 @@ extern "C" int sfa_argo_bev_shape(const double* boundary, double discretization,
   return argo_shape(boundary, discretization, H, W);
 }
 
-// First half: the frames' maximum words + the atomic path's cells (zero between calls); second
-// half: the record path's regions and table (written before they are read, left dirty).  The
-// halves are split by the scratch's size alone, so calls of any batch and any map size that the
-// scratch holds may share it: no call's records land in another call's zero area.
-extern "C" size_t sfa_argo_bev_scratch_size(int batch, int H, int W) {
-  if (batch < 1 || batch > SFA_BEV_MAX_BATCH || H < 1 || H > kArgoMaxDim || W < 1 || W > kArgoMaxDim) return 0;
-  return 2 * argo_atomic_bytes(batch, H, W);
+// The scratch's halves and the choice of the path: argo_plan (bev_plan.h).
+extern "C" size_t sfa_argo_bev_scratch_size(int batch, int H, int W) { return argo_scratch_size(batch, H, W); }
+
+namespace {
+
+// What the launches of both paths share.
+struct ArgoCall {
+  const float* pts;
+  ArgoArgs a;
+  int batch, layout;
+  int64_t max_n;  // points of the largest frame
+  bool vec4;      // one aligned float4 per point
+  void* out;
+  char* scratch;
+  hipStream_t st;
+  template <typename T>
+  T* at(const Region& r) const { return reinterpret_cast<T*>(scratch + r.off); }
+};
+
+int argo_records(const ArgoCall& c, const ArgoPlan& p) {
+  ArgoRecScratch rs;
+  rs.zi = c.at<uint2>(p.zi);
+  rs.cell = c.at<unsigned short>(p.cell);
+  rs.tab = c.at<unsigned>(p.tab);
+  rs.nblk_total = p.nblk_total;
+  std::copy(p.blk0, p.blk0 + c.batch + 1, rs.blk0);
+  unsigned* fmax = c.at<unsigned>(p.fmax);
+  if (c.max_n > 0) {
+    const dim3 g1((unsigned)((c.max_n + kArgoBlkPts - 1) / kArgoBlkPts), c.batch);
+    if (int rc = with_bool(c.vec4, [&](auto VEC4) {
+          return launch({g1, dim3(kArgoBlkThreads), c.st}, argo_bin_kernel<VEC4.value>, c.pts, c.a, rs, fmax);
+        }))
+      return rc;
+  }
+  const dim3 g2(c.a.strips, c.batch);
+  return with_f32_layout(c.layout, [&](auto L) {
+    return launch({g2, dim3(kArgoStripThreads), c.st}, argo_strip_kernel<L.value>, c.a, rs, fmax, c.out);
+  });
 }
+
+int argo_atomic(const ArgoCall& c, const ArgoPlan& p) {
+  unsigned* fmax = c.at<unsigned>(p.fmax);
+  unsigned* cells3 = c.at<unsigned>(p.cells3);
+  if (c.max_n > 0) {
+    const int64_t nb = (c.max_n + 255) / 256;
+    if (nb > INT32_MAX) {
+      set_error("argo bev: a frame of %lld points is beyond the launch grid", (long long)c.max_n);
+      return SFA_E_UNSUPPORTED;
+    }
+    const dim3 g1((unsigned)nb, c.batch);
+    if (int rc = with_bool(c.vec4, [&](auto VEC4) {
+          return launch({g1, dim3(256), c.st}, argo_scatter_kernel<VEC4.value>, c.pts, c.a, cells3, fmax);
+        }))
+      return rc;
+  }
+  const dim3 g2((unsigned)ceil_div(c.a.H * c.a.W, 256), c.batch);
+  return with_f32_layout(c.layout, [&](auto L) {
+    return launch({g2, dim3(256), c.st}, argo_gather_kernel<L.value>, c.a, cells3, fmax, c.out);
+  });
+}
+
+// The frames' starts and the largest frame.
+int argo_fill_frames(const float* points, const int64_t* frame_offsets, int batch, ArgoArgs* a, int64_t* max_n) {
+  SFA_CHECK_ARG(frame_offsets[0] >= 0, "argo bev: negative frame offset");
+  *max_n = 0;
+  for (int b = 0; b <= batch; ++b) {
+    a->start[b] = frame_offsets[b];
+    if (b > 0) {
+      const int64_t n = frame_offsets[b] - frame_offsets[b - 1];
+      SFA_CHECK_ARG(n >= 0, "argo bev: frame_offsets not monotone at %d", b);
+      if (n >= (int64_t)0xffffffff) {  // the per-cell count is 32 bits
+        set_error("argo bev: frame %d has %lld points (< 2^32 - 1 supported)", b - 1, (long long)n);
+        return SFA_E_UNSUPPORTED;
+      }
+      *max_n = std::max(*max_n, n);
+    }
+  }
+  SFA_CHECK_ARG(*max_n == 0 || points, "argo bev: null points");
+  return SFA_OK;
+}
+
+}  // namespace
 
 extern "C" int sfa_argo_bev_voxelize(const float* points, int point_stride, const int64_t* frame_offsets, int batch,
                                      const double* boundary, double discretization, int out_layout, void* out,
@@ -370,36 +434,23 @@ extern "C" int sfa_argo_bev_voxelize(const float* points, int point_stride, cons
   SFA_CHECK_ARG(frame_offsets && boundary && out && scratch, "argo bev: null argument");
   SFA_CHECK_ARG(point_stride >= 3, "argo bev: point_stride %d (floats per point: 3 or >= 4)", point_stride);
   const bool force_atomic = (out_layout & SFA_ARGO_BEV_FORCE_ATOMIC) != 0;
-  const int layout = out_layout & ~SFA_ARGO_BEV_FORCE_ATOMIC;
-  SFA_CHECK_ARG(layout == SFA_BEV_NCHW3_F32 || layout == SFA_BEV_NHWC4_F32,
+  ArgoCall c;
+  c.layout = out_layout & ~SFA_ARGO_BEV_FORCE_ATOMIC;
+  SFA_CHECK_ARG(c.layout == SFA_BEV_NCHW3_F32 || c.layout == SFA_BEV_NHWC4_F32,
                 "argo bev: out_layout %d (SFA_BEV_NCHW3_F32 or SFA_BEV_NHWC4_F32)", out_layout);
-  ArgoArgs a;
-  const int rc = argo_shape(boundary, discretization, &a.H, &a.W);
-  if (rc != SFA_OK) return rc;
-  SFA_CHECK_ARG(frame_offsets[0] >= 0, "argo bev: negative frame offset");
-  int64_t max_n = 0;
-  for (int b = 0; b <= batch; ++b) {
-    a.start[b] = frame_offsets[b];
-    if (b > 0) {
-      const int64_t n = frame_offsets[b] - frame_offsets[b - 1];
-      SFA_CHECK_ARG(n >= 0, "argo bev: frame_offsets not monotone at %d", b);
-      if (n >= (int64_t)0xffffffff) {  // the per-cell count is 32 bits
-        set_error("argo bev: frame %d has %lld points (< 2^32 - 1 supported)", b - 1, (long long)n);
-        return SFA_E_UNSUPPORTED;
-      }
-      max_n = std::max(max_n, n);
-    }
-  }
-  SFA_CHECK_ARG(max_n == 0 || points, "argo bev: null points");
+  ArgoArgs& a = c.a;
+  if (int rc = argo_shape(boundary, discretization, &a.H, &a.W)) return rc;
+  if (int rc = argo_fill_frames(points, frame_offsets, batch, &a, &c.max_n)) return rc;
   SFA_CHECK_ARG(reinterpret_cast<uintptr_t>(scratch) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 &&
                     reinterpret_cast<uintptr_t>(points) % 4 == 0,
                 "argo bev: misaligned buffer (scratch / out: 16 B, points: 4 B)");
-  const size_t need = sfa_argo_bev_scratch_size(batch, a.H, a.W);
+  const size_t need = argo_scratch_size(batch, a.H, a.W);
   if (scratch_bytes < need) {
     set_error("argo bev: scratch of %zu bytes, %d frames of %d x %d need %zu (sfa_argo_bev_scratch_size)",
               scratch_bytes, batch, a.H, a.W, need);
     return SFA_E_WORKSPACE;
   }
+  const ArgoPlan p = argo_plan(scratch_bytes, batch, frame_offsets, a.H, a.W, force_atomic);
   // Python floats -> f32 as numpy does for ops with a float32 array
   a.minX = (float)boundary[0];
   a.maxX = (float)boundary[1];
@@ -410,67 +461,16 @@ extern "C" int sfa_argo_bev_voxelize(const float* points, int point_stride, cons
   a.disc = (float)discretization;
   a.z_range = (float)(boundary[5] - boundary[4]);
   a.stride = point_stride;
-  a.strip_rows = std::max(1, std::min({kArgoMaxStripRows, kArgoStripCells / a.W, a.H}));
-  a.strips = ceil_div(a.H, a.strip_rows);
-  const bool vec4 = point_stride == 4 && reinterpret_cast<uintptr_t>(points) % 16 == 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  char* sb = reinterpret_cast<char*>(scratch);
-  unsigned* fmax = reinterpret_cast<unsigned*>(sb);
-  const size_t rec_base = (scratch_bytes / 2) & ~(size_t)255;  // >= the atomic area's end (need / 2)
-  const size_t rec_room = scratch_bytes - rec_base;
-
-  ArgoRecScratch rs;
-  int64_t nblk_total = 0, max_regions = 0;
-  for (int b = 0; b < batch; ++b) {
-    rs.blk0[b] = (int)std::min<int64_t>(nblk_total, INT32_MAX);
-    const int64_t r = (frame_offsets[b + 1] - frame_offsets[b] + kArgoBlkPts - 1) / kArgoBlkPts;
-    nblk_total += r;
-    max_regions = std::max(max_regions, r);
-  }
-  rs.blk0[batch] = (int)nblk_total;
-  rs.nblk_total = (int)nblk_total;
-  const size_t zi_bytes = (size_t)nblk_total * kArgoBlkPts * sizeof(uint2);
-  const size_t cell_bytes = (size_t)nblk_total * kArgoBlkPts * sizeof(unsigned short);
-  const size_t tab_bytes = (size_t)nblk_total * a.strips * sizeof(unsigned);
-  const bool records = !force_atomic && max_regions <= kArgoMaxRegions &&
-                       a.strips <= kArgoMaxStrips && zi_bytes + cell_bytes + tab_bytes <= rec_room;
-  if (records) {
-    rs.zi = reinterpret_cast<uint2*>(sb + rec_base);
-    rs.cell = reinterpret_cast<unsigned short*>(sb + rec_base + zi_bytes);
-    rs.tab = reinterpret_cast<unsigned*>(sb + rec_base + zi_bytes + cell_bytes);
-    if (max_n > 0) {
-      dim3 g1((unsigned)((max_n + kArgoBlkPts - 1) / kArgoBlkPts), batch);
-      if (vec4) hipLaunchKernelGGL(argo_bin_kernel<true>, g1, dim3(kArgoBlkThreads), 0, st, points, a, rs, fmax);
-      else hipLaunchKernelGGL(argo_bin_kernel<false>, g1, dim3(kArgoBlkThreads), 0, st, points, a, rs, fmax);
-      SFA_LAUNCH_CHECK();
-    }
-    dim3 g2(a.strips, batch);
-    if (layout == SFA_BEV_NHWC4_F32)
-      hipLaunchKernelGGL(argo_strip_kernel<SFA_BEV_NHWC4_F32>, g2, dim3(kArgoStripThreads), 0, st, a, rs, fmax, out);
-    else
-      hipLaunchKernelGGL(argo_strip_kernel<SFA_BEV_NCHW3_F32>, g2, dim3(kArgoStripThreads), 0, st, a, rs, fmax, out);
-    SFA_LAUNCH_CHECK();
-  } else {
-    unsigned* cells3 = reinterpret_cast<unsigned*>(sb + kArgoHeaderBytes);
-    if (max_n > 0) {
-      const int64_t nb = (max_n + 255) / 256;
-      if (nb > INT32_MAX) {
-        set_error("argo bev: a frame of %lld points is beyond the launch grid", (long long)max_n);
-        return SFA_E_UNSUPPORTED;
-      }
-      dim3 g1((unsigned)nb, batch);
-      if (vec4) hipLaunchKernelGGL(argo_scatter_kernel<true>, g1, dim3(256), 0, st, points, a, cells3, fmax);
-      else hipLaunchKernelGGL(argo_scatter_kernel<false>, g1, dim3(256), 0, st, points, a, cells3, fmax);
-      SFA_LAUNCH_CHECK();
-    }
-    dim3 g2((unsigned)ceil_div(a.H * a.W, 256), batch);
-    if (layout == SFA_BEV_NHWC4_F32)
-      hipLaunchKernelGGL(argo_gather_kernel<SFA_BEV_NHWC4_F32>, g2, dim3(256), 0, st, a, cells3, fmax, out);
-    else
-      hipLaunchKernelGGL(argo_gather_kernel<SFA_BEV_NCHW3_F32>, g2, dim3(256), 0, st, a, cells3, fmax, out);
-    SFA_LAUNCH_CHECK();
-  }
+  a.strip_rows = p.strip_rows;
+  a.strips = p.strips;
+  c.pts = points;
+  c.batch = batch;
+  c.vec4 = point_stride == 4 && reinterpret_cast<uintptr_t>(points) % 16 == 0;
+  c.out = out;
+  c.scratch = reinterpret_cast<char*>(scratch);
+  c.st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = p.records ? argo_records(c, p) : argo_atomic(c, p)) return rc;
   // the frames' maxima back to zero (only a pass over points can have raised them)
-  if (max_n > 0) return launch_zero_words(fmax, (size_t)batch * sizeof(unsigned), st);
+  if (c.max_n > 0) return launch_zero_words(c.at<unsigned>(p.fmax), (size_t)batch * sizeof(unsigned), c.st);
   return SFA_OK;
 }

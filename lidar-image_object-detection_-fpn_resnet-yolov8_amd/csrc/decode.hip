@@ -41,8 +41,8 @@
 // decode_class_merge_kernel then reduces each (frame, class)'s NT tile lists to one sorted K-list,
 // kMergeMax / K lists per pass, and the per-frame merge + gather above run over those C lists
 // (S = 1).  By the partition argument the result equals the oracle's bit for bit.
-#include "common.h"
 #include "decode_plan.h"
+#include "dispatch.h"
 
 namespace sfa {
 
@@ -847,9 +847,7 @@ using namespace sfa;
 
 extern "C" size_t sfa_decode_workspace_size(int batch, int num_classes, int K) {
   if (batch <= 0 || num_classes <= 0 || K <= 0) return 0;
-  // the band candidates (C * S * K per frame, S <= 16) or the per-class ones (C * K)
-  const size_t n = (size_t)batch * num_classes * K * 16;
-  return align_up(n * sizeof(unsigned), 256) + align_up(n * sizeof(int), 256);
+  return list_workspace_bytes(batch, num_classes, K);  // the band candidates (S <= 16) or the per-class ones
 }
 
 extern "C" size_t sfa_decode_workspace_size_hw(int batch, int num_classes, int height, int width, int K) {
@@ -867,27 +865,53 @@ extern "C" size_t sfa_topk_workspace_size_hw(int batch, int num_classes, int hei
   return sfa_decode_workspace_size_hw(batch, num_classes, height, width, K);
 }
 
-// Tiled form, shared by sfa_decode (PEAK) and sfa_topk: the tile lists, then one K-list per
-// (frame, class) at *ck / *ci (workspace already checked against tiled_layout().total).
+// The code object lists the kernel templates in the order they are first named.  Naming them once
+// here fixes that order (and so the device binary) whatever the arrangement of the host code below.
+[[maybe_unused]] static const void* const kKernelOrder[] = {
+    (void*)decode_band_topk_kernel<0, true, true>,   (void*)decode_band_topk_kernel<0, true, false>,
+    (void*)decode_class_topk_kernel<true>,           (void*)decode_band_topk_kernel<0, false, true>,
+    (void*)topk_band_merge_kernel<true>,             (void*)topk_band_merge_kernel<false>,
+    (void*)decode_band_topk_kernel<0, false, false>, (void*)decode_class_topk_kernel<false>,
+    (void*)topk_class_out_kernel<true>,              (void*)topk_class_out_kernel<false>};
+
+// The candidate lists of one call: `lists` sorted K-lists per (frame, class) at key / idx.
+struct CandLists {
+  unsigned* key;
+  int* idx;
+  int lists;
+  bool band_merge;  // the lists go to the band merge kernels (tiled, band); false: the per-class ones
+};
+
+// The stage sfa_decode (PEAK) and sfa_topk share: the form is chosen by the map (tiled above
+// kDecMaxHW cells, else bands when band_plan finds a split, else one block per class), the
+// workspace is carved by decode_plan.h's layouts and the list kernels are launched.  The workspace
+// was checked against sfa_decode_workspace_size_hw, which covers the chosen form.
 template <bool PEAK>
-static int tiled_class_lists(const float* hm, int batch, int num_classes, int height, int width, int K,
-                             int apply_sigmoid, void* workspace, hipStream_t st, unsigned** ck, int** ci) {
-  int R, TC, NY, NX;
-  tile_plan(height, width, &R, &TC, &NY, &NX);
-  const int NT = NY * NX;
-  const TiledLayout l = tiled_layout(batch, num_classes, NT, K);
+static int candidate_lists(const float* hm, int batch, int num_classes, int height, int width, int K,
+                           int apply_sigmoid, void* workspace, hipStream_t st, CandLists* out) {
   char* ws = reinterpret_cast<char*>(workspace);
-  auto* tk = reinterpret_cast<unsigned*>(ws);
-  auto* ti = reinterpret_cast<int*>(ws + l.tile_idx);
-  *ck = reinterpret_cast<unsigned*>(ws + l.class_key);
-  *ci = reinterpret_cast<int*>(ws + l.class_idx);
-  hipLaunchKernelGGL((decode_band_topk_kernel<0, PEAK, true>), dim3(NT, num_classes, batch), dim3(kBandThreads), 0,
-                     st, hm, num_classes, height, width, K, R, apply_sigmoid, tk, ti, TileGeo<true>{NX, TC});
-  SFA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(decode_class_merge_kernel, dim3(batch * num_classes), dim3(1024), 0, st, tk, ti, NT, K, *ck,
-                     *ci);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  auto* key = reinterpret_cast<unsigned*>(ws);
+  if (height * width > kDecMaxHW) {  // tile lists -> one merged list per class
+    int R, TC, NY, NX;
+    tile_plan(height, width, &R, &TC, &NY, &NX);
+    const int NT = NY * NX;
+    const TiledLayout l = tiled_layout(batch, num_classes, NT, K);
+    auto* ti = reinterpret_cast<int*>(ws + l.tile_idx);
+    *out = {reinterpret_cast<unsigned*>(ws + l.class_key), reinterpret_cast<int*>(ws + l.class_idx), 1, true};
+    if (int rc = launch({dim3(NT, num_classes, batch), dim3(kBandThreads), st}, decode_band_topk_kernel<0, PEAK, true>,
+                        hm, num_classes, height, width, K, R, apply_sigmoid, key, ti, TileGeo<true>{NX, TC}))
+      return rc;
+    return launch({dim3(batch * num_classes), dim3(1024), st}, decode_class_merge_kernel, key, ti, NT, K, out->key,
+                  out->idx);
+  }
+  int S = 0, R = height;
+  band_plan(num_classes, height, width, K, &S, &R);
+  *out = {key, reinterpret_cast<int*>(ws + list_layout(batch, num_classes, S > 0 ? S : 1, K).idx), S > 0 ? S : 1, S > 0};
+  if (S > 0)
+    return launch({dim3(S, num_classes, batch), dim3(kBandThreads), st}, decode_band_topk_kernel<0, PEAK, false>, hm,
+                  num_classes, height, width, K, R, apply_sigmoid, key, out->idx, TileGeo<false>{});
+  return launch({dim3(batch * num_classes), dim3(kDecThreads), st}, decode_class_topk_kernel<PEAK>, hm, num_classes,
+                height, width, K, apply_sigmoid, key, out->idx);
 }
 
 extern "C" int sfa_decode(const float* hm, const float* off, const float* dir, const float* z,
@@ -907,45 +931,14 @@ extern "C" int sfa_decode(const float* hm, const float* off, const float* dir, c
     return SFA_E_WORKSPACE;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (height * width > kDecMaxHW) {  // tiled: tile lists -> class lists -> the per-frame merge over C lists
-    unsigned* ck;
-    int* ci;
-    const int rc = tiled_class_lists<true>(hm, batch, num_classes, height, width, K, apply_sigmoid, workspace, st,
-                                           &ck, &ci);
-    if (rc != SFA_OK) return rc;
-    hipLaunchKernelGGL(decode_band_merge_gather_kernel, dim3(batch), dim3(1024), 0, st, ck, ci, num_classes, 1, K,
-                       height, width, apply_sigmoid, off, dir, z, dim, dets);
-    SFA_LAUNCH_CHECK();
-    return SFA_OK;
-  }
-  int S = 0, R = height;
-  band_plan(num_classes, height, width, K, &S, &R);
-  if (S > 0) {
-    const size_t nb = (size_t)batch * num_classes * S * K;
-    auto* bk = reinterpret_cast<unsigned*>(workspace);
-    auto* bi = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + align_up(nb * sizeof(unsigned), 256));
-    if (align_up(nb * sizeof(unsigned), 256) + nb * sizeof(int) > workspace_bytes) {
-      set_error("decode: workspace too small");
-      return SFA_E_WORKSPACE;
-    }
-    hipLaunchKernelGGL(decode_band_topk_kernel<0>, dim3(S, num_classes, batch), dim3(kBandThreads), 0, st, hm,
-                       num_classes, height, width, K, R, apply_sigmoid, bk, bi, TileGeo<false>{});
-    SFA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(decode_band_merge_gather_kernel, dim3(batch), dim3(1024), 0, st, bk, bi, num_classes, S,
-                       K, height, width, apply_sigmoid, off, dir, z, dim, dets);
-    SFA_LAUNCH_CHECK();
-    return SFA_OK;
-  }
-  const size_t n = (size_t)batch * num_classes * K;
-  auto* ck = reinterpret_cast<unsigned*>(workspace);
-  auto* ci = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) +
-                                    align_up(n * sizeof(unsigned), 256));
-  hipLaunchKernelGGL(decode_class_topk_kernel<true>, dim3(batch * num_classes), dim3(kDecThreads), 0, st, hm, num_classes, height, width, K, apply_sigmoid, ck, ci);
-  SFA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(decode_merge_gather_kernel, dim3(batch), dim3(256), 0, st, ck, ci,
-                     num_classes, K, height, width, apply_sigmoid, off, dir, z, dim, dets);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  CandLists c;
+  if (int rc = candidate_lists<true>(hm, batch, num_classes, height, width, K, apply_sigmoid, workspace, st, &c))
+    return rc;
+  if (c.band_merge)  // the per-frame merge over C x lists lists, then the gather
+    return launch({dim3(batch), dim3(1024), st}, decode_band_merge_gather_kernel, c.key, c.idx, num_classes, c.lists, K,
+                  height, width, apply_sigmoid, off, dir, z, dim, dets);
+  return launch({dim3(batch), dim3(256), st}, decode_merge_gather_kernel, c.key, c.idx, num_classes, K, height, width,
+                apply_sigmoid, off, dir, z, dim, dets);
 }
 
 extern "C" int sfa_heat_nms(const float* heat, float* out, int64_t maps, int height, int width, void* stream) {
@@ -953,10 +946,8 @@ extern "C" int sfa_heat_nms(const float* heat, float* out, int64_t maps, int hei
   const int64_t n = maps * (int64_t)height * width;
   if (n == 0) return SFA_OK;
   SFA_CHECK_ARG(heat && out && heat != out, "heat_nms: null or aliased buffers");
-  hipLaunchKernelGGL(heat_nms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), heat, out, n, height, width);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({dim3((unsigned)((n + 255) / 256)), dim3(256), reinterpret_cast<hipStream_t>(stream)}, heat_nms_kernel,
+                heat, out, n, height, width);
 }
 
 extern "C" size_t sfa_topk_workspace_size(int batch, int num_classes, int K) {
@@ -977,53 +968,16 @@ extern "C" int sfa_topk(const float* scores, int batch, int num_classes, int hei
     return SFA_E_WORKSPACE;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int groups = per_channel ? batch * num_classes : batch;
-  if (height * width > kDecMaxHW) {  // tiled (no peak test), then the band merge over C (or 1) lists
-    unsigned* ck;
-    int* ci;
-    const int rc = tiled_class_lists<false>(scores, batch, num_classes, height, width, K, 0, workspace, st, &ck, &ci);
-    if (rc != SFA_OK) return rc;
-    if (per_channel)
-      hipLaunchKernelGGL(topk_band_merge_kernel<true>, dim3(groups), dim3(1024), 0, st, ck, ci, num_classes, 1, K,
-                         width, out_scores, out_inds, out_clses, out_ys, out_xs);
-    else
-      hipLaunchKernelGGL(topk_band_merge_kernel<false>, dim3(groups), dim3(1024), 0, st, ck, ci, num_classes, 1, K,
-                         width, out_scores, out_inds, out_clses, out_ys, out_xs);
-    SFA_LAUNCH_CHECK();
-    return SFA_OK;
-  }
-  int S = 0, R = height;
-  band_plan(num_classes, height, width, K, &S, &R);
-  if (S > 0) {
-    const size_t nb = (size_t)batch * num_classes * S * K;
-    auto* bk = reinterpret_cast<unsigned*>(workspace);
-    auto* bi = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + align_up(nb * sizeof(unsigned), 256));
-    hipLaunchKernelGGL((decode_band_topk_kernel<0, false>), dim3(S, num_classes, batch), dim3(kBandThreads), 0, st,
-                       scores, num_classes, height, width, K, R, 0, bk, bi, TileGeo<false>{});
-    SFA_LAUNCH_CHECK();
-    if (per_channel)
-      hipLaunchKernelGGL(topk_band_merge_kernel<true>, dim3(groups), dim3(1024), 0, st, bk, bi, num_classes, S, K,
-                         width, out_scores, out_inds, out_clses, out_ys, out_xs);
-    else
-      hipLaunchKernelGGL(topk_band_merge_kernel<false>, dim3(groups), dim3(1024), 0, st, bk, bi, num_classes, S, K,
-                         width, out_scores, out_inds, out_clses, out_ys, out_xs);
-    SFA_LAUNCH_CHECK();
-    return SFA_OK;
-  }
-  const size_t n = (size_t)batch * num_classes * K;
-  auto* ck = reinterpret_cast<unsigned*>(workspace);
-  auto* ci = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + align_up(n * sizeof(unsigned), 256));
-  hipLaunchKernelGGL(decode_class_topk_kernel<false>, dim3(batch * num_classes), dim3(kDecThreads), 0, st, scores,
-                     num_classes, height, width, K, 0, ck, ci);
-  SFA_LAUNCH_CHECK();
-  if (per_channel)
-    hipLaunchKernelGGL(topk_class_out_kernel<true>, dim3(groups), dim3(256), 0, st, ck, ci, num_classes, K, width,
-                       out_scores, out_inds, out_clses, out_ys, out_xs);
-  else
-    hipLaunchKernelGGL(topk_class_out_kernel<false>, dim3(groups), dim3(256), 0, st, ck, ci, num_classes, K, width,
-                       out_scores, out_inds, out_clses, out_ys, out_xs);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  CandLists c;  // no peak test, no sigmoid
+  if (int rc = candidate_lists<false>(scores, batch, num_classes, height, width, K, 0, workspace, st, &c)) return rc;
+  const dim3 groups(per_channel ? batch * num_classes : batch);
+  return with_bool(per_channel != 0, [&](auto PERCH) {
+    if (c.band_merge)
+      return launch({groups, dim3(1024), st}, topk_band_merge_kernel<PERCH.value>, c.key, c.idx, num_classes, c.lists,
+                    K, width, out_scores, out_inds, out_clses, out_ys, out_xs);
+    return launch({groups, dim3(256), st}, topk_class_out_kernel<PERCH.value>, c.key, c.idx, num_classes, K, width,
+                  out_scores, out_inds, out_clses, out_ys, out_xs);
+  });
 }
 
 extern "C" int sfa_gather_feat(const void* feat, int batch, int64_t n, int dim, int64_t stride_n, int64_t stride_d,
@@ -1033,15 +987,10 @@ extern "C" int sfa_gather_feat(const void* feat, int batch, int64_t n, int dim, 
   const int64_t total = (int64_t)batch * K * dim;
   if (total == 0) return SFA_OK;
   SFA_CHECK_ARG(feat && ind && out, "gather_feat: null argument");
-  const dim3 g((unsigned)((total + 255) / 256)), b(256);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const LaunchCfg cfg{dim3((unsigned)((total + 255) / 256)), dim3(256), reinterpret_cast<hipStream_t>(stream)};
   if (elem_bytes == 4)
-    hipLaunchKernelGGL(gather_feat_kernel<unsigned>, g, b, 0, st, reinterpret_cast<const unsigned*>(feat), n, dim,
-                       stride_n, stride_d, ind, K, total, reinterpret_cast<unsigned*>(out));
-  else
-    hipLaunchKernelGGL(gather_feat_kernel<unsigned long long>, g, b, 0, st,
-                       reinterpret_cast<const unsigned long long*>(feat), n, dim, stride_n, stride_d, ind, K, total,
-                       reinterpret_cast<unsigned long long*>(out));
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+    return launch(cfg, gather_feat_kernel<unsigned>, reinterpret_cast<const unsigned*>(feat), n, dim, stride_n,
+                  stride_d, ind, K, total, reinterpret_cast<unsigned*>(out));
+  return launch(cfg, gather_feat_kernel<unsigned long long>, reinterpret_cast<const unsigned long long*>(feat), n, dim,
+                stride_n, stride_d, ind, K, total, reinterpret_cast<unsigned long long*>(out));
 }

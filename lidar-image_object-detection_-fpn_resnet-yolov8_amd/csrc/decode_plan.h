@@ -64,6 +64,23 @@ inline bool tile_plan(int H, int W, int* R_out, int* TC_out, int* NY_out, int* N
 
 inline size_t plan_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Workspace of the band and class forms: `lists` sorted K-lists per (frame, class) (the S bands, or
+// 1), keys at 0, then indices; both parts 256-B aligned.
+struct ListLayout {
+  size_t idx, total;  // byte offsets
+};
+inline ListLayout list_layout(int B, int C, int lists, int K) {
+  const size_t n = (size_t)B * C * lists * K;
+  ListLayout l;
+  l.idx = plan_align_up(n * sizeof(unsigned), 256);
+  l.total = l.idx + plan_align_up(n * sizeof(int), 256);
+  return l;
+}
+// band_plan gives S <= 16 (its largest candidate), so room for 16 lists per class holds either form:
+// the entries check the workspace against this size once, and no form needs a check of its own.
+constexpr int kBandMaxS = 16;
+inline size_t list_workspace_bytes(int B, int C, int K) { return list_layout(B, C, kBandMaxS, K).total; }
+
 // Workspace of the tiled form: NT = NY * NX sorted K-lists per (frame, class) (keys, then
 // indices), then one merged K-list per (frame, class) (keys, then indices); every part 256-B aligned.
 struct TiledLayout {

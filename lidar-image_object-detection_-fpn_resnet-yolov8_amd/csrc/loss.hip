@@ -20,7 +20,7 @@
 // rounds like numpy's.
 #include <math.h>
 
-#include "common.h"
+#include "dispatch.h"
 
 #pragma clang fp contract(off)
 
@@ -624,17 +624,45 @@ extern "C" int sfa_build_targets(const float* labels, const int64_t* frame_offse
   const int64_t cells = (int64_t)g.C * g.H * g.W;
   const int per_block = kTgtThreads * kTgtCellsPerThread;
   const dim3 grid((unsigned)((cells + per_block - 1) / per_block), (unsigned)batch);
-  hipLaunchKernelGGL(build_targets_kernel, grid, dim3(kTgtThreads), 0, reinterpret_cast<hipStream_t>(stream), labels,
-                     frame_offsets, total_rows, g, hm_cen, cen_offset, direction, z_coor, dim, indices_center,
-                     obj_mask, status);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({grid, dim3(kTgtThreads), reinterpret_cast<hipStream_t>(stream)}, build_targets_kernel, labels,
+                frame_offsets, total_rows, g, hm_cen, cen_offset, direction, z_coor, dim, indices_center, obj_mask,
+                status);
 }
 
 extern "C" size_t sfa_compute_loss_workspace_size(int batch, int num_classes, int height, int width,
                                                   int max_objects) {
   LossPlan p;
   return loss_plan(batch, num_classes, height, width, max_objects, &p) ? p.bytes : 0;
+}
+
+// The head maps, targets and slot rows both loss entries take.
+struct LossInputs {
+  const float *hm_cen, *cen_offset, *direction, *z_coor, *dim;
+  const float *t_hm_cen, *t_cen_offset, *t_direction, *t_z_coor, *t_dim;
+  const int64_t* indices_center;
+  const uint8_t* obj_mask;
+  LossMaps maps() const {
+    return {cen_offset, direction, z_coor, dim, t_cen_offset, t_direction, t_z_coor, t_dim, indices_center, obj_mask};
+  }
+};
+
+// The checks both entries share: the shape (plan_ok: the entry's plan accepted it), the buffers
+// (outputs_ok: the entry's own ones) and the workspace against the plan's size.
+static int loss_check(const char* who, bool plan_ok, const LossInputs& in, bool outputs_ok, int batch, int num_classes,
+                      int height, int width, int max_objects, const void* workspace, size_t workspace_bytes,
+                      size_t need) {
+  SFA_CHECK_ARG(plan_ok, "%s: batch %d (1..64), classes %d (1..%d), map %d x %d, max_objects %d (1..%d)", who, batch,
+                num_classes, kMaxClasses, height, width, max_objects, kMaxObjects);
+  SFA_CHECK_ARG(in.hm_cen && in.cen_offset && in.direction && in.z_coor && in.dim && in.t_hm_cen && in.t_cen_offset &&
+                    in.t_direction && in.t_z_coor && in.t_dim && in.indices_center && in.obj_mask && outputs_ok &&
+                    workspace,
+                "%s: null buffer", who);
+  SFA_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "%s: workspace not 8-byte aligned", who);
+  if (workspace_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    return SFA_E_WORKSPACE;
+  }
+  return SFA_OK;
 }
 
 extern "C" int sfa_compute_loss(const float* hm_cen, const float* cen_offset, const float* direction,
@@ -644,36 +672,27 @@ extern "C" int sfa_compute_loss(const float* hm_cen, const float* cen_offset, co
                                 int num_classes, int height, int width, int max_objects, int apply_sigmoid,
                                 float* loss, double* sums, uint32_t* status, void* workspace, size_t workspace_bytes,
                                 void* stream) {
-  LossPlan p;
-  SFA_CHECK_ARG(loss_plan(batch, num_classes, height, width, max_objects, &p),
-                "compute_loss: batch %d (1..64), classes %d (1..%d), map %d x %d, max_objects %d (1..%d)", batch,
-                num_classes, kMaxClasses, height, width, max_objects, kMaxObjects);
-  SFA_CHECK_ARG(hm_cen && cen_offset && direction && z_coor && dim && t_hm_cen && t_cen_offset && t_direction &&
-                    t_z_coor && t_dim && indices_center && obj_mask && loss && sums && status && workspace,
-                "compute_loss: null buffer");
-  SFA_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "compute_loss: workspace not 8-byte aligned");
-  if (workspace_bytes < p.bytes) {
-    set_error("compute_loss: workspace %zu < %zu bytes", workspace_bytes, p.bytes);
-    return SFA_E_WORKSPACE;
-  }
+  const LossInputs in{hm_cen,   cen_offset,   direction,   z_coor,   dim,   //
+                      t_hm_cen, t_cen_offset, t_direction, t_z_coor, t_dim, indices_center, obj_mask};
+  LossPlan p{};
+  const bool plan_ok = loss_plan(batch, num_classes, height, width, max_objects, &p);
+  if (int rc = loss_check("compute_loss", plan_ok, in, loss && sums && status, batch, num_classes, height, width,
+                          max_objects, workspace, workspace_bytes, p.bytes))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   double* focal = reinterpret_cast<double*>(workspace);
   double* rows = reinterpret_cast<double*>(static_cast<char*>(workspace) + p.rows_offset);
+  const int sig = apply_sigmoid ? 1 : 0;
   const bool vec = (reinterpret_cast<uintptr_t>(hm_cen) | reinterpret_cast<uintptr_t>(t_hm_cen)) % 16 == 0;
-  if (vec)
-    hipLaunchKernelGGL(focal_partial_kernel<true>, dim3(p.n_focal), dim3(kFocalThreads), 0, st, hm_cen, t_hm_cen,
-                       p.cells, apply_sigmoid ? 1 : 0, focal);
-  else
-    hipLaunchKernelGGL(focal_partial_kernel<false>, dim3(p.n_focal), dim3(kFocalThreads), 0, st, hm_cen, t_hm_cen,
-                       p.cells, apply_sigmoid ? 1 : 0, focal);
-  SFA_LAUNCH_CHECK();
-  LossMaps m{cen_offset, direction, z_coor, dim, t_cen_offset, t_direction, t_z_coor, t_dim, indices_center, obj_mask};
-  hipLaunchKernelGGL(rows_partial_kernel, dim3(p.n_rows), dim3(kRowThreads), 0, st, m, batch, max_objects,
-                     (int64_t)height * width, apply_sigmoid ? 1 : 0, exp(1.5 / 0.5) - 1, rows);
-  SFA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_fold_kernel, dim3(1), dim3(256), 0, st, focal, p.n_focal, rows, p.n_rows, loss, sums, status);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  if (int rc = with_bool(vec, [&](auto VEC) {
+        return launch({dim3(p.n_focal), dim3(kFocalThreads), st}, focal_partial_kernel<VEC.value>, hm_cen, t_hm_cen,
+                      p.cells, sig, focal);
+      }))
+    return rc;
+  if (int rc = launch({dim3(p.n_rows), dim3(kRowThreads), st}, rows_partial_kernel, in.maps(), batch, max_objects,
+                      (int64_t)height * width, sig, exp(1.5 / 0.5) - 1, rows))
+    return rc;
+  return launch({dim3(1), dim3(256), st}, loss_fold_kernel, focal, p.n_focal, rows, p.n_rows, loss, sums, status);
 }
 
 extern "C" size_t sfa_compute_loss_grad_workspace_size(int batch, int num_classes, int height, int width,
@@ -690,48 +709,35 @@ extern "C" int sfa_compute_loss_grad(const float* hm_cen, const float* cen_offse
                                      int apply_sigmoid, float* g_hm_cen, float* g_cen_offset, float* g_direction,
                                      float* g_z_coor, float* g_dim, uint32_t* status, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-  GradPlan p;
-  SFA_CHECK_ARG(grad_plan(batch, num_classes, height, width, max_objects, &p),
-                "compute_loss_grad: batch %d (1..64), classes %d (1..%d), map %d x %d, max_objects %d (1..%d)", batch,
-                num_classes, kMaxClasses, height, width, max_objects, kMaxObjects);
-  SFA_CHECK_ARG(hm_cen && cen_offset && direction && z_coor && dim && t_hm_cen && t_cen_offset && t_direction &&
-                    t_z_coor && t_dim && indices_center && obj_mask && g_hm_cen && g_cen_offset && g_direction &&
-                    g_z_coor && g_dim && status && workspace,
-                "compute_loss_grad: null buffer");
-  SFA_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "compute_loss_grad: workspace not 8-byte aligned");
-  if (workspace_bytes < p.bytes) {
-    set_error("compute_loss_grad: workspace %zu < %zu bytes", workspace_bytes, p.bytes);
-    return SFA_E_WORKSPACE;
-  }
+  const LossInputs in{hm_cen,   cen_offset,   direction,   z_coor,   dim,   //
+                      t_hm_cen, t_cen_offset, t_direction, t_z_coor, t_dim, indices_center, obj_mask};
+  GradPlan p{};
+  const bool plan_ok = grad_plan(batch, num_classes, height, width, max_objects, &p);
+  if (int rc = loss_check("compute_loss_grad", plan_ok, in,
+                          g_hm_cen && g_cen_offset && g_direction && g_z_coor && g_dim && status, batch, num_classes,
+                          height, width, max_objects, workspace, workspace_bytes, p.bytes))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   double* scal = reinterpret_cast<double*>(workspace);
   uint32_t* counts = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + kGradScalarBytes);
   const int HW = height * width;
-  if (reinterpret_cast<uintptr_t>(t_hm_cen) % 16 == 0)
-    hipLaunchKernelGGL(grad_count_kernel<true>, dim3(p.n_counts), dim3(kFocalThreads), 0, st, t_hm_cen, p.cells,
-                       counts);
-  else
-    hipLaunchKernelGGL(grad_count_kernel<false>, dim3(p.n_counts), dim3(kFocalThreads), 0, st, t_hm_cen, p.cells,
-                       counts);
-  SFA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(grad_fold_kernel, dim3(1), dim3(256), 0, st, counts, p.n_counts, indices_center, obj_mask,
-                     batch * max_objects, (int64_t)HW, scal, status);
-  SFA_LAUNCH_CHECK();
-  LossMaps m{cen_offset, direction, z_coor, dim, t_cen_offset, t_direction, t_z_coor, t_dim, indices_center, obj_mask};
-  GradMaps g{g_hm_cen, g_cen_offset, g_direction, g_z_coor, g_dim};
+  if (int rc = with_bool(reinterpret_cast<uintptr_t>(t_hm_cen) % 16 == 0, [&](auto VEC) {
+        return launch({dim3(p.n_counts), dim3(kFocalThreads), st}, grad_count_kernel<VEC.value>, t_hm_cen, p.cells,
+                      counts);
+      }))
+    return rc;
+  if (int rc = launch({dim3(1), dim3(256), st}, grad_fold_kernel, counts, p.n_counts, indices_center, obj_mask,
+                      batch * max_objects, (int64_t)HW, scal, status))
+    return rc;
+  const GradMaps g{g_hm_cen, g_cen_offset, g_direction, g_z_coor, g_dim};
   // 128-bit loads and stores need every channel plane 16-byte aligned: the bases and H*W % 4 == 0
   const uintptr_t bases = reinterpret_cast<uintptr_t>(hm_cen) | reinterpret_cast<uintptr_t>(t_hm_cen) |
                           reinterpret_cast<uintptr_t>(g_hm_cen) | reinterpret_cast<uintptr_t>(g_cen_offset) |
                           reinterpret_cast<uintptr_t>(g_direction) | reinterpret_cast<uintptr_t>(g_z_coor) |
                           reinterpret_cast<uintptr_t>(g_dim);
   const dim3 grid((unsigned)((HW + kGradTile - 1) / kGradTile), (unsigned)batch);
-  const double bb = exp(1.5 / 0.5) - 1;
-  if (bases % 16 == 0 && HW % 4 == 0)
-    hipLaunchKernelGGL(loss_grad_kernel<true>, grid, dim3(kGradThreads), 0, st, hm_cen, t_hm_cen, m, g, num_classes,
-                       max_objects, HW, apply_sigmoid ? 1 : 0, bb, scal);
-  else
-    hipLaunchKernelGGL(loss_grad_kernel<false>, grid, dim3(kGradThreads), 0, st, hm_cen, t_hm_cen, m, g, num_classes,
-                       max_objects, HW, apply_sigmoid ? 1 : 0, bb, scal);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return with_bool(bases % 16 == 0 && HW % 4 == 0, [&](auto VEC) {
+    return launch({grid, dim3(kGradThreads), st}, loss_grad_kernel<VEC.value>, hm_cen, t_hm_cen, in.maps(), g,
+                  num_classes, max_objects, HW, apply_sigmoid ? 1 : 0, exp(1.5 / 0.5) - 1, scal);
+  });
 }

@@ -157,10 +157,14 @@ def test_binned_path_equals_atomic_path(gpu, flip):
 
 
 def test_oversized_frame_uses_atomic_path(gpu):
-    """A batch with more points than the scratch holds as records (here 1 frame of 400,000 points,
-    capacity ~277 k) takes the global-atomic path: still bit-exact, scratch still clean."""
+    """A batch that fits neither record form takes the global-atomic path un-forced: still bit-exact,
+    scratch still clean. One frame of 600,000 points at capacity 1 (4,435,968 B after the zero
+    areas): the blocked path needs 586 regions x 1024 x 8 B = 4,800,512 B of records alone, and the
+    binned path holds (4,435,968 - 1,536) / 16 = 277,152 records. (400,000 points, this test's
+    earlier size, are 391 regions: 3,203,072 + 237,728 B of table + 1,536 B of counters fit, so
+    that call took the blocked path.)"""
     rng = np.random.default_rng(13)
-    n = 400_000
+    n = 600_000
     pts = np.zeros((n, 4), np.float32)
     pts[:, 0] = rng.uniform(-1, 51, n)
     pts[:, 1] = rng.uniform(-26, 26, n)
@@ -168,6 +172,7 @@ def test_oversized_frame_uses_atomic_path(gpu):
     pts[:, 3] = rng.uniform(0, 1, n)
     vox = runtime.BevVoxelizer(gpu, 1)
     assert n * 16 > vox.scratch.numel() // 2  # the record region: the half after the atomic cells
+    assert -(-n // 1024) * 1024 * 8 > vox.scratch.numel() // 2  # nor do the blocked path's regions fit
     got = vox(torch.from_numpy(pts).to(gpu), [0, n], gc.BOUNDARY, layout=_lib.BEV_NCHW3_F64).cpu().numpy()[0]
     assert _scratch_clean(vox)
     exp = bev_oracle.makeBEVMap(bev_oracle.get_filtered_lidar(pts, gc.BOUNDARY), gc.BOUNDARY)
@@ -178,7 +183,9 @@ def test_scratch_shared_across_batch_sizes(gpu):
     """One scratch (sized for 8 frames, as runtime.voxelizer() shares it) serves calls of every
     batch size and path in any order: the layout follows the scratch's capacity, not the call's
     batch, so a small call's records never land in a later larger call's zero areas (ADVICE r03:
-    B = 1 blocked, then B = 4 atomic / B = 2 binned / a frame over 1 M points)."""
+    B = 1 blocked, then B = 4 atomic / B = 2 binned / a frame over 1 M points). The `huge` batch
+    takes the binned path: 1,200,000 points are 1172 regions of one frame, above the blocked
+    path's 1024, and its 1.46 M records are within the ~2.2 M that capacity 8 holds."""
     from sfa_hip import synthetic
     rng = np.random.default_rng(17)
     huge = np.zeros((1_200_000, 4), np.float32)  # > 1024 regions of one frame: not the blocked path

@@ -123,6 +123,7 @@ def test_decode_without_offset(gpu):
     (2, 16, 24, 24, 256),    # C * K = 4096: one band per class
     (1, 3, 3, 4100, 40),     # a band tile wider than LDS allows: the one-block-per-class kernels
     (2, 3, 152, 152, 50),    # production shape with quantised values: ties across band cuts
+    (1, 3, 193, 192, 50),    # just above the band kernels' largest map: the tiled form, three classes
 ])
 def test_decode_band_split_shapes(gpu, B, C, H, W, K):
     """The band-parallel decode (S row bands per class map, sorted band lists merged per frame)
@@ -192,6 +193,32 @@ def test_topk_helpers_match_oracle(gpu, shape, K, ties):
             np.testing.assert_array_equal(cxs[b, c], (i % W).astype(np.float32))
     with pytest.raises(RuntimeError):
         _topk(_t(s, gpu), K=H * W + 1)
+
+
+@pytest.mark.parametrize("shape,K", [((1, 3, 3, 4100), 40),    # one block per class: no band tile holds a row
+                                     ((3, 3, 37, 29), 50),     # bands
+                                     ((1, 3, 193, 192), 50)])  # tiles
+@pytest.mark.parametrize("per_channel", [False, True])
+def test_topk_three_forms(gpu, shape, K, per_channel):
+    """sfa_topk behind the candidate-list stage it shares with sfa_decode (whose three forms
+    test_decode_band_split_shapes meets at these shapes): class, band and tiled lists, merged over
+    the classes or kept per class, bit-exact against the oracle on a map with heavy ties."""
+    B, C, H, W = shape
+    s = _scores(*shape, seed=sum(shape) + K, ties=True)
+    got = [t.cpu().numpy() for t in runtime.topk(_t(s, gpu), K, per_channel=per_channel)]
+    if not per_channel:
+        for g, e in zip(got, decode_oracle.topk(s, K)):
+            np.testing.assert_array_equal(g, e)
+        return
+    csc, cind, cys, cxs = got
+    flat = s.reshape(B, C, H * W)
+    for b in range(B):
+        for c in range(C):
+            v, i = decode_oracle._topk_desc(flat[b, c], K)
+            np.testing.assert_array_equal(csc[b, c], v)
+            np.testing.assert_array_equal(cind[b, c], i)
+            np.testing.assert_array_equal(cys[b, c], (i // W).astype(np.float32))
+            np.testing.assert_array_equal(cxs[b, c], (i % W).astype(np.float32))
 
 
 def test_gather_helpers_bit_exact(gpu):
