@@ -678,6 +678,46 @@ int sfa_compute_loss_grad(const float* hm_cen, const float* cen_offset, const fl
                           float* g_z_coor, float* g_dim, uint32_t* status, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------- apply_kfpn as an operator: forward + gradient --
+ * For a detector built in torch that trains against sfa_compute_loss_grad: the last operator between
+ * the 15 per-level head outputs and the five head maps.  sfa_model_forward keeps its own fused
+ * combine; these two entries take the user-facing layouts and cover every head in one launch each.
+ *
+ * sfa_kfpn_combine replaces models/fpn_resnet.py:248-254 apply_kfpn for all heads, with the nearest
+ * resize of level 0 (:229-230) read in place.
+ *   levels       HOST array [3 * num_heads] of DEVICE f32 pointers, head-major: head j's levels 0, 1, 2 at
+ *                3 j, 3 j + 1, 3 j + 2.  Levels 1 and 2 are NCHW (B, channels[j], h, w), contiguous;
+ *                level 0 too when level0_half == 0, and (B, channels[j], h / 2, w / 2) when
+ *                level0_half == 1, read by nearest resize (src = dst / 2: F.interpolate(size=(h, w)) at an
+ *                exact 0.5 scale; h and w even)
+ *   channels     HOST int [num_heads], each > 0; num_heads 1 .. SFA_MAX_HEADS
+ *   out          HOST array [num_heads] of DEVICE f32 (B, channels[j], h, w)
+ *   weights      NULL, or HOST array [num_heads] of DEVICE f32 (B, channels[j], h, w, 3): the softmax
+ *                over the three levels, apply_kfpn's second return value
+ * Per element, in float32 without contraction and in sfa_model_forward's order: mx = max(v0, v1, v2),
+ * e_i = expf(v_i - mx), s = e0 + e1 + e2, w_i = e_i / s, out = v0 w0 + v1 w1 + v2 w2: given the same level
+ * values the result is bit-identical to sfa_model_forward's head maps.
+ *
+ * sfa_kfpn_combine_grad: the gradient of a scalar `total` at the 3 * num_heads level maps given
+ * grad_out[j] = d total / d out[j] (DEVICE f32, out's shape):
+ *   d total / d v_j = g w_j (1 + v_j - out),  w = softmax(v), out = sum_i v_i w_i
+ * evaluated in float64 from the float32 operands and rounded to float32 once.  grad_levels: HOST array
+ * [3 * num_heads] of DEVICE f32 maps of the levels' shapes.  Under level0_half a level-0 cell receives
+ * the sum of its four children's terms, added in float64 in the order (0,0), (0,1), (1,0), (1,1) (row,
+ * column) by the thread that owns the cell: no atomics, nothing needs zeroing, every byte of every
+ * gradient map is written, runs are bit-identical.
+ *
+ * Both: one launch on the caller's stream, no workspace, no allocation, no synchronisation
+ * (graph-capturable).  128-bit loads and stores when w % 4 == 0 and every DEVICE pointer is 16-byte
+ * aligned, scalar ones otherwise, with the same bits.  SFA_E_INVALID before any launch: a NULL array or
+ * entry, num_heads outside 1 .. SFA_MAX_HEADS, B, h, w or a channel count <= 0, level0_half not 0 / 1, odd
+ * h or w under level0_half, B or the channel sum above 65535, h w above 2^30. */
+int sfa_kfpn_combine(const float* const* levels, const int* channels, int num_heads, int B, int h, int w,
+                     int level0_half, float* const* out, float* const* weights, void* stream);
+int sfa_kfpn_combine_grad(const float* const* levels, const int* channels, int num_heads, int B, int h,
+                          int w, int level0_half, const float* const* grad_out,
+                          float* const* grad_levels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from sfa_hip import _lib
 from sfa_hip import dropin as _dropin
-from sfa_hip.runtime import KfpnEngine, pack_state_dict
+from sfa_hip.runtime import KfpnEngine, kfpn_heads, pack_state_dict
 
 BN_MOMENTUM = 0.1
 
@@ -202,7 +202,15 @@ class PoseResNet(nn.Module):
             self.kfpn_weights[name] = F.softmax(torch.stack(lv, dim=-1), dim=-1)
 
     def apply_kfpn(self, outs):
-        raise RuntimeError("apply_kfpn runs fused inside the HIP forward (kfpn_combine kernel)")
+        """fpn_resnet.py:248-254 for one head: ``outs`` is a list of three equal-shaped (B, c, h, w) GPU tensors;
+        returns (sum over the levels of v * softmax(v), the softmax weights (B, c, h, w, 3)).  One HIP launch
+        (sfa_kfpn_combine), differentiable through sfa_kfpn_combine_grad; the weights carry no gradient (the
+        reference only ever detaches them).  The model's own forward keeps its fused combine."""
+        outs = list(outs)
+        if len(outs) != 3:
+            raise ValueError(f"apply_kfpn: {len(outs)} levels, expected 3")
+        ret, weights = kfpn_heads({"head": outs}, level0_half=False, return_weights=True)
+        return ret["head"], weights["head"]
 
     def get_visualization_data(self):
         return {"backbone_features": self.backbone_features, "kfpn_features": self.kfpn_features,

@@ -222,6 +222,11 @@ _PROTOS["sfa_compute_loss_workspace_size"] = (_c_size, [_c_int, _c_int, _c_int, 
 _PROTOS["sfa_compute_loss"] = (_c_int, [_vp] * 12 + [_c_int] * 6 + [_vp, _vp, _vp, _vp, _c_size, _vp])
 _PROTOS["sfa_compute_loss_grad_workspace_size"] = (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int])
 _PROTOS["sfa_compute_loss_grad"] = (_c_int, [_vp] * 12 + [_c_int] * 6 + [_vp] * 5 + [_vp, _vp, _c_size, _vp])
+# apply_kfpn as an operator: forward + gradient (host arrays of device pointers, include/sfa_hip.h)
+_PROTOS["sfa_kfpn_combine"] = (_c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_c_int)] + [_c_int] * 5
+                               + [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp])
+_PROTOS["sfa_kfpn_combine_grad"] = (_c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_c_int)] + [_c_int] * 5
+                                    + [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp])
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
 _lib = None

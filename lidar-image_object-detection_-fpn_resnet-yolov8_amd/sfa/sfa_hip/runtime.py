@@ -1359,3 +1359,138 @@ class LossEvaluator:
         if verify and int(self.grad_status.item()) & _lib.STATUS_INDEX_OUT_OF_MAP:
             raise IndexError(f"Compute_Loss: an indices_center entry under a set obj_mask is outside [0, {H * W})")
         return dict(zip(DEFAULT_HEADS, grads))
+
+
+# ------------------------------------------------- apply_kfpn as an operator: forward + gradient
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _kfpn_operands(levels_by_head: dict, level0_half: bool, what: str):
+    """Checks {head: [level 0, level 1, level 2]}: (names, flat contiguous tensors, channels, (B, h, w))."""
+    if not isinstance(levels_by_head, dict) or not 1 <= len(levels_by_head) <= _lib.SFA_MAX_HEADS:
+        raise ValueError(f"{what}: a dict of 1..{_lib.SFA_MAX_HEADS} heads is needed")
+    names, flat, channels, shape, dev = list(levels_by_head), [], [], None, None
+    for name in names:
+        lv = list(levels_by_head[name])
+        if len(lv) != 3:
+            raise ValueError(f"{what}: head {name!r} has {len(lv)} levels, expected 3")
+        lv = [_require_gpu_tensor(t, f"{what} levels[{name!r}][{i}]") for i, t in enumerate(lv)]
+        if lv[1].dim() != 4:
+            raise ValueError(f"{what}: head {name!r} level 1 is {tuple(lv[1].shape)}, expected (B, c, h, w)")
+        B, c, h, w = (int(v) for v in lv[1].shape)
+        if shape is None:
+            shape, dev = (B, h, w), lv[1].device
+        if level0_half and (h % 2 or w % 2):
+            raise ValueError(f"{what}: level0_half needs even h and w, got {h} x {w}")
+        want = [(B, c, h // 2, w // 2) if level0_half else (B, c, h, w), (B, c, h, w), (B, c, h, w)]
+        for i, t in enumerate(lv):
+            if tuple(t.shape) != want[i] or (B, h, w) != shape or t.device != dev:
+                raise ValueError(f"{what}: head {name!r} level {i} is {tuple(t.shape)} on {t.device}, expected "
+                                 f"{want[i]} (B, h, w = {shape}) on {dev}")
+        flat += lv
+        channels.append(c)
+    return names, flat, channels, shape
+
+
+def _kfpn_buffers(given, names, shapes, like, what):
+    """The output tensors of one entry: fresh ones, or the caller's (contiguous, of the right shape)."""
+    if given is None:
+        return [torch.empty(s, dtype=torch.float32, device=like.device) for s in shapes]
+    out = []
+    for name, s in zip(names, shapes):
+        t = _require_gpu_tensor(given[name], f"{what}[{name!r}]")
+        if tuple(t.shape) != tuple(s) or t.data_ptr() != given[name].data_ptr():
+            raise ValueError(f"{what}[{name!r}]: a contiguous tensor of shape {tuple(s)} is needed")
+        out.append(t)
+    return out
+
+
+def kfpn_combine(levels_by_head: dict, level0_half: bool = False, return_weights: bool = False, out: dict = None,
+                 weights: dict = None):
+    """apply_kfpn (models/fpn_resnet.py:248-254) for every head of ``levels_by_head`` = {head: [level 0, level 1,
+    level 2]} in one launch (sfa_kfpn_combine).  Levels 1 and 2 are float32 GPU tensors (B, c, h, w); level 0 too,
+    or (B, c, h / 2, w / 2) with ``level0_half`` (the nearest resize of :229-230 is read in place).  Returns
+    {head: (B, c, h, w)}, with ``return_weights`` also {head: (B, c, h, w, 3)}, the softmax over the levels.  Not
+    differentiable (see :func:`kfpn_heads`); ``out`` / ``weights`` (dicts of contiguous tensors) receive the
+    results instead of fresh tensors, and the call then only enqueues its launch (graph-capturable)."""
+    names, flat, channels, (B, h, w) = _kfpn_operands(levels_by_head, level0_half, "kfpn_combine")
+    shapes = [(B, c, h, w) for c in channels]
+    outs = _kfpn_buffers(out, names, shapes, flat[0], "kfpn_combine out")
+    wts = None
+    if return_weights or weights is not None:
+        wts = _kfpn_buffers(weights, names, [s + (3,) for s in shapes], flat[0], "kfpn_combine weights")
+    with torch.cuda.device(flat[0].device):
+        check(lib().sfa_kfpn_combine(_ptr_array(flat), (ctypes.c_int * len(channels))(*channels), len(names), B, h, w,
+                                     1 if level0_half else 0, _ptr_array(outs), _ptr_array(wts) if wts else None,
+                                     _lib.stream_ptr(flat[0].device)), "sfa_kfpn_combine")
+    res = dict(zip(names, outs))
+    return (res, dict(zip(names, wts))) if wts is not None else res
+
+
+def kfpn_combine_grad(levels_by_head: dict, grad_out_by_head: dict, level0_half: bool = False, out: dict = None):
+    """The gradient of apply_kfpn at the level maps (sfa_kfpn_combine_grad): ``grad_out_by_head`` = {head:
+    d total / d out, (B, c, h, w)}; returns {head: [d total / d level 0, 1, 2]} of the levels' shapes, every
+    element written by the call (float64 from the float32 operands, rounded once; under ``level0_half`` a level-0
+    cell gathers its four children in a fixed order, so runs are bit-identical).  ``out`` ({head: [three
+    contiguous tensors]}) receives the maps instead of fresh tensors; the call then only enqueues its launch."""
+    names, flat, channels, (B, h, w) = _kfpn_operands(levels_by_head, level0_half, "kfpn_combine_grad")
+    gouts = []
+    for name, c in zip(names, channels):
+        g = _require_gpu_tensor(grad_out_by_head[name], f"kfpn_combine_grad grad_out[{name!r}]")
+        if tuple(g.shape) != (B, c, h, w):
+            raise ValueError(f"kfpn_combine_grad grad_out[{name!r}]: {tuple(g.shape)} != {(B, c, h, w)}")
+        gouts.append(g)
+    if out is None:
+        glev = [torch.empty_like(t) for t in flat]
+    else:
+        glev = []
+        for name, lv in zip(names, (flat[i:i + 3] for i in range(0, len(flat), 3))):
+            glev += _kfpn_buffers(dict(enumerate(out[name])), range(3), [t.shape for t in lv], lv[0],
+                                  f"kfpn_combine_grad out[{name!r}]")
+    with torch.cuda.device(flat[0].device):
+        check(lib().sfa_kfpn_combine_grad(_ptr_array(flat), (ctypes.c_int * len(channels))(*channels), len(names), B, h,
+                                          w, 1 if level0_half else 0, _ptr_array(gouts), _ptr_array(glev),
+                                          _lib.stream_ptr(flat[0].device)), "sfa_kfpn_combine_grad")
+    return {name: glev[3 * j:3 * j + 3] for j, name in enumerate(names)}
+
+
+class _KfpnCombine(torch.autograd.Function):
+    """apply_kfpn of all heads with its gradient, both from the HIP library: forward runs sfa_kfpn_combine and
+    saves the level tensors, backward runs sfa_kfpn_combine_grad on them.  The outputs come first, then (when
+    wanted) the weights, which are marked non-differentiable (the reference only ever detaches them)."""
+
+    @staticmethod
+    def forward(ctx, names, level0_half, want_weights, *levels):
+        by_head = {n: levels[3 * j:3 * j + 3] for j, n in enumerate(names)}
+        res = kfpn_combine(by_head, level0_half, return_weights=want_weights)
+        ctx.names, ctx.half = tuple(names), bool(level0_half)
+        ctx.save_for_backward(*levels)
+        if not want_weights:
+            return tuple(res[n] for n in names)
+        wts = tuple(res[1][n] for n in names)
+        ctx.mark_non_differentiable(*wts)
+        return tuple(res[0][n] for n in names) + wts
+
+    @staticmethod
+    def backward(ctx, *grads):
+        levels, n = ctx.saved_tensors, len(ctx.names)
+        by_head = {name: levels[3 * j:3 * j + 3] for j, name in enumerate(ctx.names)}
+        g = kfpn_combine_grad(by_head, dict(zip(ctx.names, grads[:n])), ctx.half)
+        flat = [t for name in ctx.names for t in g[name]]
+        return (None, None, None) + tuple(t if need else None for t, need in zip(flat, ctx.needs_input_grad[3:]))
+
+
+def kfpn_heads(levels_by_head: dict, level0_half: bool = True, return_weights: bool = False):
+    """The differentiable all-heads form: what the loop of models/fpn_resnet.py:219-244 leaves in ``ret`` from the
+    15 per-level head outputs, {head: [level 0, level 1, level 2]}, in one launch; level 0 is taken at half
+    resolution as the head convolutions produce it (``level0_half=False``: already (B, c, h, w)).  Returns {head:
+    (B, c, h, w)} (with ``return_weights`` also the detached softmax weights per head); ``backward`` through the
+    result reaches the level tensors that require grad, again in one launch."""
+    names = list(levels_by_head)
+    flat = [t for n in names for t in levels_by_head[n]]
+    if len(flat) != 3 * len(names):
+        raise ValueError("kfpn_heads: every head needs its three levels")
+    res = _KfpnCombine.apply(tuple(names), bool(level0_half), bool(return_weights), *flat)
+    outs = dict(zip(names, res[:len(names)]))
+    return (outs, dict(zip(names, res[len(names):]))) if return_weights else outs

@@ -8,6 +8,7 @@ total_loss over the frames, one JSON line.
   --math fp16      also runs SFA_MATH_FP16 on the same frames and reports its loss next to fp16x3's
   --timing         median microseconds of target build + loss for 16 frames on a captured HIP graph
   --timing --grad  also targets + loss + gradient (sfa_compute_loss_grad) on one graph, then bench.py
+  --timing --grad --kfpn   also that graph with the KFPN gradient (sfa_kfpn_combine_grad) behind the loss gradient
 
 The loop is evaluation only (the gradient at the heads is only timed).  With a data set, the labels of a batch are read with the
 data set's own helpers (get_label, camera_to_lidar_box, filter_labels: a reference tree on sys.path or in
@@ -124,9 +125,10 @@ def evaluate(model, batches, args, device):
     return losses.avg, {k: v / max(frames, 1) for k, v in parts.items()}, frames
 
 
-def timing(device, args, frames=16, reps=50, grad=False):
-    """Median microseconds of sfa_build_targets + sfa_compute_loss (with ``grad`` also sfa_compute_loss_grad)
-    for ``frames`` frames, one HIP graph."""
+def timing(device, args, frames=16, reps=50, grad=False, kfpn=False):
+    """Median microseconds of sfa_build_targets + sfa_compute_loss (with ``grad`` also sfa_compute_loss_grad, with
+    ``kfpn`` also sfa_kfpn_combine_grad from the head gradients to the 15 per-level maps, level 0 at half
+    resolution) for ``frames`` frames, one HIP graph."""
     hm = args.input_size // 4
     labels, offsets = synthetic.synthetic_labels(frames, seed=args.seed)
     builder = runtime.TargetBuilder(device, runtime.DEFAULT_BOUNDARY, (hm, hm), 3, args.max_objects)
@@ -137,12 +139,20 @@ def timing(device, args, frames=16, reps=50, grad=False):
             for i, (h, c) in enumerate(runtime.DEFAULT_HEADS.items())}
     tg = builder.alloc(frames)
     grads = {h: torch.empty_like(t) for h, t in outs.items()}
+    if kfpn:
+        sizes = (hm // 2, hm, hm)  # level 0 at half resolution
+        levels = {h: [torch.from_numpy(synthetic.synthetic_logits((frames, c, n, n), args.seed, 80 + 3 * i + l)).to(device)
+                      for l, n in enumerate(sizes)]
+                  for i, (h, c) in enumerate(runtime.DEFAULT_HEADS.items())}
+        level_grads = {h: [torch.empty_like(t) for t in lv] for h, lv in levels.items()}
 
     def step():
         builder(d_labels, d_offsets, None, out=tg, verify=False)
         ev(outs, tg, apply_sigmoid=True, verify=False)
         if grad:
             ev.grad(outs, tg, apply_sigmoid=True, verify=False, out=grads)
+        if kfpn:
+            runtime.kfpn_combine_grad(levels, grads, level0_half=True, out=level_grads)
 
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -192,6 +202,8 @@ def main(argv=None):
     ap.add_argument("--timing", action="store_true")
     ap.add_argument("--grad", action="store_true",
                     help="with --timing: also time targets + loss + gradient on one graph, then run bench.py")
+    ap.add_argument("--kfpn", action="store_true",
+                    help="with --timing --grad: also time that graph with the KFPN gradient added (one run, no threshold)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gpu_idx", type=int, default=0)
     args = ap.parse_args(argv)
@@ -214,6 +226,8 @@ def main(argv=None):
         result["targets_plus_loss_graph"] = timing(device, args)
         if args.grad:
             result["targets_plus_loss_plus_grad_graph"] = timing(device, args, grad=True)
+            if args.kfpn:
+                result["targets_plus_loss_plus_grad_plus_kfpn_grad_graph"] = timing(device, args, grad=True, kfpn=True)
             result["bench"] = run_bench()
     print(json.dumps(result))
     return result
