@@ -718,6 +718,50 @@ int sfa_kfpn_combine_grad(const float* const* levels, const int* channels, int n
                           int w, int level0_half, const float* const* grad_out,
                           float* const* grad_levels, void* stream);
 
+/* ------------------------------------------- head parameter gradients (one KFPN level) --
+ * What total_loss.backward() leaves at the parameters of the level's heads, fpn{level}_{head}.0.weight,
+ * .0.bias, .2.weight, .2.bias (models/fpn_resnet.py:135-143 conv3x3 -> ReLU -> conv1x1; train.py:190-247),
+ * given g = d total / d y, the level's head outputs, as sfa_kfpn_combine_grad writes them.  With x the
+ * heads' input, A = conv3x3(x; W1) + b1, Hd = max(A, 0), y = W2 Hd + b2:
+ *   db2[c] = sum_{b,p} g[b,c,p]                    dW2[c,o] = sum_{b,p} g[b,c,p] Hd[b,p,o]
+ *   dA[b,p,o] = Hd[b,p,o] > 0 ? sum_c W2[c,o] g[b,c,p] : 0   (strict, torch's ReLU backward)
+ *   db1[o] = sum_{b,p} dA[b,p,o]
+ *   dW1[o,i,ky,kx] = sum_{b,y,x} dA[b,y,x,o] x[b,y+ky-1,x+kx-1,i], zero outside the map
+ * The gradient with respect to x is not formed (fine-tuning the heads on a frozen backbone needs none).
+ *   model, level   a SFA_BACKBONE_KFPN handle and its level 0, 1, 2: Cin = 256, 128, 64 and the level's head
+ *                  weights inside the handle (SFA_BACKBONE_DECONV: SFA_E_UNSUPPORTED)
+ *   x              DEVICE f32 (B, h, w, Cin) NHWC, 16-byte aligned: SFA_BUF_UP_LEVEL2 / 3 / 4 after a forward,
+ *                  or any caller buffer; h, w any positive sizes
+ *   grad_levels    HOST array [num_heads] of DEVICE f32 (B, c_j, h, w) NCHW, forward head order
+ *   grad_w1/b1/w2/b2  HOST arrays [num_heads] of DEVICE f32 (64, Cin, 3, 3), (64), (c_j, 64, 1, 1), (c_j):
+ *                  torch's own layouts, every byte written by the call
+ *   hidden_out, dhidden_out   NULL, or DEVICE f32 (B, h, w, 64 num_heads), 16-byte aligned: Hd and dA as the
+ *                  kernels used them (head j's channels at 64 j ..); NULL keeps them in the workspace
+ *   max_chunk_pixels  0: the plan's choice (4096); > 0 caps the pixels of one split-K chunk of dW1.  A chunk
+ *                  is a run of whole rows of one frame, at least one row
+ *   workspace      DEVICE, 16-byte aligned, sfa_model_heads_grad_workspace_size(...) bytes (0 for arguments
+ *                  the entry refuses); smaller: SFA_E_WORKSPACE
+ * Arithmetic.  Hd is recomputed by the fp16x3 convolution (SFA_MATH_FP16X3, the forward's default arithmetic)
+ * whatever sfa_model_set_math says, with every frame of x scaled by its own max |x|, which the call measures: it
+ * may differ from the forward's own hidden activation in the last bits (another kernel, another summation order),
+ * and in the sign of a pre-activation that close to zero.  dA, dW2, db1, db2: float64 from the float32
+ * operands, rounded once (per-block partials added in block order).  dW1: v_mfma_f32_32x32x2_f32 with
+ * float32 accumulation inside one chunk, the chunks added in chunk order in float64, rounded once;
+ * sfa_model_heads_grad_chunk_pixels returns K_c, the largest chunk's pixel count, which is the K of the
+ * float32 part (0 for arguments the entry refuses).
+ * Eight launches (seven for an even head count) on the caller's stream; no allocation, no synchronisation, no memset, no floating-point
+ * atomics; two runs are bit-identical; graph-capturable.  Before any launch: SFA_E_INVALID for a NULL
+ * pointer, a level outside 0..2, non-positive B, h or w, negative max_chunk_pixels, a misaligned buffer, or
+ * B h w max(Cin, 64 num_heads) 4 >= 2^31 (32-bit byte offsets); SFA_E_WORKSPACE for a short workspace. */
+size_t sfa_model_heads_grad_workspace_size(const sfa_model* model, int level, int B, int h, int w,
+                                           int max_chunk_pixels);
+int sfa_model_heads_grad_chunk_pixels(const sfa_model* model, int level, int B, int h, int w,
+                                      int max_chunk_pixels);
+int sfa_model_heads_grad(const sfa_model* model, int level, const float* x, int B, int h, int w,
+                         const float* const* grad_levels, float* const* grad_w1, float* const* grad_b1,
+                         float* const* grad_w2, float* const* grad_b2, float* hidden_out, float* dhidden_out,
+                         int max_chunk_pixels, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -304,4 +304,17 @@ int launch_conv(const ConvArgs& a, int epilogue, int math, hipStream_t stream);
 // pass (stem_patch_kernel.h); SFA_E_UNSUPPORTED if the stem's shape does not tile 16 x 16.
 int launch_stem_patch(const ConvArgs& a, hipStream_t stream);
 
+// One KFPN level's head parameters inside a model handle's packed weights (model.hip), for
+// sfa_model_heads_grad (heads_grad.hip): the 3x3 convs of all heads as one [64 heads][9 Cin] float32 matrix
+// (K order kh, kw, c), their biases, that matrix's fp16x3 terms and row scales, the 1x1 convs [head][4][64] and their biases [head][4].
+// SFA_E_INVALID for a level outside the model's, SFA_E_UNSUPPORTED for a SFA_BACKBONE_DECONV model.
+struct HeadsLevel {
+  const float *w3, *b3, *w1, *b1;
+  const uint16_t* wh;  // the 3x3 matrix's fp16x3 terms [2][64 heads][9 Cin]
+  const float* winv;   // [64 heads]
+  int Cin, num_heads;
+  int ch[SFA_MAX_HEADS];
+};
+int model_heads_level(const sfa_model* m, int level, HeadsLevel* out);
+
 }  // namespace sfa

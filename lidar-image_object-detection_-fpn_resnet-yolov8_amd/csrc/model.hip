@@ -873,6 +873,26 @@ extern "C" int64_t sfa_forward_buffer_offset(const sfa_model* m, int batch, int 
   }
 }
 
+// The head parameters of KFPN level `level` inside the handle (conv.h HeadsLevel).
+int sfa::model_heads_level(const sfa_model* m, int level, HeadsLevel* out) {
+  if (m->backbone == SFA_BACKBONE_DECONV) {
+    set_error("heads_grad: a SFA_BACKBONE_DECONV model has no KFPN head levels");
+    return SFA_E_UNSUPPORTED;
+  }
+  SFA_CHECK_ARG(level >= 0 && level < 3, "heads_grad: level %d outside 0..2", level);
+  const PHeads& hp = m->plan.heads[level];
+  out->w3 = m->w + hp.w3;
+  out->b3 = m->w + hp.b3;
+  out->w1 = m->w + hp.w1;
+  out->b1 = m->w + hp.b1;
+  out->wh = reinterpret_cast<const uint16_t*>(m->w + hp.wh);
+  out->winv = m->w + hp.winv;
+  out->Cin = kFpnC[level];
+  out->num_heads = m->arch.num_heads;
+  for (int j = 0; j < SFA_MAX_HEADS; ++j) out->ch[j] = j < m->arch.num_heads ? m->arch.head_channels[j] : 0;
+  return SFA_OK;
+}
+
 #define SFA_RC(expr)            \
   do {                          \
     int rc_ = (expr);           \

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from sfa_hip import _lib
 from sfa_hip import dropin as _dropin
-from sfa_hip.runtime import KfpnEngine, kfpn_heads, pack_state_dict
+from sfa_hip.runtime import KfpnEngine, kfpn_combine_grad, kfpn_heads, pack_state_dict
 
 BN_MOMENTUM = 0.1
 
@@ -70,6 +70,39 @@ class BasicBlock(nn.Module):
         raise RuntimeError("BasicBlock runs fused inside PoseResNet's HIP forward")
 
 
+class _TrainableHeadsForward(torch.autograd.Function):
+    """PoseResNet.forward with the 60 head parameters as differentiable inputs (heads_trainable()).  forward is
+    the engine's forward into a workspace this call keeps; backward takes the level maps and the heads' inputs
+    from that workspace and runs sfa_kfpn_combine_grad, then sfa_model_heads_grad per level.  The input image
+    gets no gradient (nothing behind the heads is differentiated)."""
+
+    @staticmethod
+    def forward(ctx, eng, in_layout, x, *params):
+        B, _, H, W = x.shape
+        with torch.cuda.device(x.device):
+            outs = eng.alloc_outputs(B, H, W)
+            ws = torch.empty(eng.workspace_bytes(B, H, W), dtype=torch.uint8, device=x.device)
+            eng.forward_into(x, outs, in_layout, ws)
+        ctx.eng, ctx.ws, ctx.shape = eng, ws, (B, H, W)
+        return tuple(outs[n] for n, _ in eng.heads)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        eng, ws, (B, H, W) = ctx.eng, ctx.ws, ctx.shape
+        with torch.cuda.device(ws.device):
+            levels = {n: [t.contiguous() for t in lv] for n, lv in eng.debug_views(ws, B, H, W)["levels"].items()}
+            gout = {n: (g.contiguous() if g is not None else torch.zeros_like(levels[n][1]))
+                    for (n, _), g in zip(eng.heads, grads)}
+            glev = kfpn_combine_grad(levels, gout, level0_half=True)
+            flat = []
+            for level in range(3):
+                res = eng.heads_param_grad(level, eng.level_input(ws, B, H, W, level),
+                                           {n: glev[n][level] for n, _ in eng.heads})
+                for n, _ in eng.heads:
+                    flat += list(res[n])
+        return (None, None, None) + tuple(t if need else None for t, need in zip(flat, ctx.needs_input_grad[3:]))
+
+
 class PoseResNet(nn.Module):
     def __init__(self, block, layers, heads, head_conv, **kwargs):
         self.inplanes = 64
@@ -109,6 +142,7 @@ class PoseResNet(nn.Module):
         self._math = None  # set_math: None = the engine's default (SFA_MATH or fp16x3)
         self._sig = None
         self._state_tensors = None  # (structure generation, [state tensors]) cache of _signature
+        self._heads_trainable = False
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
@@ -166,6 +200,27 @@ class PoseResNet(nn.Module):
     def forward(self, x):
         return self.forward_layout(x, _lib.IN_NCHW3)
 
+    def heads_trainable(self, flag=True):
+        """Fine-tuning of the detection heads on a frozen backbone.  Off (the default): forward runs under
+        no_grad and returns detached maps.  On: with grad mode enabled, forward returns the same five maps (bit
+        for bit) carrying a grad_fn whose backward leaves ``.grad`` at the 60 head parameters
+        ``fpn{0,1,2}_{head}.{0,2}.{weight,bias}`` that require grad (sfa_kfpn_combine_grad, then
+        sfa_model_heads_grad per level).  Nothing behind the heads is differentiated: the input and every other
+        parameter get no gradient, and BatchNorm stays folded with its running statistics.  A batch above one
+        forward pass (``max_batch``) is refused in this mode.  Returns self."""
+        self._heads_trainable = bool(flag)
+        return self
+
+    def head_parameters(self):
+        """The 60 head parameters in the order the trainable forward differentiates them: level, head (forward
+        order), then 0.weight, 0.bias, 2.weight, 2.bias."""
+        out = []
+        for f in range(3):
+            for head in self.heads:
+                seq = getattr(self, f"fpn{f}_{head}")
+                out += [seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias]
+        return out
+
     def forward_layout(self, x, in_layout):
         """forward() with the input read as ``in_layout``: _lib.IN_NCHW3 (the reference's), or
         _lib.IN_NCHW3_FLIP_HW = forward(torch.flip(x, [2, 3])) with the flip fused in."""
@@ -178,6 +233,15 @@ class PoseResNet(nn.Module):
             raise ValueError(f"unsupported input layout {in_layout}")
         eng = self._engine(x.device)
         x = x.contiguous().float()
+        if self._heads_trainable and torch.is_grad_enabled():
+            B, _, H, W = x.shape
+            if B > eng.max_batch(H, W):
+                raise ValueError(f"heads_trainable: batch {B} is above one forward pass ({eng.max_batch(H, W)} frames "
+                                 f"at {H}x{W}); the workspace holds one pass only")
+            res = _TrainableHeadsForward.apply(eng, in_layout, x.detach(), *self.head_parameters())
+            self.kfpn_features, self.fpn_outputs = [], {}
+            self.kfpn_weights, self.backbone_features = {}, {}
+            return {n: t for (n, _), t in zip(eng.heads, res)}
         with torch.no_grad(), torch.cuda.device(x.device):
             B, _, H, W = x.shape
             outs = eng.alloc_outputs(B, H, W)

@@ -227,6 +227,12 @@ _PROTOS["sfa_kfpn_combine"] = (_c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_c_i
                                + [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp])
 _PROTOS["sfa_kfpn_combine_grad"] = (_c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_c_int)] + [_c_int] * 5
                                     + [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp])
+# head parameter gradients of one KFPN level (include/sfa_hip.h)
+_PROTOS["sfa_model_heads_grad_workspace_size"] = (_c_size, [_vp] + [_c_int] * 5)
+_PROTOS["sfa_model_heads_grad_chunk_pixels"] = (_c_int, [_vp] + [_c_int] * 5)
+_PROTOS["sfa_model_heads_grad"] = (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_int] + [ctypes.POINTER(_vp)] * 5
+                                   + [_vp, _vp, _c_int, _vp, _c_size, _vp])
+HEADS_LEVEL_CIN = (256, 128, 64)  # input channels of KFPN level 0, 1, 2 (SFA_BUF_UP_LEVEL2 / 3 / 4)
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
 _lib = None

@@ -260,6 +260,71 @@ class KfpnEngine:
         v["levels"] = levels
         return v
 
+    # ------------------------------------------------ head parameter gradients (sfa_model_heads_grad)
+    def level_input(self, ws: torch.Tensor, B, H, W, level: int) -> torch.Tensor:
+        """The NHWC (B, h, w, Cin) float32 view of the heads' input of KFPN ``level`` (SFA_BUF_UP_LEVEL2 / 3 / 4)
+        that the last forward left in workspace ``ws``."""
+        if self.deconv or level not in (0, 1, 2):
+            raise ValueError(f"level_input: KFPN level {level!r} of a {'resnet_18' if self.deconv else 'KFPN'} model")
+        if B < 1 or B > self.max_batch(H, W):
+            raise ValueError(f"level_input: batch {B} is outside one forward pass at {H}x{W}")
+        h, w, c = (H // 8, W // 8, 256) if level == 0 else (H // 4, W // 4, _lib.HEADS_LEVEL_CIN[level])
+        off = int(lib().sfa_forward_buffer_offset(self._h, B, H, W, _lib.BUF_UP_LEVEL2 + level))
+        return ws[off: off + B * h * w * c * 4].view(torch.float32).view(B, h, w, c)
+
+    def heads_grad_chunk_pixels(self, level: int, B, h, w, max_chunk_pixels: int = 0) -> int:
+        """K_c of :meth:`heads_param_grad`: the pixel count of its largest split-K chunk, the length of the
+        float32 accumulation inside dW1 (0 for a shape the entry refuses)."""
+        return int(lib().sfa_model_heads_grad_chunk_pixels(self._h, int(level), B, h, w, int(max_chunk_pixels)))
+
+    def heads_grad_workspace_bytes(self, level: int, B, h, w, max_chunk_pixels: int = 0) -> int:
+        return int(lib().sfa_model_heads_grad_workspace_size(self._h, int(level), B, h, w, int(max_chunk_pixels)))
+
+    def heads_param_grad(self, level: int, x: torch.Tensor, grad_by_head: dict, out: dict = None,
+                         want_hidden: bool = False, max_chunk_pixels: int = 0, workspace: torch.Tensor = None):
+        """The parameter gradients of KFPN ``level``'s heads (sfa_model_heads_grad).  ``x``: the heads' input,
+        float32 NHWC (B, h, w, Cin) on the GPU (Cin = 256 / 128 / 64; :meth:`level_input` after a forward, or any
+        tensor); ``grad_by_head`` = {head: d total / d (the level's head output), (B, c, h, w)}, every head of the
+        model.  Returns {head: (dW1 (64, Cin, 3, 3), db1 (64), dW2 (c, 64, 1, 1), db2 (c))}, every element written
+        by the call; ``out`` (the same structure, contiguous tensors) receives them instead of fresh tensors.
+        With ``want_hidden`` also returns Hd and dA, (B, h, w, 64 * heads) each, as the kernels used them.  The
+        hidden activation is recomputed in fp16x3 whatever the engine's math mode is.  With ``out`` and
+        ``workspace`` given the call only enqueues its launches (graph-capturable)."""
+        x = _require_gpu_tensor(x, "heads_param_grad x")
+        if x.dim() != 4 or level not in (0, 1, 2) or int(x.shape[3]) != _lib.HEADS_LEVEL_CIN[level]:
+            raise ValueError(f"heads_param_grad: x {tuple(x.shape)} is not (B, h, w, Cin) of level {level!r}")
+        B, h, w, cin = (int(v) for v in x.shape)
+        names = [n for n, _ in self.heads]
+        gs = []
+        for n, c in self.heads:
+            g = _require_gpu_tensor(grad_by_head[n], f"heads_param_grad grad[{n!r}]")
+            if tuple(g.shape) != (B, c, h, w):
+                raise ValueError(f"heads_param_grad grad[{n!r}]: {tuple(g.shape)} != {(B, c, h, w)}")
+            gs.append(g)
+        shapes = [((64, cin, 3, 3), (64,), (c, 64, 1, 1), (c,)) for _, c in self.heads]
+        if out is None:
+            res = [[torch.empty(s, dtype=torch.float32, device=x.device) for s in sh] for sh in shapes]
+        else:
+            res = [_kfpn_buffers(dict(enumerate(out[n])), range(4), sh, x, f"heads_param_grad out[{n!r}]")
+                   for n, sh in zip(names, shapes)]
+        hid = [torch.empty((B, h, w, 64 * len(names)), dtype=torch.float32, device=x.device) for _ in range(2)] \
+            if want_hidden else None
+        need = self.heads_grad_workspace_bytes(level, B, h, w, max_chunk_pixels)
+        if need == 0:
+            msg = lib().sfa_last_error_string()
+            raise ValueError(f"heads_param_grad: B={B}, h={h}, w={w}, max_chunk_pixels={max_chunk_pixels} refused: "
+                             f"{msg.decode() if msg else ''}")
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            check(lib().sfa_model_heads_grad(self._h, level, x.data_ptr(), B, h, w, _ptr_array(gs),
+                                             *(_ptr_array([r[k] for r in res]) for k in range(4)),
+                                             hid[0].data_ptr() if hid else None, hid[1].data_ptr() if hid else None,
+                                             int(max_chunk_pixels), workspace.data_ptr(), workspace.numel(),
+                                             _lib.stream_ptr(x.device)), "sfa_model_heads_grad")
+        grads = {n: tuple(r) for n, r in zip(names, res)}
+        return (grads, hid[0], hid[1]) if want_hidden else grads
+
     def forward(self, x: torch.Tensor, in_layout: int = _lib.IN_NCHW3) -> dict:
         x = _require_gpu_tensor(x, "PoseResNet.forward")
         if in_layout != _lib.IN_NHWC4:

@@ -9,6 +9,8 @@ total_loss over the frames, one JSON line.
   --timing         median microseconds of target build + loss for 16 frames on a captured HIP graph
   --timing --grad  also targets + loss + gradient (sfa_compute_loss_grad) on one graph, then bench.py
   --timing --grad --kfpn   also that graph with the KFPN gradient (sfa_kfpn_combine_grad) behind the loss gradient
+  --timing --grad --kfpn --heads   also that graph with the head parameter gradients (sfa_model_heads_grad) of one,
+                           two and all three KFPN levels behind the KFPN gradient
 
 The loop is evaluation only (the gradient at the heads is only timed).  With a data set, the labels of a batch are read with the
 data set's own helpers (get_label, camera_to_lidar_box, filter_labels: a reference tree on sys.path or in
@@ -31,7 +33,7 @@ for p in (REPO, SFA_ROOT):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-from sfa_hip import runtime, synthetic  # noqa: E402
+from sfa_hip import _lib, runtime, synthetic  # noqa: E402
 
 
 class Cfg(dict):
@@ -125,10 +127,11 @@ def evaluate(model, batches, args, device):
     return losses.avg, {k: v / max(frames, 1) for k, v in parts.items()}, frames
 
 
-def timing(device, args, frames=16, reps=50, grad=False, kfpn=False):
+def timing(device, args, frames=16, reps=50, grad=False, kfpn=False, heads_levels=0, engine=None):
     """Median microseconds of sfa_build_targets + sfa_compute_loss (with ``grad`` also sfa_compute_loss_grad, with
     ``kfpn`` also sfa_kfpn_combine_grad from the head gradients to the 15 per-level maps, level 0 at half
-    resolution) for ``frames`` frames, one HIP graph."""
+    resolution; with ``heads_levels`` = n also sfa_model_heads_grad of KFPN levels 0 .. n - 1 of ``engine`` from those
+    level gradients and a synthetic heads' input) for ``frames`` frames, one HIP graph."""
     hm = args.input_size // 4
     labels, offsets = synthetic.synthetic_labels(frames, seed=args.seed)
     builder = runtime.TargetBuilder(device, runtime.DEFAULT_BOUNDARY, (hm, hm), 3, args.max_objects)
@@ -146,6 +149,15 @@ def timing(device, args, frames=16, reps=50, grad=False, kfpn=False):
                   for i, (h, c) in enumerate(runtime.DEFAULT_HEADS.items())}
         level_grads = {h: [torch.empty_like(t) for t in lv] for h, lv in levels.items()}
 
+    hg = []
+    for level in range(heads_levels):
+        n, cin = sizes[level], _lib.HEADS_LEVEL_CIN[level]
+        x = torch.from_numpy(np.abs(synthetic.synthetic_logits((frames, n, n, cin), args.seed, 120 + level))).to(device)
+        out = {h: [torch.empty(s, dtype=torch.float32, device=device)
+                   for s in ((64, cin, 3, 3), (64,), (c, 64, 1, 1), (c,))] for h, c in runtime.DEFAULT_HEADS.items()}
+        ws = torch.empty(engine.heads_grad_workspace_bytes(level, frames, n, n), dtype=torch.uint8, device=device)
+        hg.append((level, x, {h: lv[level] for h, lv in level_grads.items()}, out, ws))
+
     def step():
         builder(d_labels, d_offsets, None, out=tg, verify=False)
         ev(outs, tg, apply_sigmoid=True, verify=False)
@@ -153,6 +165,8 @@ def timing(device, args, frames=16, reps=50, grad=False, kfpn=False):
             ev.grad(outs, tg, apply_sigmoid=True, verify=False, out=grads)
         if kfpn:
             runtime.kfpn_combine_grad(levels, grads, level0_half=True, out=level_grads)
+        for level, x, g, out, ws in hg:
+            engine.heads_param_grad(level, x, g, out=out, workspace=ws)
 
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -204,6 +218,9 @@ def main(argv=None):
                     help="with --timing: also time targets + loss + gradient on one graph, then run bench.py")
     ap.add_argument("--kfpn", action="store_true",
                     help="with --timing --grad: also time that graph with the KFPN gradient added (one run, no threshold)")
+    ap.add_argument("--heads", action="store_true",
+                    help="with --timing --grad --kfpn: also time that graph with the head parameter gradients of KFPN "
+                         "levels 0, 0-1 and 0-2 added (one run, no threshold)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gpu_idx", type=int, default=0)
     args = ap.parse_args(argv)
@@ -228,6 +245,13 @@ def main(argv=None):
             result["targets_plus_loss_plus_grad_graph"] = timing(device, args, grad=True)
             if args.kfpn:
                 result["targets_plus_loss_plus_grad_plus_kfpn_grad_graph"] = timing(device, args, grad=True, kfpn=True)
+                if args.heads:
+                    if args.arch != "fpn_resnet_18":
+                        ap.error("--heads needs the KFPN model (fpn_resnet_18)")
+                    eng = model._engine(device)
+                    for n in (1, 2, 3):
+                        result[f"plus_heads_grad_levels_0_to_{n - 1}_graph"] = timing(
+                            device, args, grad=True, kfpn=True, heads_levels=n, engine=eng)
             result["bench"] = run_bench()
     print(json.dumps(result))
     return result
