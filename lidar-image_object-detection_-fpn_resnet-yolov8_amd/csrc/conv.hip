@@ -75,29 +75,34 @@ static bool strip_ok(const ConvArgs& a) {
 //    conv_r3_kernel, float4 taps;
 //  * the rest (layer3/4 stride-2 and conv + downsample, the FPN low-resolution 1x1 convs, the stem
 //    without the patch kernel): conv_h3_kernel on 16x16x32 MFMAs.
-// conv_r3_kernel ABL values (conv_r3_kernel.h bit list): 256 spread W DMA | 2048 transposed
-// accumulators, always; 524288 chunk-major K order (the 3x3 window's 32-channel slices stay in L2
-// across the 9 taps; heads' HBM traffic 3.5-4.7x lower: profiles/r02_convbench_cmaj.txt);
-// 32768 the upsampled-residual epilogue (FPN skip convs).
-constexpr int R3_BODY = 256 | 2048 | 524288;
-constexpr int R3_FPN = 256 | 2048 | 32768;
-// heads: + s_setprio 1 for waves 4-7 (4), v_fma_mix split (4096), 3-block W read-ahead (8192), scalar
-// tap decode (16384), packed epilogue (65536), waves 4-7 half a K-tile behind their SIMD partners
-// with three W stages (1048576: -4.6 / -3.1 / -1.0 % per launch on L1 / L2 / L0, bit-identical,
+// The product instances' option sets (bit semantics: r3opt / h3sopt / h3opt beside the kernels).
+// The integers are part of the kernels' names, which the recorded profiles are matched by: pinned below.
+// conv_r3 body and FPN skip convs: chunk-major K order (heads' HBM traffic 3.5-4.7x lower:
+// profiles/r02_convbench_cmaj.txt) / the upsampled-residual epilogue.
+constexpr int R3_BODY = r3opt::ALWAYS | r3opt::CHUNK_MAJOR;
+constexpr int R3_FPN = r3opt::ALWAYS | r3opt::RES_UP;
+// heads: the stagger (-4.6 / -3.1 / -1.0 % per launch on L1 / L2 / L0, bit-identical,
 // profiles/r03h_convbench_heads_stagger.txt), the delayed half issuing every W DMA piece of the K loop
-// (2097152, round 5: -2.2 %, bit-identical, profiles/r05ah_heads_delayed_half_dma.txt)
-constexpr int R3_HEAD_STAG = 256 | 2048 | 4 | 4096 | 8192 | 16384 | 65536 | 524288 | 1048576 | 2097152;
-// strip kernel (conv_h3s_kernel.h bits): transposed epilogue (2), v_fma_mix split (8), the pre-split
-// strip (4) and the residual tile loaded during the last super-step (128) on every tile shape (round
-// 5: with the one-latency presplit the 128-wide tiles gain from them too, layer2 -4.6 % / -6.5 % with a
-// residual, layer3 -1 / -2 %, bit-identical: profiles/r05j_*; the names of the former two forms stay),
-// the strip in registers instead of an LDS-DMA buffer (1024, late round 5: layer1 -2.7 %, layer2 -2.2 %,
-// layer4 -2.8 %, bench +0.6 %, bit-identical, profiles/r05bi_*)
-constexpr int H3S_64 = 2 | 4 | 8 | 128 | 1024;
-constexpr int H3S_128 = 2 | 4 | 8 | 128 | 1024;
+// (round 5: -2.2 %, bit-identical, profiles/r05ah_heads_delayed_half_dma.txt)
+constexpr int R3_HEAD_STAG = r3opt::ALWAYS | r3opt::PRIO_HALF | r3opt::MIX_SPLIT | r3opt::READ_AHEAD3 |
+                             r3opt::SCALAR_TAPS | r3opt::PACKED_HEAD | r3opt::CHUNK_MAJOR | r3opt::STAGGER |
+                             r3opt::DELAYED_DMA;
+// strip kernel: the pre-split strip and the residual prefetch on every tile shape (round 5: with the
+// one-latency presplit the 128-wide tiles gain from them too, layer2 -4.6 % / -6.5 % with a residual,
+// layer3 -1 / -2 %, bit-identical: profiles/r05j_*; the names of the former two forms stay), the strip in
+// registers (late round 5: layer1 -2.7 %, layer2 -2.2 %, layer4 -2.8 %, bench +0.6 %, bit-identical,
+// profiles/r05bi_*)
+constexpr int H3S_64 = h3sopt::ALWAYS | h3sopt::PRESPLIT | h3sopt::RES_PREFETCH | h3sopt::STRIP_REGS;
+constexpr int H3S_128 = H3S_64;
 // 128 x 128 tiles (layer2): at 3 blocks / CU without the residual prefetch (198 -> 168 VGPRs; the strip in
 // registers freed the LDS), 722 tiles in one round of 768 slots: -1.9 %, bit-identical, profiles/r05bj_*
-constexpr int H3S_128W = 2 | 4 | 8 | 1024;
+constexpr int H3S_128W = h3sopt::ALWAYS | h3sopt::PRESPLIT | h3sopt::STRIP_REGS;
+// conv_h3: the 64-wide instances as they are, the 128-wide ones with a sched_barrier per column block
+constexpr int H3_PLAIN = 0;
+constexpr int H3_PIPE = h3opt::PIPE;
+static_assert(R3_BODY == 526592 && R3_FPN == 35072 && R3_HEAD_STAG == 3766532, "conv_r3 instance names");
+static_assert(H3S_64 == 1166 && H3S_128 == 1166 && H3S_128W == 1038, "conv_h3s instance names");
+static_assert(H3_PLAIN == 0 && H3_PIPE == 2, "conv_h3 instance names");
 
 // FPN 1x1 convs (commuted: the low-resolution W_a . x and the skip conv with the upsampled
 // residual) on the persistent weight-resident kernel (fpn_kernel.h), by channel count.
@@ -162,9 +167,9 @@ static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
   if (a.N == 64) {
     if (strip) rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64, TERMS>(a, st);
     if (!ok(rc) && a.Kpad >= 256)
-      rc = launch_conv_h3_cfg<256, 64, 32, EPI_STD, 1, 32, 2, false, 0, 1, 64, TERMS>(a, st);
+      rc = launch_conv_h3_cfg<256, 64, 32, EPI_STD, 1, 32, 2, false, H3_PLAIN, 1, 64, TERMS>(a, st);
     if constexpr (TERMS == 2) {
-      if (!ok(rc)) rc = launch_conv_h3_cfg<128, 64, 32, EPI_STD, 2, 16, 3, false, 0>(a, st);
+      if (!ok(rc)) rc = launch_conv_h3_cfg<128, 64, 32, EPI_STD, 2, 16, 3, false, H3_PLAIN>(a, st);
       if (!ok(rc) && !sliced) rc = launch_conv_x6g_cfg<256, 64, 32, EPI_STD, 1, 16, 3, 0, 64, 1>(a, st);
     }
     return rc;
@@ -196,8 +201,8 @@ static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
       // layer3 / 4 convs on the same tiles were slower, r05bn_*)
       if constexpr (TERMS == 2)
         if (sliced && a.seg[0].KH == 1 && a.seg[0].KW == 1)
-          rc = launch_conv_h3_cfg<64, 128, 32, EPI_STD, 3, 32, 2, false, 2, 1, 64>(b, st);
-      if (!ok(rc)) rc = launch_conv_h3_cfg<128, 128, 32, EPI_STD, 2, 32, 2, false, 2, 1, 128, TERMS>(b, st);
+          rc = launch_conv_h3_cfg<64, 128, 32, EPI_STD, 3, 32, 2, false, H3_PIPE, 1, 64>(b, st);
+      if (!ok(rc)) rc = launch_conv_h3_cfg<128, 128, 32, EPI_STD, 2, 32, 2, false, H3_PIPE, 1, 128, TERMS>(b, st);
     }
     if constexpr (TERMS == 2)
       if (!ok(rc) && !sliced) rc = launch_conv_x6g_cfg<128, 128, 32, EPI_STD, 2, 16, 3, 0, 128, 1>(b, st);

@@ -241,8 +241,15 @@ __device__ __forceinline__ void h3_pool_epilogue(const ConvArgs& a, x6_f32x16 (&
   }
 }
 
-// ABL (variants for tools/convbench): 1 = no DMA in the K loop (ablation), 2 = software-
-// pipelined fragment reads (compute_pipe), 4 = s_setprio 1 for the second half of the waves.
+// ABL: conv_h3_kernel's option bits (variants for tools/convbench; the values are part of the
+// instances' names).
+namespace h3opt {
+constexpr int NO_LOOP_DMA = 1;  // no DMA in the K loop (ablation)
+// software-pipelined fragment reads: compute_pipe (32x32x16 form), a sched_barrier per column block
+// (16x16x32 form)
+constexpr int PIPE = 2;
+constexpr int PRIO_HALF = 4;  // s_setprio 1 for the second half of the waves
+}  // namespace h3opt
 // MF: 0 = v_mfma_f32_32x32x16_f16 (32-row / 32-column wave sub-tiles), 1 = v_mfma_f32_16x16x32_f16
 // (16 x 16 sub-tiles, BK 32: same LDS reads and registers per MAC; the chip holds a higher
 // clock under the 16x16 shape on random data, MI355X_MICROARCH.md 'DVFS give-back' (7)).
@@ -277,6 +284,9 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WN) * 64, OCC) conv_h3_kerne
   // TERMS: 2 = fp16x3; 1 = SFA_MATH_FP16 (16x16x32 form only; conv_r3_kernel.h): the high A term alone, only
   // plane 0 of a.wh in the stage, one MFMA per fragment pair
   static_assert(TERMS == 2 || (TERMS == 1 && MF == 1), "one-product form: 16x16x32 MFMAs");
+  constexpr bool LOOP_DMA = (ABL & h3opt::NO_LOOP_DMA) == 0;
+  constexpr bool PIPE = (ABL & h3opt::PIPE) != 0;
+  constexpr bool PRIO_HALF = (ABL & h3opt::PRIO_HALF) != 0;
   static_assert(BK == 16 || BK == 32, "BK");
   static_assert(NSTAGE >= 2 && NSTAGE <= 4, "ring depth");
   static_assert(NSEG == 1 || NSEG == 2, "segments");
@@ -518,7 +528,7 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WN) * 64, OCC) conv_h3_kerne
     }
   };
 
-  // Software-pipelined form (ABL & 2): the scheduler may not move instructions across
+  // Software-pipelined form (h3opt::PIPE): the scheduler may not move instructions across
   // the column-block boundaries, so the W fragments are read two column blocks ahead
   // (across the k-step boundary too) and the next k-step's A quads are read after the
   // first column block and split after the third, between MFMAs.
@@ -625,7 +635,7 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WN) * 64, OCC) conv_h3_kerne
           cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(hf[0][mi], c0, cc, 0, 0, 0);
           acc[mi][ni] = cc;
         }
-        if constexpr ((ABL & 2) != 0) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (PIPE) __builtin_amdgcn_sched_barrier(0);
       }
     }
   };
@@ -635,7 +645,7 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WN) * 64, OCC) conv_h3_kerne
   // ring: tile kt lives in stage kt % NSTAGE; tiles kt+1 .. kt+NSTAGE-1 are in flight
 #pragma unroll
   for (int p = 0; p < NSTAGE - 1; ++p) load_tile(kt0 + (p < nk ? p : nk - 1), smem + p * STAGE);
-  if constexpr ((ABL & 4) != 0) {
+  if constexpr (PRIO_HALF) {
     if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
   }
   int st_cur = 0, st_next = NSTAGE - 1;
@@ -647,13 +657,13 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WN) * 64, OCC) conv_h3_kerne
     else
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSTAGE - 2) * (PER - 1)) : "memory");
     __builtin_amdgcn_s_barrier();  // every wave's: stage kt complete; stage kt-1 no longer read
-    if constexpr (!(ABL & 1)) {
+    if constexpr (LOOP_DMA) {
       const int kn = kt + NSTAGE - 1;
       load_tile(kt0 + (kn < nk ? kn : nk - 1), smem + st_next * STAGE);
     }
     if constexpr (MF == 1)
       compute16(smem + st_cur * STAGE);
-    else if constexpr ((ABL & 2) != 0)
+    else if constexpr (PIPE)
       compute_pipe(smem + st_cur * STAGE);
     else
       compute(smem + st_cur * STAGE);

@@ -24,21 +24,32 @@ namespace sfa {
 // tools/experiments/r03/conv_h3s_kernel.h with their convbench hooks): transposed accumulators
 // (the W fragment as the MFMA A operand) with conv_r3_kernel.h's float4 epilogue
 // (r3t_epilogue_std) and float4 split-K partials, the fp16 split in 2 VALU per value
-// (split2h_x8 / split2h_pair, inline v_fma_mix). ABL bits (the values are kept from round 3, so
-// the instances keep their names: H3S_64 = 142, H3S_128 = 10 in conv.hip):
-// 4 = pre-split strip: at kw 0 each wave splits ITS rows of the f32 strip (WM + 2 rows, the kw
+// (split2h_x8 / split2h_pair, inline v_fma_mix). ABL is a set of h3sopt bits (the values are kept
+// from round 3, so the instances keep their names: conv.hip H3S_*).
+namespace h3sopt {
+constexpr int TRANSPOSED = 2;  // transposed accumulators, float4 epilogue and partials (always set)
+// pre-split strip: at kw 0 each wave splits ITS rows of the f32 strip (WM + 2 rows, the kw
 // halo included) once into fp16 hi / lo rows of a private LDS region, and the three kw k-steps
 // read ready fp16 fragments (a third of the split VALU; conv padding by reading a zero row).
 // One f32 strip buffer: the next strip is issued at kw 1, when every wave has split this one.
-// 128 = (with 4) the residual tile loaded at the last super-step's kw 1 (in place of the no-op
-// strip reload), so the last six k-steps' MFMAs hide its latency; 2 and 8 are always set.
-// 256 = register-staged W (round 4): each k-step's W pieces are fetched with buffer_load_dwordx4
+constexpr int PRESPLIT = 4;
+constexpr int MIX_SPLIT = 8;  // fp16 split in 2 VALU per value, inline v_fma_mix (always set)
+// (with PRESPLIT) the residual tile loaded at the last super-step's kw 1 (in place of the no-op
+// strip reload), so the last six k-steps' MFMAs hide its latency
+constexpr int RES_PREFETCH = 128;
+// register-staged W (round 4): each k-step's W pieces are fetched with buffer_load_dwordx4
 // into VGPRs at the step's start and written to the other W stage with ds_write_b128 after the
 // step's MFMAs (an LDS-DMA piece costs ~60 issue cycles, a load + ds_write_b128 ~20); same
 // LDS image, same products: bit-identical.
-// 1024 = (with 4; round 5) the strip into REGISTERS: each wave loads its own WM + 2 rows (the kw halo) of
+constexpr int REG_W = 256;
+// (with PRESPLIT; round 5) the strip into REGISTERS: each wave loads its own WM + 2 rows (the kw halo) of
 // the next (kh, chunk) strip with buffer loads at kw 1 and splits them from its VGPRs at kw 0, so the f32
 // strip never passes through LDS (no strip buffer, no LDS-DMA pieces, no f32 LDS reads in the split).
+constexpr int STRIP_REGS = 1024;
+constexpr int ALWAYS = TRANSPOSED | MIX_SPLIT;  // set in every product instance
+constexpr int ALLOWED = ALWAYS | PRESPLIT | RES_PREFETCH | REG_W | STRIP_REGS;
+}  // namespace h3sopt
+
 // TERMS: 2 = fp16x3; 1 = SFA_MATH_FP16 (one product per MAC, conv_r3_kernel.h): the pre-split rows hold the
 // high term alone, only plane 0 of a.wh is staged, one MFMA per fragment pair.
 template <int BM, int BN, int WM, int EPI, int OCC, int ABL = 0, int TERMS = 2>
@@ -54,10 +65,10 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
   constexpr int ND_B = W_BYTES / 1024;  // W pieces per k-step (16 rows each)
   constexpr int NS = (ND_S + NW - 1) / NW, NS_REM = ND_S % NW;
   constexpr int NB = (ND_B + NW - 1) / NW, NB_REM = ND_B % NW;
-  constexpr bool PS = (ABL & 4) != 0;
-  constexpr bool RESPF = PS && (ABL & 128) != 0;
-  constexpr bool RW = (ABL & 256) != 0;
-  constexpr bool SREG = (ABL & 1024) != 0;
+  constexpr bool PS = (ABL & h3sopt::PRESPLIT) != 0;
+  constexpr bool RESPF = PS && (ABL & h3sopt::RES_PREFETCH) != 0;
+  constexpr bool RW = (ABL & h3sopt::REG_W) != 0;
+  constexpr bool SREG = (ABL & h3sopt::STRIP_REGS) != 0;
   constexpr int PROWS = WM + 2;              // a wave's pre-split rows (its WM rows + the kw halo)
   constexpr int PR_BYTES = (PROWS + 1) * 64;  // per term: 32 fp16 per row, + one zero row
   constexpr int NSB = PS ? (SREG ? 0 : 1) : 2;  // f32 strip buffers
@@ -66,7 +77,8 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
   constexpr int CSB_OFF = MAIN_BYTES;  // the tile's winv / bias columns (epilogue), staged in the prologue
   constexpr int LDS_BYTES = MAIN_BYTES + 2 * BN * 4;
   static_assert(NW % 2 == 0 && WM % 16 == 0 && BN % 16 == 0, "tile");
-  static_assert((ABL & 10) == 10 && (ABL & ~(2 | 4 | 8 | 128 | 256 | 1024)) == 0, "product strip-kernel form (see the bit list)");
+  static_assert((ABL & h3sopt::ALWAYS) == h3sopt::ALWAYS && (ABL & ~h3sopt::ALLOWED) == 0,
+                "product strip-kernel form (see h3sopt)");
   static_assert(!SREG || (PS && !RW), "strip in registers: the pre-split form, W by LDS-DMA");
   static_assert(EPI == EPI_STD, "transposed form: standard epilogue only");
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];

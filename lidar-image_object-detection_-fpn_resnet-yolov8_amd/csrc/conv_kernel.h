@@ -26,11 +26,19 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // GLDS: stage the A/B tiles with buffer_load ... lds (LDS-DMA, no VGPR staging)
 //   into a 3-deep ring of unpadded, XOR-swizzled tiles (BK = 16 only).
-// ABL: diagnostic ablation bits for tools/convbench (0 in the product):
-//   1 = no global loads in the K loop, 2 = no barrier, 4 = no LDS fragment reads.
+// ABL: diagnostic ablation bits for tools/convbench (0 in the product).
+namespace f32opt {
+constexpr int NO_LOOP_LOADS = 1;  // no global loads in the K loop
+constexpr int NO_BARRIER = 2;     // no barrier
+constexpr int NO_LDS_READS = 4;   // no LDS fragment reads
+}  // namespace f32opt
+
 template <int BM, int BN, int WM, int WN, int BK, int EPI, int OCC, bool GLDS = false, int ABL = 0>
 __global__ void __launch_bounds__(256, OCC) conv_mfma_kernel(const ConvArgs a) {
   static_assert(!GLDS || BK == 16, "the LDS-DMA ring is built for BK = 16");
+  constexpr bool LOOP_LOADS = (ABL & f32opt::NO_LOOP_LOADS) == 0;
+  constexpr bool BARRIER = (ABL & f32opt::NO_BARRIER) == 0;
+  constexpr bool LDS_READS = (ABL & f32opt::NO_LDS_READS) == 0;
   // GLDS rows are 64 B, quad q of row R stored at position q ^ ((R >> 2) & 3)
   constexpr int LDK = GLDS ? BK : BK + 4;
   constexpr int NSTAGE = GLDS ? 3 : 2;
@@ -163,7 +171,7 @@ __global__ void __launch_bounds__(256, OCC) conv_mfma_kernel(const ConvArgs a) {
 
   const int r = lane & 31, h = lane >> 5;
   auto compute = [&](int stage) {
-    const float* As = smem + (ABL & 4 ? 0 : stage * STAGE);
+    const float* As = smem + (LDS_READS ? stage * STAGE : 0);
     const float* Bs = As + BM * LDK;
     f32x4 af[TM][FR], bf[TN][FR];
     // row R = 32-row group base + r; with GLDS, (R >> 2) & 3 == (r >> 2) & 3
@@ -222,10 +230,10 @@ __global__ void __launch_bounds__(256, OCC) conv_mfma_kernel(const ConvArgs a) {
     // Unconditional prefetch (the last iteration re-stages the final tile into the
     // idle buffer): keeps ra/rb in registers — a conditional definition made hipcc
     // spill them to scratch.
-    if constexpr (!(ABL & 1)) load_tile(kt + 1 < nk ? kt + 1 : kt);
+    if constexpr (LOOP_LOADS) load_tile(kt + 1 < nk ? kt + 1 : kt);
     compute(cur);
     store_tile(cur ^ 1);
-    if constexpr (!(ABL & 2)) __syncthreads();
+    if constexpr (BARRIER) __syncthreads();
   }
   }
 

@@ -32,7 +32,7 @@ namespace sfa {
 
 typedef unsigned r3_u32x4 __attribute__((ext_vector_type(4)));
 
-// Epilogues of the TRANSPOSED accumulator form (ABL 2048: the MFMAs take the W fragment as
+// Epilogues of the TRANSPOSED accumulator form (r3opt::TRANSPOSED: the MFMAs take the W fragment as
 // their A operand and the activation fragment as B, so the 16x16 tile of acc[mi][ni] holds
 // C^T: lane l, register v -> output channel n0 + 16 ni + 4 (l >> 4) + v of pixel row
 // m0 + 16 mi + (l & 15)). Every lane owns four consecutive channels of ONE pixel: its own row
@@ -290,33 +290,36 @@ __device__ __forceinline__ void r3t_epilogue_head(const ConvArgs& a, f32x4_t (&a
   }
 }
 
-// ABL: the product form's bits (round 4: the measured-and-rejected variants and ablations —
+// ABL: the product form's option bits (round 4: the measured-and-rejected variants and ablations —
 // compiler-scheduled DMA, A split one tile ahead, staggered split, 3-stage ring without the
 // stagger, in-kernel split-K, non-temporal stores, residual prefetch, shifted A fragments, the
 // grouped head launch — live in tools/experiments/r03/conv_r3_kernel.h with their convbench
 // hooks). The values are kept from round 3, so the instances keep their names (conv.hip R3_*).
-// Always set: 256 = spread the W DMA: A loads at block 0, then one W piece per block from block 2,
-// the two waves of a SIMD (w, w + NW/2) on alternate blocks, so no SIMD issues two DMA bursts at
-// once; 2048 = transposed accumulators (W fragment as the MFMA A operand) with the float4 /
-// shuffle epilogues above.
-// Per launch configuration:
-// 4 = s_setprio 1 for the second half of the waves,
-// 4096 = fp16 split in 2 VALU per value (split2h_x8, inline v_fma_mix),
-// 8192 = W fragments read 3 column blocks ahead (with the stagger) instead of 2,
-// 16384 = scalar tap decode + per-lane tap validity masks for the A addresses (one segment,
-// C >= 32, checked at launch),
-// 32768 = the epilogue also takes an upsampled half-resolution residual (a.res_up: the FPN skip
-// convs; only those instances carry its registers),
-// 65536 = (heads) packed epilogue: v_pk_fma_f32 over channel pairs, only the head's ch outputs
-// formed,
-// 524288 = channel-chunk-major K order over segment 0 (a 3x3 window, C % 32 == 0): K-tile kt covers
+namespace r3opt {
+constexpr int PRIO_HALF = 4;  // s_setprio 1 for the second half of the waves
+// spread the W DMA: A loads at block 0, then one W piece per block from block 2, the two waves of a
+// SIMD (w, w + NW/2) on alternate blocks, so no SIMD issues two DMA bursts at once
+constexpr int SPREAD_DMA = 256;
+// transposed accumulators (W fragment as the MFMA A operand) with the float4 / shuffle epilogues above
+constexpr int TRANSPOSED = 2048;
+constexpr int MIX_SPLIT = 4096;  // fp16 split in 2 VALU per value (split2h_x8, inline v_fma_mix)
+constexpr int READ_AHEAD3 = 8192;  // W fragments read 3 column blocks ahead (with the stagger) instead of 2
+// scalar tap decode + per-lane tap validity masks for the A addresses (one segment, C >= 32, checked
+// at launch)
+constexpr int SCALAR_TAPS = 16384;
+// the epilogue also takes an upsampled half-resolution residual (a.res_up: the FPN skip convs; only
+// those instances carry its registers)
+constexpr int RES_UP = 32768;
+// (heads) packed epilogue: v_pk_fma_f32 over channel pairs, only the head's ch outputs formed
+constexpr int PACKED_HEAD = 65536;
+// channel-chunk-major K order over segment 0 (a 3x3 window, C % 32 == 0): K-tile kt covers
 // tap kt % 9 of the 32-channel chunk kt / 9 (weight columns tap * C + 32 chunk .. +31), so the
 // blocks resident on one XCD sweep a 32-channel slice of their input window through all 9 taps
 // before the next slice: that slice (~1-2 MB per XCD for the heads) stays in the 4 MB L2, where
 // the tap-major order's whole-window working set (4-9 MB per XCD at C = 128 / 256) re-read the
-// input from the fabric at every tap (heads L0 / L1: 7x / 5x their input in HBM traffic),
-// 2097152 = (with the stagger) the delayed half issues every W DMA piece of the K loop, the leading half none,
-// 1048576 = half-tile stagger (NSTAGE 3): waves NW/2 .. NW - 1 run their K loop half a K-tile
+// input from the fabric at every tap (heads L0 / L1: 7x / 5x their input in HBM traffic)
+constexpr int CHUNK_MAJOR = 524288;
+// half-tile stagger (NSTAGE 3): waves NW/2 .. NW - 1 run their K loop half a K-tile
 // behind their SIMD partners (w - NW/2). The barrier that closes interval i (W of tile i + 1
 // landed) comes after tile i for the first half of the waves and after the first half of tile i
 // for the second, so the partners never reach their split VALU, their tile-top W reads and the
@@ -324,8 +327,19 @@ __device__ __forceinline__ void r3t_epilogue_head(const ConvArgs& a, f32x4_t (&a
 // tiles i - 1 (second half only) and i, and DMAs tile i + 1: three stages. The delayed half reads
 // the next tile's first W blocks ahead across its tile boundary (that tile was published by the
 // barrier before); the leading half reads them after its barrier. Same products in the same
-// order: bit-identical to the unstaggered loop.
-// Without the stagger the ring has two stages (NSTAGE 2).
+// order: bit-identical to the unstaggered loop. Without the stagger the ring has two stages
+// (NSTAGE 2).
+constexpr int STAGGER = 1048576;
+// (with the stagger; round 5) the delayed half also issues its SIMD partner's W pieces in the K loop
+// (piece e = wave - NW / 2 + NW j), the leading half none: the delayed half (s_setprio 1) reached
+// each barrier ~1,100 cycles early and idled there, the leading half now sheds its DMA issue
+// (heads -2.2 %, same bits: profiles/r05ah_*)
+constexpr int DELAYED_DMA = 2097152;
+constexpr int ALWAYS = SPREAD_DMA | TRANSPOSED;  // set in every product instance
+constexpr int ALLOWED = ALWAYS | PRIO_HALF | MIX_SPLIT | READ_AHEAD3 | SCALAR_TAPS | RES_UP | PACKED_HEAD |
+                        CHUNK_MAJOR | STAGGER | DELAYED_DMA;
+}  // namespace r3opt
+
 // The kernel body for output tile (and split-K slice) lbid; conv_r3_kernel maps blockIdx to lbid
 // with xcd_remap.
 // TERMS: 2 = fp16x3 (hi / lo terms, three products); 1 = SFA_MATH_FP16: one product per MAC — the A
@@ -335,10 +349,17 @@ __device__ __forceinline__ void r3t_epilogue_head(const ConvArgs& a, f32x4_t (&a
 template <int BM, int BN, int WM, int EPI, int OCC, int NSTAGE, int NSEG, int ABL = 0, int TERMS = 2>
 __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
   static_assert(TERMS == 1 || TERMS == 2, "fp16 terms per operand");
-  constexpr bool STAG = (ABL & 1048576) != 0;
-  static_assert((ABL & (256 | 2048)) == (256 | 2048) &&
-                    (ABL & ~(4 | 256 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536 | 524288 | 1048576 | 2097152)) == 0,
-                "product conv_r3 form (see the bit list)");
+  static_assert((ABL & r3opt::ALWAYS) == r3opt::ALWAYS && (ABL & ~r3opt::ALLOWED) == 0,
+                "product conv_r3 form (see r3opt)");
+  constexpr bool PRIO_HALF = (ABL & r3opt::PRIO_HALF) != 0;
+  constexpr bool MIX_SPLIT = (ABL & r3opt::MIX_SPLIT) != 0;
+  constexpr int RA = (ABL & r3opt::READ_AHEAD3) != 0 ? 3 : 2;  // W fragment blocks read ahead of their MFMAs
+  constexpr bool FAST_A = (ABL & r3opt::SCALAR_TAPS) != 0 && NSEG == 1;  // two-segment launches are refused
+  constexpr bool RES_UP = (ABL & r3opt::RES_UP) != 0;
+  constexpr bool PACKED_HEAD = (ABL & r3opt::PACKED_HEAD) != 0;
+  constexpr bool CMAJ = (ABL & r3opt::CHUNK_MAJOR) != 0;
+  constexpr bool STAG = (ABL & r3opt::STAGGER) != 0;
+  constexpr bool DMA_DEL = (ABL & r3opt::DELAYED_DMA) != 0;
   static_assert(STAG ? NSTAGE == 3 : NSTAGE == 2, "W ring depth: 3 stages with the stagger, else 2");
   static_assert(NSEG == 1 || NSEG == 2, "segments");
   static_assert(EPI == EPI_STD || EPI == EPI_HEAD, "epilogue");
@@ -444,13 +465,11 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
   }
 
   r3_u32x4 raw[TM][2];  // A fragment of the next K-tile (f32 bits)
-  // ABL 16384 (one segment, C >= 32: a K-tile lies in one tap): the tap decode is wave-uniform
+  // FAST_A (one segment, C >= 32: a K-tile lies in one tap): the tap decode is wave-uniform
   // (scalar), and each lane keeps a validity bit per tap and sub-tile row and the byte offset of
   // its pixel + channel group, so an A address costs a bit test, an add and a select.
-  constexpr bool FAST_A = (ABL & 16384) != 0 && NSEG == 1;  // two-segment launches are refused
-  // chunk-major K order over segment 0 (a 3x3 window, checked at launch); segment 1 (the fused
+  // CMAJ: chunk-major K order over segment 0 (a 3x3 window, checked at launch); segment 1 (the fused
   // 1x1 downsample) keeps its order after it
-  constexpr bool CMAJ = (ABL & 524288) != 0;
   const int cmaj_tiles = NSEG == 2 ? a.kseg1 / BK : a.Kpad / BK;  // K-tiles of segment 0
   // first weight column of K-tile kt: tap * C + chunk * 32 (chunk-major) or kt * BK
   auto kcol = [&](int kt) -> int {
@@ -535,11 +554,7 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
 #pragma unroll
     for (int j = 0; j < NB; ++j) load_w_piece(j, kt, S);
   };
-  // ABL 2097152 (with the stagger; round 5): the delayed half also issues its SIMD partner's W pieces in
-  // the K loop (piece e = wave - NW / 2 + NW j), the leading half none: the delayed half (s_setprio 1)
-  // reached each barrier ~1,100 cycles early and idled there, the leading half now sheds its DMA issue
-  // (heads -2.2 %, same bits: profiles/r05ah_*)
-  constexpr bool DMA_DEL = (ABL & 2097152) != 0;
+  // DMA_DEL (r3opt::DELAYED_DMA): the delayed half's offsets of its SIMD partner's W pieces
   [[maybe_unused]] int boff_p[NB];
   if constexpr (DMA_DEL) {
     static_assert(NB_REM == 0 || TERMS == 1, "whole pieces per wave");
@@ -561,9 +576,9 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi) {
       if constexpr (TERMS == 1) {  // the high term alone
-        h[0][mi] = hi1h_x8<(ABL & 4096) != 0>(__builtin_bit_cast(x6_f32x4, raw[mi][0]),
-                                              __builtin_bit_cast(x6_f32x4, raw[mi][1]), as[mi]);
-      } else if constexpr ((ABL & 4096) != 0) {  // 2 VALU per value (split2h_x8)
+        h[0][mi] = hi1h_x8<MIX_SPLIT>(__builtin_bit_cast(x6_f32x4, raw[mi][0]),
+                                      __builtin_bit_cast(x6_f32x4, raw[mi][1]), as[mi]);
+      } else if constexpr (MIX_SPLIT) {  // 2 VALU per value (split2h_x8)
         split2h_x8(__builtin_bit_cast(x6_f32x4, raw[mi][0]), __builtin_bit_cast(x6_f32x4, raw[mi][1]), as[mi],
                    h[0][mi], h[1][mi]);
       } else {
@@ -585,7 +600,6 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
       for (int v = 0; v < 4; ++v) acc[mi][ni][v] = 0.f;
 
   const int bfo = c16 * BROW + ((g ^ swzB(c16)) << 4);  // this lane's W fragment in a block
-  constexpr int RA = (ABL & 8192) != 0 ? 3 : 2;  // W fragment blocks read ahead of their MFMAs
   constexpr int RS = RA + 1;
   static_assert(RA == 2 || STAG, "3-block read-ahead: with the stagger only");
   static_assert(!STAG || (TN % RS == 0 && TN % 2 == 0 && TN / 2 > RA), "stagger: W ring slots must repeat per tile");
@@ -612,7 +626,7 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
   }
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NA_OPS) : "memory");
   __builtin_amdgcn_s_barrier();
-  if constexpr ((ABL & 4) != 0) {
+  if constexpr (PRIO_HALF) {
     if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
   }
   const int wave_half = wave >= NW / 2 ? 1 : 0;  // SIMD partners: waves w and w + NW / 2
@@ -629,9 +643,9 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
       acc[mi][ni] = cc;
     }
   };
-  // stagger (see the ABL list): the K loop of one half of the waves, HB = the delayed half.
+  // stagger (r3opt::STAGGER): the K loop of one half of the waves, HB = the delayed half.
   // Interval i = the steps between barriers i - 1 and i; a block's interval-relative position r
-  // places the W DMA pieces (slot s at r = 2 + 2 s + HB, as ABL 256 spreads them) of tile i + 1.
+  // places the W DMA pieces (slot s at r = 2 + 2 s + HB, as r3opt::SPREAD_DMA spreads them) of tile i + 1.
   auto stag_loop = [&](auto hb_c) {
     constexpr bool HB = decltype(hb_c)::value;
     constexpr int H2 = TN / 2;
@@ -759,12 +773,11 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
     return;
   }
   if constexpr (EPI == EPI_HEAD) {  // reads only the constants' region: no barrier after the K loop
-    r3t_epilogue_head<TM, TN, NT, BN / 64, (ABL & 65536) != 0>(a, acc, smem + HS_OFF, m0 + wave * WM, n0, nt, tid,
-                                                              ainv);
+    r3t_epilogue_head<TM, TN, NT, BN / 64, PACKED_HEAD>(a, acc, smem + HS_OFF, m0 + wave * WM, n0, nt, tid, ainv);
   } else {
     __syncthreads();
-    r3t_epilogue_std<TM, TN, NT, (ABL & 32768) != 0, false, true>(a, acc, smem, m0 + wave * WM, m0, n0, lane, ainv,
-                                                                  nullptr, reinterpret_cast<const float*>(smem + HS_OFF));
+    r3t_epilogue_std<TM, TN, NT, RES_UP, false, true>(a, acc, smem, m0 + wave * WM, m0, n0, lane, ainv, nullptr,
+                                                      reinterpret_cast<const float*>(smem + HS_OFF));
   }
 }
 
@@ -776,19 +789,21 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_r3_kernel(const Conv
 // Launch-time checks of one conv_r3 launch (the kernel never bounds-checks these).
 template <int BM, int BN, int EPI, int ABL>
 inline int conv_r3_check(const ConvArgs& a) {
+  constexpr bool RES_UP = (ABL & r3opt::RES_UP) != 0;
+  constexpr bool SCALAR_TAPS = (ABL & r3opt::SCALAR_TAPS) != 0;
+  constexpr bool CMAJ = (ABL & r3opt::CHUNK_MAJOR) != 0;
   if (!a.wh || !a.winv || a.Kpad % 32 != 0 || (a.nseg == 2 && a.kseg1 % 32 != 0) || a.N % BN != 0 ||
-      (a.res_up && ((ABL & 32768) == 0 || a.res || a.nseg != 1))) {
+      (a.res_up && (!RES_UP || a.res || a.nseg != 1))) {
     set_error("conv_r3: K/N not aligned to the tile, no split weights or an upsampled residual (Kpad=%d kseg1=%d N=%d)", a.Kpad,
               a.kseg1, a.N);
     return SFA_E_UNSUPPORTED;
   }
-  if ((ABL & 16384) != 0 && (a.nseg != 1 || a.seg[0].C < 32 || a.seg[0].taps > 32)) {
+  if (SCALAR_TAPS && (a.nseg != 1 || a.seg[0].C < 32 || a.seg[0].taps > 32)) {
     set_error("conv_r3: fast A addressing needs one segment with C >= 32 (C=%d)", a.seg[0].C);
     return SFA_E_UNSUPPORTED;
   }
-  if ((ABL & 524288) != 0 && (a.seg[0].taps != 9 || a.seg[0].C % 32 != 0 ||
-                              (a.nseg == 2 ? a.kseg1 : a.Kpad) != 9 * a.seg[0].C || a.Kpad / 32 > 3600 ||
-                              a.wstride || a.wk0)) {
+  if (CMAJ && (a.seg[0].taps != 9 || a.seg[0].C % 32 != 0 || (a.nseg == 2 ? a.kseg1 : a.Kpad) != 9 * a.seg[0].C ||
+               a.Kpad / 32 > 3600 || a.wstride || a.wk0)) {
     set_error("conv_r3: chunk-major K order needs a 3x3 first segment with C %% 32 == 0 (C=%d Kpad=%d)", a.seg[0].C,
               a.Kpad);
     return SFA_E_UNSUPPORTED;

@@ -428,17 +428,29 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WN) * 64, OCC) conv_x6_kerne
 //   W rows BK bf16 per term: 32 B (BK 16, swz = (R >> 3) & 1) or 64 B (BK 32, (R >> 2) & 3)
 // DMA instructions (1 KiB each) are dealt round-robin to the waves; each wave waits for
 // its own with a counted vmcnt, then the barrier makes the whole stage visible.
-// ABL: diagnostic ablation bits for tools/convbench (0 in the product): 1 = no DMA in
-// the K loop, 2 = no A split (raw bits as terms), 4 = W fragments read once per k-step
-// group instead of per column block, 8 = no barrier, 16 = no epilogue (one sum per lane
-// stored), 64 = s_setprio 1 for the second half of the waves (the SIMD partners).
 // PREC 1: the fp16x3 form (two fp16 W terms, scaled A split into two fp16 terms when read,
 // products hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_f16).
+// ABL: diagnostic ablation bits for tools/convbench (0 in the product).
+namespace x6opt {
+constexpr int NO_LOOP_DMA = 1;   // no DMA in the K loop
+constexpr int NO_SPLIT = 2;      // no A split (raw bits as terms)
+constexpr int ONE_W_READ = 4;    // W fragments read once per k-step group instead of per column block
+constexpr int NO_BARRIER = 8;    // no barrier
+constexpr int NO_EPILOGUE = 16;  // no epilogue (one sum per lane stored)
+constexpr int PRIO_HALF = 64;    // s_setprio 1 for the second half of the waves (the SIMD partners)
+}  // namespace x6opt
+
 template <int BM, int BN, int WM, int EPI, int OCC, int BK = 16, int NSTAGE = 3, int ABL = 0,
           int WNT = BN, int PREC = 0>
 __global__ void __launch_bounds__((BM / WM) * (BN / WNT) * 64, OCC) conv_x6g_kernel(const ConvArgs a) {
   static_assert(BK == 16 || BK == 32, "BK");
   static_assert(NSTAGE == 2 || NSTAGE == 3, "ring depth");
+  constexpr bool LOOP_DMA = (ABL & x6opt::NO_LOOP_DMA) == 0;
+  constexpr bool SPLIT_A = (ABL & x6opt::NO_SPLIT) == 0;
+  constexpr bool ONE_W_READ = (ABL & x6opt::ONE_W_READ) != 0;
+  constexpr bool BARRIER = (ABL & x6opt::NO_BARRIER) == 0;
+  constexpr bool EPILOGUE = (ABL & x6opt::NO_EPILOGUE) == 0;
+  constexpr bool PRIO_HALF = (ABL & x6opt::PRIO_HALF) != 0;
   constexpr int WN = WNT;                 // BN: waves along M only (A split once)
   constexpr int WAVES_N = BN / WN;
   constexpr int NW = (BM / WM) * WAVES_N;
@@ -621,7 +633,7 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WNT) * 64, OCC) conv_x6g_ker
         const int q = 4 * s + 2 * h;  // logical f32 quads q, q + 1 hold k = 16s + 8h .. + 7
         const x6_f32x4 q0 = *reinterpret_cast<const x6_f32x4*>(S + R * AROW + ((q ^ swzA(R)) << 4));
         const x6_f32x4 q1 = *reinterpret_cast<const x6_f32x4*>(S + R * AROW + (((q + 1) ^ swzA(R)) << 4));
-        if constexpr (ABL & 2) {
+        if constexpr (!SPLIT_A) {
           const bf16x8_t raw = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(
                                                                __builtin_bit_cast(x6_u32x4, q0), __builtin_bit_cast(x6_u32x4, q1), 0, 2, 4, 6));
           af[0][mi] = raw;
@@ -638,7 +650,7 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WNT) * 64, OCC) conv_x6g_ker
       }
 #pragma unroll
       for (int ni = 0; ni < TN; ++ni) {
-        const int R = ((ABL & 4) ? 0 : wn * WN + ni * 32) + r;
+        const int R = (ONE_W_READ ? 0 : wn * WN + ni * 32) + r;
         const int byte = R * BROW + (((2 * s + h) ^ swzB(R)) << 4);
         bf16x8_t b0 = *reinterpret_cast<const bf16x8_t*>(SB + byte);
         bf16x8_t b1 = *reinterpret_cast<const bf16x8_t*>(SB + TERM_B + byte);
@@ -659,7 +671,7 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WNT) * 64, OCC) conv_x6g_ker
   };
 
   const int nk = a.Kpad / BK;
-  if constexpr ((ABL & 64) != 0) {
+  if constexpr (PRIO_HALF) {
     if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
   }
   if constexpr (NSTAGE == 3) {
@@ -671,21 +683,21 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WNT) * 64, OCC) conv_x6g_ker
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPW) : "memory");
       else
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPW - 1) : "memory");
-      if constexpr (!(ABL & 8)) __builtin_amdgcn_s_barrier();  // ... and every wave's: stage kt % 3 is complete
-      if constexpr (!(ABL & 1)) load_tile(kt + 2 < nk ? kt + 2 : nk - 1, smem + ((kt + 2) % 3) * STAGE);
+      if constexpr (BARRIER) __builtin_amdgcn_s_barrier();  // ... and every wave's: stage kt % 3 is complete
+      if constexpr (LOOP_DMA) load_tile(kt + 2 < nk ? kt + 2 : nk - 1, smem + ((kt + 2) % 3) * STAGE);
       compute(smem + (kt % 3) * STAGE);
     }
   } else {
     load_tile(0, smem);
     for (int kt = 0; kt < nk; ++kt) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile kt landed (this wave)
-      if constexpr (!(ABL & 8)) __builtin_amdgcn_s_barrier();  // every wave: stage kt & 1 complete, stage (kt+1) & 1 free
-      if constexpr (!(ABL & 1)) load_tile(kt + 1 < nk ? kt + 1 : nk - 1, smem + ((kt + 1) & 1) * STAGE);
+      if constexpr (BARRIER) __builtin_amdgcn_s_barrier();  // every wave: stage kt & 1 complete, stage (kt+1) & 1 free
+      if constexpr (LOOP_DMA) load_tile(kt + 1 < nk ? kt + 1 : nk - 1, smem + ((kt + 1) & 1) * STAGE);
       compute(smem + (kt & 1) * STAGE);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr ((ABL & 16) != 0) {
+  if constexpr (!EPILOGUE) {
     float t = 0.f;
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)

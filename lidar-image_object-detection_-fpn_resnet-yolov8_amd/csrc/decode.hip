@@ -316,9 +316,14 @@ __device__ int band_excl_scan(int v, int* wsum /*[kBandWaves]*/) {
   return before + x - v;
 }
 
-// ABL (timing ablations, tools/decodebench.hip only; results wrong): 1 = no sigmoid, 2 = no peak
-// test, 4 = no radix select (nothing selected), 8 = no band sort
-//
+// ABL: timing ablations of decode_band_topk_kernel (tools/decodebench.hip only; results wrong)
+namespace decopt {
+constexpr int NO_SIGMOID = 1;
+constexpr int NO_PEAK = 2;    // no peak test
+constexpr int NO_SELECT = 4;  // no radix select (nothing selected)
+constexpr int NO_SORT = 8;    // no band sort
+}  // namespace decopt
+
 // grid (S, C, B): band s = rows [s*R, min(H, s*R + R)) of class map (b, c).  The band's rows
 // plus a 1-row halo are staged in LDS with a -inf border (max_pool2d's padding: rows outside
 // the map and columns -1 / W), so the 3x3 peak test is nine unconditional reads.  Writes the
@@ -341,6 +346,10 @@ template <int ABL = 0, bool PEAK = true, bool TILED = false>
 __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
     const float* __restrict__ hm, int C, int H, int W, int K, int R, int apply_sigmoid,
     unsigned* __restrict__ bkey, int* __restrict__ bidx, TileGeo<TILED> geo) {
+  constexpr bool SIGMOID = (ABL & decopt::NO_SIGMOID) == 0;
+  constexpr bool PEAK_TEST = PEAK && (ABL & decopt::NO_PEAK) == 0;
+  constexpr bool SELECT = (ABL & decopt::NO_SELECT) == 0;
+  constexpr bool SORT = (ABL & decopt::NO_SORT) == 0;
   __shared__ __attribute__((aligned(16))) float tile[kBandMaxTile];
   __shared__ unsigned hist[256];
   __shared__ int wsum[kBandWaves];
@@ -375,7 +384,7 @@ __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
       if (i < n_tile) {
         const int r = i / TW, x = x0 + i - r * TW - 1, y = y0 - 1 + r;
         const bool in = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;  // not the border
-        tile[i] = (in && apply_sigmoid && !(ABL & 1)) ? sigmoid_clamp_f(v[j]) : v[j];
+        tile[i] = (in && apply_sigmoid && SIGMOID) ? sigmoid_clamp_f(v[j]) : v[j];
       }
     }
   }
@@ -395,7 +404,7 @@ __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
         const float* t = tile + (r + 1) * TW + x + 1;  // the pixel; neighbours at +-1, +-TW
         const float v = t[0];
         float m = v;
-        if (PEAK && !(ABL & 2)) {
+        if (PEAK_TEST) {
           const float a0 = fmaxf(fmaxf(t[-TW - 1], t[-TW]), t[-TW + 1]);
           const float a1 = fmaxf(t[-1], t[1]);
           const float a2 = fmaxf(fmaxf(t[TW - 1], t[TW]), t[TW + 1]);
@@ -412,9 +421,9 @@ __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
   }
   const int kk = min(K, nb);  // real candidates of this band
   // Radix select of the kk-th largest key.
-  unsigned prefix = (ABL & 4) ? 0xffffffffu : 0u, pmask = 0u;
-  int krem = (ABL & 4) ? 0 : kk;
-  for (int pass = 0; pass < ((ABL & 4) ? 0 : 4); ++pass) {
+  unsigned prefix = SELECT ? 0u : 0xffffffffu, pmask = 0u;
+  int krem = SELECT ? kk : 0;
+  for (int pass = 0; pass < (SELECT ? 4 : 0); ++pass) {
     const int shift = 24 - 8 * pass;
     for (int i = tid; i < 256; i += kBandThreads) hist[i] = 0u;
     __syncthreads();
@@ -501,7 +510,7 @@ __global__ void __launch_bounds__(kBandThreads) decode_band_topk_kernel(
   // that never rank into the top K: the merge kernel merges these lists
   const size_t out0 = (((size_t)b * C + c) * S + s) * K;
   for (int t = tid; t < K; t += kBandThreads) {
-    if (t < kk && !(ABL & 8)) {
+    if (t < kk && SORT) {
       const unsigned k = sel_key[t];
       const int ix = sel_idx[t];
       int r0 = 0, r1 = 0, r2 = 0, r3 = 0;  // four independent chains (LDS latency)

@@ -52,7 +52,7 @@ constexpr int LDS_BYTES = W_BYTES + 2 * PATCH_TERM + T_BYTES + WM_BYTES;  // 151
 // stem_pool_merge_kernel folds those in. A/B form (a.part == null, SFA_STEM_PATCH_ATOMIC=1):
 // cells with one writer (j, i in 1..7) are stored, the tile-border cells combined by
 // atomicMax on the f32 bits (values >= +0) into the zeroed pooled buffer, as
-// h3_pool_epilogue does. NOATOM (ablation ABL 16) applies to the A/B form only.
+// h3_pool_epilogue does. NOATOM (ablation stemopt::STORE_BORDERS) applies to the A/B form only.
 // ReLU(conv * 1/s * winv + b) of the wave's 32 rows into the tile T (row = 32 wave + q, q the
 // row within the wave: pixel (2 wave + q / 16, q % 16)), returns the lane's max. One rounding
 // (fmaf) per value, in both accumulator forms.
@@ -215,14 +215,27 @@ __device__ __forceinline__ void stem_stage_w(const ConvArgs& a, unsigned char* S
   }
 }
 
-// ABL (timing ablations only, env SFA_STEM_ABL; results wrong): 1 = no epilogue, 2 = no MFMAs,
-// 4 = no patch fetch, 8 = first patch fetched after the weights are staged,
-// 16 = border cells stored instead of atomicMax (only with a.part == null: the atomic A/B form),
-// 64 = the 32x32x16 MFMA form (round 1) instead of 16x16x32 (same products, other summation order)
+// ABL: timing ablations only (env SFA_STEM_ABL; results wrong).
+namespace stemopt {
+constexpr int NO_EPILOGUE = 1;
+constexpr int NO_MFMA = 2;
+constexpr int NO_FETCH = 4;     // no patch fetch
+constexpr int LATE_FETCH = 8;   // first patch fetched after the weights are staged
+// border cells stored instead of atomicMax (only with a.part == null: the atomic A/B form)
+constexpr int STORE_BORDERS = 16;
+// the 32x32x16 MFMA form (round 1) instead of 16x16x32 (same products, other summation order)
+constexpr int MFMA32 = 64;
+}  // namespace stemopt
+
 template <int ABL = 0, int IN = STEM_IN_NHWC4>
 __global__ void __launch_bounds__(512, 1) stem_patch_pool_kernel(const ConvArgs a, int ntiles) {
   using namespace stem_patch;
-  constexpr bool M16 = (ABL & 64) == 0;  // 16x16x32 MFMAs (default); ABL 64: the 32x32x16 form
+  constexpr bool EPILOGUE = (ABL & stemopt::NO_EPILOGUE) == 0;
+  constexpr bool MFMA = (ABL & stemopt::NO_MFMA) == 0;
+  constexpr bool FETCH = (ABL & stemopt::NO_FETCH) == 0;
+  constexpr bool LATE_FETCH = (ABL & stemopt::LATE_FETCH) != 0;
+  constexpr bool NOATOM = (ABL & stemopt::STORE_BORDERS) != 0;
+  constexpr bool M16 = (ABL & stemopt::MFMA32) == 0;  // 16x16x32 MFMAs (default)
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
   unsigned char* SW = smem;
   unsigned char* SU = smem + W_BYTES;                   // patch, 2 terms
@@ -300,14 +313,14 @@ __global__ void __launch_bounds__(512, 1) stem_patch_pool_kernel(const ConvArgs 
 
   const int G = gridDim.x;
   int tile = blockIdx.x;
-  if (!(ABL & 4) && !(ABL & 8)) {  // in flight while the weights are staged
+  if (FETCH && !LATE_FETCH) {  // in flight while the weights are staged
     if (tile < ntiles) fetch(tile, pf0);
     if (tile + G < ntiles) fetch(tile + G, pf1);
   }
   // weights: wh [2][64][Kpad] with k = (kh 7 + kw) 4 + c  ->  LDS [2][64][WROW] at k' = (kh 8 + kw) 4 + c
   stem_stage_w<NT, WROW>(a, SW, tid);
 
-  if (!(ABL & 4) && (ABL & 8)) {
+  if (FETCH && LATE_FETCH) {
     if (tile < ntiles) fetch(tile, pf0);
     if (tile + G < ntiles) fetch(tile + G, pf1);
   }
@@ -328,7 +341,7 @@ __global__ void __launch_bounds__(512, 1) stem_patch_pool_kernel(const ConvArgs 
     // patch (and, first time round, the weights) in LDS; every wave is past the previous
     // tile's epilogue reads of ST
     lds_barrier();
-    if (tile + 2 * G < ntiles && !(ABL & 4)) fetch(tile + 2 * G, cur);  // lands during the next tile
+    if (tile + 2 * G < ntiles && FETCH) fetch(tile + 2 * G, cur);  // lands during the next tile
 
     float mx;
     if constexpr (M16) {
@@ -344,7 +357,7 @@ __global__ void __launch_bounds__(512, 1) stem_patch_pool_kernel(const ConvArgs 
       const int abase16 = ((2 * (2 * wave)) * PW + 2 * c16 + 2 * g4) * 8;  // row block 0: conv row 2 wave
       const int bbase16 = c16 * WROW + 16 * g4;
 #pragma unroll
-      for (int s = 0; s < ((ABL & 2) ? 0 : KP / 32); ++s) {
+      for (int s = 0; s < (MFMA ? KP / 32 : 0); ++s) {
         f16x8_t ahi[2], alo[2];
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
@@ -375,7 +388,7 @@ __global__ void __launch_bounds__(512, 1) stem_patch_pool_kernel(const ConvArgs 
 #pragma unroll
         for (int v = 0; v < 16; ++v) acc[0][ni][v] = 0.f;
 #pragma unroll
-      for (int s = 0; s < ((ABL & 2) ? 0 : KP / 16); ++s) {
+      for (int s = 0; s < (MFMA ? KP / 16 : 0); ++s) {
         const int aoff = abase + ((s >> 1) * PW + 4 * (s & 1)) * 8;
         const f16x8_t ahi = *reinterpret_cast<const f16x8_t*>(SU + aoff);
         const f16x8_t alo = *reinterpret_cast<const f16x8_t*>(SU + PATCH_TERM + aoff);
@@ -395,12 +408,12 @@ __global__ void __launch_bounds__(512, 1) stem_patch_pool_kernel(const ConvArgs 
     }
     // the epilogue's own barrier (after its ST writes) also orders this tile's patch reads
     // before the next tile's patch stores
-    if constexpr ((ABL & 1) != 0) {
+    if constexpr (!EPILOGUE) {
       if (mx == 1234.5f) a.y[tid] = mx;
       __syncthreads();
     } else {
       const int tl = tile - b * tiles_per_frame, th = tl / tw_n;
-      stem_pool_epilogue<(ABL & 16) != 0>(a, mx, reinterpret_cast<float*>(ST), b, th, tl - th * tw_n, tid);
+      stem_pool_epilogue<NOATOM>(a, mx, reinterpret_cast<float*>(ST), b, th, tl - th * tw_n, tid);
     }
     // the next patch's max into WM (every wave read WM before this tile's lds_barrier)
     if (tile + G < ntiles) patch_max_to_lds(nxt);
@@ -430,8 +443,11 @@ __global__ void __launch_bounds__(512, 1) stem_patch_pool_kernel(const ConvArgs 
 //    ReLU(fmaf(acc, winv / s, b)) values: bit-identical output.
 //  * Per tile, between barriers: the previous tile's pooled row (stores), the next patch's split,
 //    this tile's MFMAs, its ReLU / horizontal maxima / exchange writes, the max of the patch two
-//    ahead. ABL 1: waves 4-7 issue their MFMAs first and the previous tile's stores and the split
-//    after them, so the two waves of a SIMD do not reach their MFMAs together.
+//    ahead. stem2opt::LATE_HALF: waves 4-7 issue their MFMAs first and the previous tile's stores and
+//    the split after them, so the two waves of a SIMD do not reach their MFMAs together.
+namespace stem2opt {
+constexpr int LATE_HALF = 1;  // set in the product
+}  // namespace stem2opt
 namespace stem_patch2 {
 using namespace stem_patch;
 constexpr int XCH_W = 9 * 64 * 4;                  // one wave's second-row horizontal maxima
@@ -445,6 +461,7 @@ template <int IN = STEM_IN_NHWC4, int ABL = 0>
 __global__ void __launch_bounds__(512, 1) stem_patch_pool2_kernel(const ConvArgs a, int ntiles) {
 #pragma clang fp contract(off)
   using namespace stem_patch2;
+  constexpr bool LATE_HALF = (ABL & stem2opt::LATE_HALF) != 0;
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS2];
   unsigned char* SW = smem;
   unsigned char* SU0 = smem + W_BYTES;                              // patch buffers: [2][2 terms]
@@ -628,7 +645,7 @@ __global__ void __launch_bounds__(512, 1) stem_patch_pool2_kernel(const ConvArgs
       ainv_next = split_patch(WMX + (par ^ 1) * NW, Rs, SUn);
       if (tile + 3 * G < ntiles) fetch(tile + 3 * G, Rs);
     };
-    const bool late = (ABL & 1) != 0 && wave >= NW / 2;
+    const bool late = LATE_HALF && wave >= NW / 2;
     if (!late) {
       finish_prev(par ^ 1);
       prep_next();
@@ -766,11 +783,15 @@ inline int launch_stem_patch_pool(const ConvArgs& a, hipStream_t st) {
       const int nt = nf * tpf;
       const dim3 gc((unsigned)(nt < ncu ? nt : ncu));
       switch (a.stem_in) {
-        case STEM_IN_NCHW3: hipLaunchKernelGGL((stem_patch_pool2_kernel<STEM_IN_NCHW3, 1>), gc, bd, 0, st, c, nt); break;
-        case STEM_IN_NCHW3_FLIP:
-          hipLaunchKernelGGL((stem_patch_pool2_kernel<STEM_IN_NCHW3_FLIP, 1>), gc, bd, 0, st, c, nt);
+        case STEM_IN_NCHW3:
+          hipLaunchKernelGGL((stem_patch_pool2_kernel<STEM_IN_NCHW3, stem2opt::LATE_HALF>), gc, bd, 0, st, c, nt);
           break;
-        default: hipLaunchKernelGGL((stem_patch_pool2_kernel<STEM_IN_NHWC4, 1>), gc, bd, 0, st, c, nt); break;
+        case STEM_IN_NCHW3_FLIP:
+          hipLaunchKernelGGL((stem_patch_pool2_kernel<STEM_IN_NCHW3_FLIP, stem2opt::LATE_HALF>), gc, bd, 0, st, c, nt);
+          break;
+        default:
+          hipLaunchKernelGGL((stem_patch_pool2_kernel<STEM_IN_NHWC4, stem2opt::LATE_HALF>), gc, bd, 0, st, c, nt);
+          break;
       }
       SFA_LAUNCH_CHECK();
     }

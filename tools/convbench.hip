@@ -271,7 +271,8 @@ int main(int argc, char** argv) {
       {"head tiny 3x3 8->5x64 (epilogue cost)", 16, 152, 152, 8, 3, 1, 1, 320, true, false},
   };
   // round 2: conv_r3_kernel (A in registers) against the round-1 defaults (first entry of each)
-  // round 3: strip-kernel ablations / variants on the body shapes (4096 = no W DMA in the K loop,
+  // round 3: strip-kernel ablations / variants on the body shapes (the numbers are the frozen round-3
+  // kernels' own bits, tools/experiments/r03/conv_h3s_kernel.h; 4096 = no W DMA in the K loop,
   // 32 = no epilogue; 14 = pre-split 128-wide, 26 = spread DMA)
   // 16384 = A prefetch: the next tap's fragments read and split during this tap's MFMAs
   std::vector<Cand> n64 = {

@@ -132,6 +132,16 @@ struct Cand {
 };
 static float* g_part = nullptr;
 static const size_t g_part_floats = 64u << 20;
+// The candidates pass their option masks as numbers: the labels ("abl142") are made from them, and recorded
+// outputs are matched by label. What each number is (h3sopt: conv_h3s_kernel.h, r3opt: conv_r3_kernel.h):
+static_assert(10 == h3sopt::ALWAYS && 142 == (h3sopt::ALWAYS | h3sopt::PRESPLIT | h3sopt::RES_PREFETCH) &&
+                  266 == (10 | h3sopt::REG_W) && 398 == (142 | h3sopt::REG_W),
+              "strip kernel masks");
+static_assert(526592 == (r3opt::ALWAYS | r3opt::CHUNK_MAJOR) &&  // conv.hip R3_BODY
+                  1603844 == (526592 | r3opt::PRIO_HALF | r3opt::MIX_SPLIT | r3opt::READ_AHEAD3 | r3opt::SCALAR_TAPS |
+                              r3opt::STAGGER) &&
+                  1669380 == (1603844 | r3opt::PACKED_HEAD),  // conv.hip R3_HEAD_STAG without DELAYED_DMA
+              "conv_r3 masks");
 #define CANDTK(BM, BN, WM, EPI, OCC, ABL, KS)                                                      \
   Cand {                                                                                          \
     "h3strip " #BM "x" #BN " w" #WM " occ" #OCC " abl" #ABL " ks" #KS, 32,                          \
@@ -150,7 +160,7 @@ static const size_t g_part_floats = 64u << 20;
       b.ksplit = KS;                                                                              \
       b.part = g_part;                                                                            \
       b.part_floats = g_part_floats;                                                              \
-      return launch_conv_h3_cfg<BM, BN, WM, EPI_STD, OCC, NK, NST, false, 2, 1>(b, s);             \
+      return launch_conv_h3_cfg<BM, BN, WM, EPI_STD, OCC, NK, NST, false, h3opt::PIPE, 1>(b, s);   \
     }                                                                                             \
   }
 // the fp16x3 stems (NCHW3 input planes, pooled output): band kernel / round-3 patch kernel + merge
@@ -194,7 +204,7 @@ int main(int argc, char** argv) {
       {"head L0 3x3 256->5x64", 16, 76, 76, 256, 3, 1, 1, 320, true, false},
       {"head tiny 3x3 8->5x64 (epilogue cost)", 16, 152, 152, 8, 3, 1, 1, 320, true, false},
   };
-  // round 4: register-staged W (ABL 256) against the product strip kernels, A B A B
+  // round 4: register-staged W (h3sopt::REG_W) against the product strip kernels, A B A B
   std::vector<Cand> n64 = {
       CANDTK(128, 64, 32, EPI_STD, 3, 142, 1), CANDTK(128, 64, 32, EPI_STD, 3, 398, 1),
       CANDTK(128, 64, 32, EPI_STD, 3, 142, 1), CANDTK(128, 64, 32, EPI_STD, 3, 398, 1),

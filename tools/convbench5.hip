@@ -128,6 +128,13 @@ struct Cand {
 static float* g_part = nullptr;
 static unsigned* g_tick = nullptr;  // split-K tickets (zeroed before every launch, as the forward's memset does)
 static const size_t g_part_floats = 64u << 20;
+// The candidates pass their option masks as numbers: the labels ("abl142") are made from them, and recorded
+// outputs are matched by label. What each number is (h3sopt: conv_h3s_kernel.h, r3opt: conv_r3_kernel.h):
+static_assert(10 == h3sopt::ALWAYS && 14 == (10 | h3sopt::PRESPLIT) && 142 == (14 | h3sopt::RES_PREFETCH),
+              "strip kernel masks");
+static_assert(1603844 == (r3opt::ALWAYS | r3opt::PRIO_HALF | r3opt::MIX_SPLIT | r3opt::READ_AHEAD3 |
+                          r3opt::SCALAR_TAPS | r3opt::CHUNK_MAJOR | r3opt::STAGGER),
+              "conv_r3 mask: conv.hip R3_HEAD_STAG without PACKED_HEAD and DELAYED_DMA");
 #define CS(BM, BN, WM, OCC, ABL, KS)                                                                  \
   Cand {                                                                                            \
     "h3s " #BM "x" #BN " occ" #OCC " abl" #ABL " ks" #KS, [](const ConvArgs& a, hipStream_t s) {      \
@@ -186,7 +193,7 @@ int main(int argc, char** argv) {
   // (late round 5: 256-row tiles, 8 waves, 1 / 2 blocks per CU: the W tile amortised over twice the rows)
   std::vector<Cand> l1 = {CS(128, 64, 32, 3, 142, 1), CS(256, 64, 32, 1, 142, 1), CS(256, 64, 32, 2, 142, 1),
                           CS(128, 64, 32, 3, 142, 1), CS(256, 64, 32, 1, 142, 1), CS(256, 64, 32, 2, 142, 1)};
-  // round 5: the pre-split strip (4) and the residual prefetch (128) on the 128-wide tiles
+  // round 5: the pre-split strip (h3sopt::PRESPLIT) and the residual prefetch (RES_PREFETCH) on the 128-wide tiles
   std::vector<Cand> l2 = {CS(128, 128, 32, 2, 10, 1), CS(128, 128, 32, 2, 14, 1), CS(128, 128, 32, 2, 142, 1),
                           CS(128, 128, 32, 2, 10, 1), CS(128, 128, 32, 2, 14, 1), CS(128, 128, 32, 2, 142, 1)};
   // round 5: the heads' register-A kernel (half-tile stagger, 3-stage W ring) on 256-wide tiles, the

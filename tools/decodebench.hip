@@ -72,6 +72,7 @@ int main(int argc, char** argv) {
   time("sfa_decode (band topk + merge)", [&] {
     sfa_decode(hm, off, dr, zz, dm, B, C, H, W, K, 1, dets, ws, wsb, nullptr);
   });
+  // the labels keep the numbers (decopt, decode.hip): 1 NO_SIGMOID, 2 NO_PEAK, 4 NO_SELECT, 8 NO_SORT
 #define BAND(ABL)                                                                                       \
   time("band_topk<" #ABL ">", [&] {                                                                     \
     hipLaunchKernelGGL(decode_band_topk_kernel<ABL>, dim3(S, C, B), dim3(kBandThreads), 0, 0, hm, C, H, W, K, R, 1, bk, bi, TileGeo<false>{}); \
@@ -82,6 +83,7 @@ int main(int argc, char** argv) {
   BAND(4);
   BAND(8);
   BAND(15);
+  static_assert(15 == (decopt::NO_SIGMOID | decopt::NO_PEAK | decopt::NO_SELECT | decopt::NO_SORT), "all four");
   // valid band lists for the merge (the ablations above leave garbage behind)
   hipLaunchKernelGGL(decode_band_topk_kernel<0>, dim3(S, C, B), dim3(kBandThreads), 0, 0, hm, C, H, W, K, R, 1, bk, bi, TileGeo<false>{});
   CK(hipDeviceSynchronize());

@@ -5,7 +5,7 @@
 // strip kernel; tools/convbench5.hip keeps the hook).
 //
 // Same products, K order, operand split, LDS images and epilogue arithmetic as conv_h3s_kernel with
-// the pre-split strip (ABL 4): bit-identical outputs.  What differs is the life of a workgroup.  The
+// the pre-split strip (h3sopt::PRESPLIT): bit-identical outputs.  What differs is the life of a workgroup.  The
 // strip kernel runs one 128-row output tile per workgroup, so every tile pays a prologue (row
 // decomposition with integer divisions, per-lane frame-scale loads, the first strip + W DMA and its
 // full latency before the first MFMA) and an epilogue drain (residual, stores, the per-frame maxima)

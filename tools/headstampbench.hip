@@ -82,7 +82,10 @@ static void split_weights_h3(const float* w, int N, int Kpad, uint16_t** wh, flo
 
 
 int main(int argc, char** argv) {
-  constexpr int R3_HEAD_STAG = 256 | 2048 | 4 | 4096 | 8192 | 16384 | 65536 | 524288 | 1048576 | 2097152;  // conv.hip (experiment bit)
+  constexpr int R3_HEAD_STAG = r3opt::ALWAYS | r3opt::PRIO_HALF | r3opt::MIX_SPLIT | r3opt::READ_AHEAD3 |
+                               r3opt::SCALAR_TAPS | r3opt::PACKED_HEAD | r3opt::CHUNK_MAJOR | r3opt::STAGGER |
+                               r3opt::DELAYED_DMA;  // conv.hip
+  static_assert(R3_HEAD_STAG == 3766532, "the product heads instance");
   struct Sh { const char* name; int H, C; };
   const Sh shapes[] = {{"L0", 76, 256}, {"L1", 152, 128}, {"L2", 152, 64}};
   const int hch[5] = {3, 2, 2, 1, 3}, nhead = 5, N = 320;
