@@ -219,10 +219,8 @@ int launch_amax_nhwc4(const float* x, int B, int H, int W, unsigned* amax, hipSt
     set_error("amax: batch %d too large", B);
     return SFA_E_INVALID;
   }
-  hipLaunchKernelGGL(amax_nhwc4_kernel, frame_grid(B, (long long)H * W), dim3(256), 0, st,
-                     reinterpret_cast<const float4*>(x), H * W, amax);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({frame_grid(B, (long long)H * W), 256, st}, amax_nhwc4_kernel, reinterpret_cast<const float4*>(x),
+                H * W, amax);
 }
 
 static int pow2_c4(int C, const char* what) {
@@ -239,11 +237,8 @@ int launch_maxpool3s2(const float* x, float* y, int B, int H, int W, int C, hipS
   const int lc = pow2_c4(C, "maxpool3s2");
   if (lc < 0) return SFA_E_UNSUPPORTED;
   SFA_CHECK_ARG(B <= 65535 && OH <= 65535, "maxpool3s2: grid too large");
-  hipLaunchKernelGGL(maxpool3s2_kernel, dim3((unsigned)((OW * (C / 4) + 255) / 256), (unsigned)OH, (unsigned)B),
-                     dim3(256), 0, st, reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), H, W,
-                     lc, OH, OW);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({dim3((unsigned)((OW * (C / 4) + 255) / 256), (unsigned)OH, (unsigned)B), 256, st}, maxpool3s2_kernel,
+                reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), H, W, lc, OH, OW);
 }
 
 int launch_upsample2x(const float* x, float* y, int B, int H, int W, int C, hipStream_t st) {
@@ -252,22 +247,17 @@ int launch_upsample2x(const float* x, float* y, int B, int H, int W, int C, hipS
   const int lc = pow2_c4(C, "upsample2x");
   if (lc < 0) return SFA_E_UNSUPPORTED;
   SFA_CHECK_ARG(B <= 65535 && 2 * H <= 65535, "upsample2x: grid too large");
-  hipLaunchKernelGGL(upsample2x_bilinear_kernel,
-                     dim3((unsigned)((2 * W * (C / 4) + 255) / 256), (unsigned)((2 * H + UP_ROWS - 1) / UP_ROWS), (unsigned)B),
-                     dim3(256), 0,
-                     st, reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), H, W, lc, sh, sw);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({dim3((unsigned)((2 * W * (C / 4) + 255) / 256), (unsigned)((2 * H + UP_ROWS - 1) / UP_ROWS), (unsigned)B), 256, st},
+                upsample2x_bilinear_kernel, reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), H, W, lc,
+                sh, sw);
 }
 
 int launch_kfpn(const float* L0, const float* L1, const float* L2, const KfpnOut& o, int B, int h,
                 int w, hipStream_t st) {
   SFA_CHECK_ARG(B <= 65535 && o.total_ch <= 65535, "kfpn: grid too large");
   SFA_CHECK_ARG(w % 4 == 0 && h % 2 == 0, "kfpn: head map %dx%d (width must be a multiple of 4)", h, w);
-  hipLaunchKernelGGL(kfpn_combine_kernel, dim3((unsigned)((h * w / 4 + 255) / 256), (unsigned)B, (unsigned)o.total_ch),
-                     dim3(256), 0, st, L0, L1, L2, o, B, h, w);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({dim3((unsigned)((h * w / 4 + 255) / 256), (unsigned)B, (unsigned)o.total_ch), 256, st},
+                kfpn_combine_kernel, L0, L1, L2, o, B, h, w);
 }
 
 // Plain resnet_18 heads (models/resnet.py:231-233): the fused-heads launch writes one channel-planar
@@ -295,10 +285,8 @@ __global__ void __launch_bounds__(256) heads_relayout_kernel(const float* __rest
 
 int launch_heads_relayout(const float* L, const KfpnOut& o, int B, int h, int w, hipStream_t st) {
   SFA_CHECK_ARG(B <= 65535 && o.total_ch <= 65535, "heads relayout: grid too large");
-  hipLaunchKernelGGL(heads_relayout_kernel, dim3((unsigned)((h * w + 255) / 256), (unsigned)B, (unsigned)o.total_ch),
-                     dim3(256), 0, st, L, o, B, h * w);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({dim3((unsigned)((h * w + 255) / 256), (unsigned)B, (unsigned)o.total_ch), 256, st},
+                heads_relayout_kernel, L, o, B, h * w);
 }
 
 __global__ void zero_words_kernel(uint4* __restrict__ p4, long long n4, unsigned* __restrict__ tail, int ntail) {
@@ -313,35 +301,26 @@ int launch_zero_words(void* p, size_t bytes, hipStream_t st) {
     set_error("zero_words: %zu bytes at %p (need 4-B multiples, 4-B aligned)", bytes, p);
     return SFA_E_INVALID;
   }
+  auto zero = [&](long long threads, char* p4, long long n4, char* tail, size_t tail_bytes) {
+    return launch({grid_of(threads), 256, st}, zero_words_kernel, reinterpret_cast<uint4*>(p4), n4,
+                  reinterpret_cast<unsigned*>(tail), (int)(tail_bytes / 4));
+  };
   // 16-B stores up to the first 16-B boundary's multiple, words for the rest
   char* c = reinterpret_cast<char*>(p);
   const size_t head = (16 - (reinterpret_cast<uintptr_t>(c) & 15)) & 15;
   if (head >= bytes || bytes - head < 16) {
-    const long long nw = (long long)(bytes / 4);
-    hipLaunchKernelGGL(zero_words_kernel, dim3(grid_of(nw)), dim3(256), 0, st, nullptr, 0ll,
-                       reinterpret_cast<unsigned*>(c), (int)nw);
-    SFA_LAUNCH_CHECK();
-    return SFA_OK;
+    return zero((long long)(bytes / 4), nullptr, 0, c, bytes);
   }
   const long long n4 = (long long)((bytes - head) / 16);
-  if (head) {  // the few words before the 16-B boundary (one extra launch only for unaligned starts)
-    hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, st, nullptr, 0ll, reinterpret_cast<unsigned*>(c),
-                       (int)(head / 4));
-    SFA_LAUNCH_CHECK();
-  }
+  if (head)  // the few words before the 16-B boundary (one extra launch only for unaligned starts)
+    if (int rc = zero(1, nullptr, 0, c, head)) return rc;
   const size_t done = head + (size_t)n4 * 16;
-  hipLaunchKernelGGL(zero_words_kernel, dim3(grid_of(n4 > 64 ? n4 : 64)), dim3(256), 0, st,
-                     reinterpret_cast<uint4*>(c + head), n4, reinterpret_cast<unsigned*>(c + done),
-                     (int)((bytes - done) / 4));
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return zero(n4 > 64 ? n4 : 64, c + head, n4, c + done, bytes - done);
 }
 
 int launch_sigmoid_clamp(float* x, long long n, hipStream_t st) {
   if (n <= 0) return SFA_OK;
-  hipLaunchKernelGGL(sigmoid_clamp_kernel, dim3(grid_of(n)), dim3(256), 0, st, x, n);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({grid_of(n), 256, st}, sigmoid_clamp_kernel, x, n);
 }
 
 }  // namespace sfa

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/sfa_hip.h"
+#include "host_math.h"
 
 namespace sfa {
 
@@ -32,25 +33,6 @@ void set_error(const char* fmt, ...);
       return SFA_E_HIP;                                                                    \
     }                                                                                      \
   } while (0)
-
-// Checks the launch that was just enqueued (configuration errors only; no sync).
-#define SFA_LAUNCH_CHECK()                                                                      \
-  do {                                                                                          \
-    hipError_t e_ = hipGetLastError();                                                          \
-    if (e_ != hipSuccess) {                                                                     \
-      ::sfa::set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                       __LINE__);                                                               \
-      return SFA_E_HIP;                                                                         \
-    }                                                                                           \
-  } while (0)
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-inline int ilog2(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return l;
-}
 
 // CU count of the device a stream runs on (persistent-grid sizing), cached per device: each slot is
 // written with the device's own answer, so concurrent first calls and launches on several devices

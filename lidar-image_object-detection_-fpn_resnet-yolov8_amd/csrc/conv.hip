@@ -1,5 +1,6 @@
 // Convolution dispatch: picks the kernel (fp16x3, bf16x6 or f32 MFMA) and its tile
-// configuration per layer shape (conv_*_kernel.h).
+// configuration per layer shape (conv_*_kernel.h). tile_rows, pick_ksplit and strip_ok, which the
+// rules below ask, are conv_plan.h's.
 #include <cstdlib>
 
 #include "conv_kernel.h"
@@ -12,12 +13,6 @@
 #include "stem_patch_kernel.h"
 
 namespace sfa {
-
-// Tile choices are priced at the bench batch (16 frames of the launch's geometry), never at
-// a.M: different kernels sum in different orders, so a choice by the batch's row count would
-// let a frame's result depend on the batch it is computed in (tests/test_gpu_model.py
-// test_batch_invariance_608 holds every path to bit-identical frames across batches).
-static long long tile_rows(const ConvArgs& a) { return 16LL * a.OH * a.OW; }
 
 // bf16x6 tiles per shape, from tools/convbench.hip sweeps on MI355X (round 1):
 // wide-N tiles amortise the A split; 8-wave LDS-DMA tiles for the big-M layers.
@@ -40,23 +35,6 @@ static int launch_conv_x6(const ConvArgs& a, int epilogue, hipStream_t st) {
     if (!ok(rc)) rc = launch_conv_x6g_cfg<128, 128, 32, EPI_STD, 2>(a, st);
   }
   return rc;
-}
-
-// Split-K slices of a 128 x 128-tiled body conv (fp16x3, standard epilogue with bias): 2 for the
-// 512-wide (layer4) convs, whose 184 output tiles cannot fill 256 CUs (-13..16 %), combined by
-// splitk_reduce_kernel. Chosen from the conv width only, so a frame's arithmetic never depends
-// on its batch. (Balanced split counts with the slices combined in the kernel were measured 35 %
-// slower: tools/experiments/r03, profiles/r03e_ab_splitk_inkernel.txt.)
-static int pick_ksplit(const ConvArgs& a) {
-  if (!a.part || !a.bias || a.wstride || a.wk0 || a.res_up) return 1;
-  return a.N >= 512 ? 2 : 1;
-}
-
-// One-segment 3x3 / stride 1 / pad 1 conv with 32-channel chunks: conv_h3s_kernel applies.
-static bool strip_ok(const ConvArgs& a) {
-  const ConvSeg& g = a.seg[0];
-  return a.nseg == 1 && g.KH == 3 && g.KW == 3 && g.stride == 1 && g.pad == 1 && g.C >= 32 &&
-         (g.C & 31) == 0 && a.Kpad == 9 * g.C && a.OH == g.H && a.OW == g.W;
 }
 
 // fp16x3 kernels per shape (tools/convbench.hip sweeps). Round 4 keeps only
@@ -140,7 +118,7 @@ template <int TERMS>
 static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
   static_assert(TERMS == 1 || TERMS == 2, "fp16 terms per operand");
   if (!a.wh || !a.winv) return SFA_E_UNSUPPORTED;
-  const bool sliced = a.wstride || a.wk0 || a.res_up;  // conv_h3_kernel reads these; the others do not
+  const bool sliced = conv_sliced(a);  // conv_h3_kernel reads these; the others do not
   if (TERMS == 1 && sliced) return SFA_E_UNSUPPORTED;
   auto ok = [](int rc) { return rc != SFA_E_UNSUPPORTED; };
   int rc = SFA_E_UNSUPPORTED;
@@ -211,41 +189,8 @@ static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
 }
 
 int launch_conv(const ConvArgs& a, int epilogue, int math, hipStream_t st) {
-  // Host-side shape checks: the kernels assume these and never bounds-check them.
-  if (a.N <= 0 || a.N % 64 != 0 || a.M <= 0 || a.Kpad <= 0 || a.Kpad % 16 != 0) {
-    set_error("conv: unsupported shape M=%d N=%d Kpad=%d", a.M, a.N, a.Kpad);
-    return SFA_E_UNSUPPORTED;
-  }
-  for (int s = 0; s < a.nseg; ++s) {
-    const ConvSeg& g = a.seg[s];
-    if (!g.x || g.C < 4 || (g.C & (g.C - 1)) || (1 << g.logC) != g.C || g.KW <= 0 || g.KH <= 0) {
-      set_error("conv: bad segment %d (C=%d)", s, g.C);
-      return SFA_E_UNSUPPORTED;
-    }
-    if (g.bytes == 0 || g.bytes >= (1u << 31)) {
-      set_error("conv: segment %d input is empty or >= 2 GiB (32-bit buffer offsets)", s);
-      return SFA_E_UNSUPPORTED;
-    }
-    if (g.C < 16 && s != a.nseg - 1) {
-      set_error("conv: narrow-channel segment must be last");
-      return SFA_E_UNSUPPORTED;
-    }
-  }
-  if (a.nseg == 2 && (a.kseg1 % 16 != 0 || a.kseg1 <= 0 || a.kseg1 >= a.Kpad)) {
-    set_error("conv: bad kseg1 %d", a.kseg1);
-    return SFA_E_UNSUPPORTED;
-  }
-  if (a.wstride || a.wk0 || a.res_up) {  // K-sliced weights / half-res residual: conv_h3_kernel only
-    if (math != SFA_MATH_FP16X3 || epilogue != EPI_STD) {
-      set_error("conv: K-sliced weights / upsampled residual need fp16x3 and the standard epilogue");
-      return SFA_E_UNSUPPORTED;
-    }
-    if (a.res_up && (a.OH % 2 || a.OW % 2 || a.res)) {
-      set_error("conv: upsampled residual needs even output dims and no full-res residual");
-      return SFA_E_UNSUPPORTED;
-    }
-    return launch_conv_h<2>(a, epilogue, st);
-  }
+  if (int rc = conv_shape_check(a, epilogue, math)) return rc;
+  if (conv_sliced(a)) return launch_conv_h<2>(a, epilogue, st);  // K-sliced weights / half-res residual
   if (math == SFA_MATH_FP16) {  // never fails where fp16x3 succeeds: shapes without a one-product kernel run fp16x3
     const int rc = launch_conv_h<1>(a, epilogue, st);
     if (rc != SFA_E_UNSUPPORTED) return rc;

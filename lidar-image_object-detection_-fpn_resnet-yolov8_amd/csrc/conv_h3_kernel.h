@@ -732,58 +732,32 @@ static __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ConvArg
   }
 }
 
+// The slices' partials of a split-K conv combined by the reduce launch.
+inline int launch_splitk_reduce(const ConvArgs& a, hipStream_t st) {
+  const long long nel = (long long)a.M * a.N;
+  return launch({(unsigned)((nel + 1023) / 1024), 256, st}, splitk_reduce_kernel, a);
+}
+
 template <int BM, int BN, int WM, int EPI, int OCC, int BK, int NSTAGE, bool NMAJ = false, int ABL = 0,
           int MF = 0, int WN = BN, int TERMS = 2>
 inline int launch_conv_h3_cfg(const ConvArgs& a, hipStream_t st) {
-  if (!a.wh || !a.winv || a.Kpad % BK != 0 || (a.nseg == 2 && a.kseg1 % BK != 0) || a.N % BN != 0) {
-    set_error("conv_h3: K/N not aligned to the tile or no split weights (Kpad=%d kseg1=%d N=%d)", a.Kpad,
-              a.kseg1, a.N);
-    return SFA_E_UNSUPPORTED;
-  }
-  if (a.wstride && (a.wstride < a.wk0 + a.Kpad || a.wk0 % 8 != 0)) {
-    set_error("conv_h3: K slice [%d, %d) outside the weight rows (stride %d)", a.wk0, a.wk0 + a.Kpad, a.wstride);
-    return SFA_E_INVALID;
-  }
-  if (2ull * a.N * (a.wstride ? a.wstride : a.Kpad) * 2ull >= (1ull << 31)) {
-    set_error("conv_h3: split weights >= 2 GiB");
-    return SFA_E_UNSUPPORTED;
-  }
-  const int ks = a.ksplit > 1 ? a.ksplit : 1;
-  if (ks > 1 && (EPI != EPI_STD || (a.Kpad / BK) % ks != 0 || !a.part ||
-                 (size_t)ks * a.M * a.N > a.part_floats || a.N % 4 != 0)) {
-    set_error("conv_h3: split-K %d unsupported here (Kpad=%d N=%d)", ks, a.Kpad, a.N);
-    return SFA_E_UNSUPPORTED;
-  }
-  const long long nblocks = (long long)ceil_div(a.M, BM) * (a.N / BN) * ks;
-  if (nblocks <= 0 || nblocks > 0x7fffffffll) {
-    set_error("conv_h3: bad grid (M=%d N=%d)", a.M, a.N);
-    return SFA_E_INVALID;
-  }
+  unsigned grid;
+  if (int rc = conv_h3_check(a, BM, BN, BK, EPI, TERMS, &grid)) return rc;
   ConvArgs c = a;  // the row decomposition's multiply-high divisions
   c.fd_ow = make_fast_div((unsigned)a.OW);
   c.fd_oh = make_fast_div((unsigned)a.OH);
-  if (a.res_up) {  // FPN skip convs (one segment): the instance with the upsampled-residual epilogue
-    if (a.nseg != 1 || TERMS != 2) {
-      set_error("conv_h3: upsampled residual with two K-segments or the one-product form");
-      return SFA_E_UNSUPPORTED;
-    }
+  const LaunchCfg cfg{grid, (BM / WM) * (BN / WN) * 64, st};
+  int rc = SFA_OK;
+  if (a.res_up) {  // FPN skip convs (one segment, fp16x3): the instance with the upsampled-residual epilogue
     if constexpr (TERMS == 2)
-      hipLaunchKernelGGL((conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, 1, NMAJ, ABL, MF, WN, true>),
-                         dim3((unsigned)nblocks), dim3((BM / WM) * (BN / WN) * 64), 0, st, c);
-  } else if (a.nseg == 2) {
-    hipLaunchKernelGGL((conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, 2, NMAJ, ABL, MF, WN, false, TERMS>),
-                       dim3((unsigned)nblocks), dim3((BM / WM) * (BN / WN) * 64), 0, st, c);
+      rc = launch(cfg, conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, 1, NMAJ, ABL, MF, WN, true>, c);
   } else {
-    hipLaunchKernelGGL((conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, 1, NMAJ, ABL, MF, WN, false, TERMS>),
-                       dim3((unsigned)nblocks), dim3((BM / WM) * (BN / WN) * 64), 0, st, c);
+    rc = with_bool(a.nseg == 2, [&](auto TWO) {
+      return launch(cfg, conv_h3_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, TWO.value ? 2 : 1, NMAJ, ABL, MF, WN, false, TERMS>, c);
+    });
   }
-  SFA_LAUNCH_CHECK();
-  if (ks > 1) {  // the slices' partials combined by the reduce launch (element-strided partials: no tickets)
-    const long long nel = (long long)a.M * a.N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((nel + 1023) / 1024)), dim3(256), 0, st, a);
-    SFA_LAUNCH_CHECK();
-  }
-  return SFA_OK;
+  if (rc != SFA_OK || ksplit_of(a) == 1) return rc;
+  return launch_splitk_reduce(a, st);  // element-strided partials: no tickets
 }
 
 }  // namespace sfa

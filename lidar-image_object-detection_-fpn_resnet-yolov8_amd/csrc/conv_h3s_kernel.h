@@ -506,54 +506,16 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
 
 template <int BM, int BN, int WM, int EPI, int OCC, int ABL = 0, int TERMS = 2>
 inline int launch_conv_h3s_cfg(const ConvArgs& a, hipStream_t st) {
-  const ConvSeg& g = a.seg[0];
-  const int ks = a.ksplit > 1 ? a.ksplit : 1;
-  if (!a.wh || !a.winv || a.nseg != 1 || g.KH != 3 || g.KW != 3 || g.stride != 1 || g.pad != 1 || g.C < 32 ||
-      (g.C & 31) != 0 || a.Kpad != 9 * g.C || a.OH != g.H || a.OW != g.W || a.N % BN != 0) {
-    set_error("conv_h3s: not a one-segment 3x3/s1/p1 conv with C %% 32 == 0 (C=%d Kpad=%d N=%d)", g.C, a.Kpad,
-              a.N);
-    return SFA_E_UNSUPPORTED;
-  }
-  // The pre-split strip (presplit) knows two fp16x3 scales per block, those of the frames of its first
-  // row and the next one, while the epilogue scales every row back by its own frame's: a block must not
-  // reach a third frame. With frames of at least BM rows none does. The bound is the largest product
-  // tile's (128 rows) for every tile shape, so which kernel a map takes, and with it a frame's bits,
-  // depends on the map's size alone, never on the batch; smaller maps take the caller's next kernel,
-  // which looks every row's frame up. (Frames of equal binary exponent hid this: a 2^9 x brighter third
-  // frame was split with its neighbour's scale, overflowed fp16 and came out as zeros after the ReLU.)
-  constexpr int MIN_FRAME_ROWS = BM > 128 ? BM : 128;
-  if (a.OH * a.OW < MIN_FRAME_ROWS) {
-    set_error("conv_h3s: frames of %d rows are shorter than %d", a.OH * a.OW, MIN_FRAME_ROWS);
-    return SFA_E_UNSUPPORTED;
-  }
-  if (ks > 1 && (EPI != EPI_STD || (3 * (g.C >> 5)) % ks != 0 || !a.part ||
-                 (size_t)ks * a.M * a.N > a.part_floats || a.N % 4 != 0)) {
-    set_error("conv_h3s: split-K %d unsupported here (C=%d N=%d)", ks, g.C, a.N);
-    return SFA_E_UNSUPPORTED;
-  }
-  if (2ull * a.N * a.Kpad * 2ull >= (1ull << 31)) {
-    set_error("conv_h3s: split weights >= 2 GiB");
-    return SFA_E_UNSUPPORTED;
-  }
-  const long long nblocks = (long long)ceil_div(a.M, BM) * (a.N / BN) * ks;
-  if (nblocks <= 0 || nblocks > 0x7fffffffll) {
-    set_error("conv_h3s: bad grid (M=%d N=%d)", a.M, a.N);
-    return SFA_E_INVALID;
-  }
+  unsigned grid;
+  if (int rc = conv_h3s_check(a, BM, BN, EPI, &grid)) return rc;
+  const int ks = ksplit_of(a);
   ConvArgs b = a;  // the strip rows' multiply-high divisions
-  b.fd_w = make_fast_div((unsigned)g.W);
-  b.fd_h = make_fast_div((unsigned)g.H);
+  b.fd_w = make_fast_div((unsigned)a.seg[0].W);
+  b.fd_h = make_fast_div((unsigned)a.seg[0].H);
   // tickets only with one word per output tile in the array: else the reduce launch
-  if (ks == 1 || (long long)ceil_div(a.M, BM) * (a.N / BN) > (long long)a.tile_cnt_words) b.tile_cnt = nullptr;
-  hipLaunchKernelGGL((conv_h3s_kernel<BM, BN, WM, EPI, OCC, ABL, TERMS>), dim3((unsigned)nblocks), dim3((BM / WM) * 64), 0,
-                     st, b);
-  SFA_LAUNCH_CHECK();
-  if (ks > 1 && !b.tile_cnt) {  // the slices' partials combined by the reduce launch
-    const long long nel = (long long)a.M * a.N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((nel + 1023) / 1024)), dim3(256), 0, st, a);
-    SFA_LAUNCH_CHECK();
-  }
-  return SFA_OK;
+  if (ks == 1 || grid / ks > (long long)a.tile_cnt_words) b.tile_cnt = nullptr;
+  if (int rc = launch({grid, (BM / WM) * 64, st}, conv_h3s_kernel<BM, BN, WM, EPI, OCC, ABL, TERMS>, b)) return rc;
+  return ks > 1 && !b.tile_cnt ? launch_splitk_reduce(a, st) : SFA_OK;
 }
 
 }  // namespace sfa

@@ -18,6 +18,8 @@
 #pragma once
 
 #include "conv.h"
+#include "conv_plan.h"
+#include "dispatch.h"
 
 namespace sfa {
 
@@ -306,22 +308,9 @@ __global__ void __launch_bounds__(256, OCC) conv_mfma_kernel(const ConvArgs a) {
 
 template <int BM, int BN, int WM, int WN, int BK, int EPI, int OCC, bool GLDS = false, int ABL = 0>
 inline int launch_conv_cfg(const ConvArgs& a, hipStream_t st) {
-  if (a.Kpad % BK != 0 || (a.nseg == 2 && a.kseg1 % BK != 0) || a.N % BN != 0) {
-    set_error("conv: K/N not aligned to the tile (Kpad=%d kseg1=%d N=%d, BK=%d BN=%d)", a.Kpad,
-              a.kseg1, a.N, BK, BN);
-    return SFA_E_UNSUPPORTED;
-  }
-  const int mt = ceil_div(a.M, BM);
-  const int nt = a.N / BN;
-  const long long nblocks = (long long)mt * nt;
-  if (nblocks <= 0 || nblocks > 0x7fffffffll) {
-    set_error("conv: bad grid (M=%d N=%d)", a.M, a.N);
-    return SFA_E_INVALID;
-  }
-  hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, BK, EPI, OCC, GLDS, ABL>), dim3((unsigned)nblocks),
-                     dim3(256), 0, st, a);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  unsigned grid;
+  if (int rc = conv_f32_check(a, BM, BN, BK, &grid)) return rc;
+  return launch({grid, 256, st}, conv_mfma_kernel<BM, BN, WM, WN, BK, EPI, OCC, GLDS, ABL>, a);
 }
 
 }  // namespace sfa

@@ -786,76 +786,21 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_r3_kernel(const Conv
   conv_r3_body<BM, BN, WM, EPI, OCC, NSTAGE, NSEG, ABL, TERMS>(a, xcd_remap(blockIdx.x, gridDim.x));
 }
 
-// Launch-time checks of one conv_r3 launch (the kernel never bounds-checks these).
-template <int BM, int BN, int EPI, int ABL>
-inline int conv_r3_check(const ConvArgs& a) {
-  constexpr bool RES_UP = (ABL & r3opt::RES_UP) != 0;
-  constexpr bool SCALAR_TAPS = (ABL & r3opt::SCALAR_TAPS) != 0;
-  constexpr bool CMAJ = (ABL & r3opt::CHUNK_MAJOR) != 0;
-  if (!a.wh || !a.winv || a.Kpad % 32 != 0 || (a.nseg == 2 && a.kseg1 % 32 != 0) || a.N % BN != 0 ||
-      (a.res_up && (!RES_UP || a.res || a.nseg != 1))) {
-    set_error("conv_r3: K/N not aligned to the tile, no split weights or an upsampled residual (Kpad=%d kseg1=%d N=%d)", a.Kpad,
-              a.kseg1, a.N);
-    return SFA_E_UNSUPPORTED;
-  }
-  if (SCALAR_TAPS && (a.nseg != 1 || a.seg[0].C < 32 || a.seg[0].taps > 32)) {
-    set_error("conv_r3: fast A addressing needs one segment with C >= 32 (C=%d)", a.seg[0].C);
-    return SFA_E_UNSUPPORTED;
-  }
-  if (CMAJ && (a.seg[0].taps != 9 || a.seg[0].C % 32 != 0 || (a.nseg == 2 ? a.kseg1 : a.Kpad) != 9 * a.seg[0].C ||
-               a.Kpad / 32 > 3600 || a.wstride || a.wk0)) {
-    set_error("conv_r3: chunk-major K order needs a 3x3 first segment with C %% 32 == 0 (C=%d Kpad=%d)", a.seg[0].C,
-              a.Kpad);
-    return SFA_E_UNSUPPORTED;
-  }
-  for (int s = 0; s < a.nseg; ++s)
-    if (a.seg[s].C < 8) {  // a lane's 8 k values must be 8 channels of one input pixel
-      set_error("conv_r3: segment %d has C=%d < 8", s, a.seg[s].C);
-      return SFA_E_UNSUPPORTED;
-    }
-  if (a.wstride && (a.wstride < a.wk0 + a.Kpad || a.wk0 % 8 != 0)) {
-    set_error("conv_r3: K slice [%d, %d) outside the weight rows (stride %d)", a.wk0, a.wk0 + a.Kpad, a.wstride);
-    return SFA_E_INVALID;
-  }
-  if (2ull * a.N * (a.wstride ? a.wstride : a.Kpad) * 2ull >= (1ull << 31)) {
-    set_error("conv_r3: split weights >= 2 GiB");
-    return SFA_E_UNSUPPORTED;
-  }
-  const int ks = a.ksplit > 1 ? a.ksplit : 1;
-  if (ks > 1 && (EPI != EPI_STD || (a.Kpad / 32) % ks != 0 || !a.part ||
-                 (size_t)ks * a.M * a.N > a.part_floats || a.N % 4 != 0)) {
-    set_error("conv_r3: split-K %d unsupported here (Kpad=%d N=%d)", ks, a.Kpad, a.N);
-    return SFA_E_UNSUPPORTED;
-  }
-  return SFA_OK;
-}
-
 template <int BM, int BN, int WM, int EPI, int OCC, int NSTAGE, int ABL = 0, int TERMS = 2>
 inline int launch_conv_r3_cfg(const ConvArgs& a, hipStream_t st) {
-  const int crc = conv_r3_check<BM, BN, EPI, ABL>(a);
-  if (crc != SFA_OK) return crc;
-  const int ks = a.ksplit > 1 ? a.ksplit : 1;
-  const long long nblocks = (long long)ceil_div(a.M, BM) * (a.N / BN) * ks;
-  if (nblocks <= 0 || nblocks > 0x7fffffffll) {
-    set_error("conv_r3: bad grid (M=%d N=%d)", a.M, a.N);
-    return SFA_E_INVALID;
-  }
+  unsigned grid;
+  if (int rc = conv_r3_check(a, BM, BN, EPI, (ABL & r3opt::RES_UP) != 0, (ABL & r3opt::SCALAR_TAPS) != 0,
+                             (ABL & r3opt::CHUNK_MAJOR) != 0, &grid))
+    return rc;
   ConvArgs b = a;  // the row decomposition's multiply-high divisions
   b.fd_ow = make_fast_div((unsigned)a.OW);
   b.fd_oh = make_fast_div((unsigned)a.OH);
-  if (a.nseg == 2)
-    hipLaunchKernelGGL((conv_r3_kernel<BM, BN, WM, EPI, OCC, NSTAGE, 2, ABL, TERMS>), dim3((unsigned)nblocks),
-                       dim3((BM / WM) * 64), 0, st, b);
-  else
-    hipLaunchKernelGGL((conv_r3_kernel<BM, BN, WM, EPI, OCC, NSTAGE, 1, ABL, TERMS>), dim3((unsigned)nblocks),
-                       dim3((BM / WM) * 64), 0, st, b);
-  SFA_LAUNCH_CHECK();
-  if (ks > 1) {  // the slices' partials combined by the reduce launch
-    const long long nel = (long long)a.M * a.N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((nel + 1023) / 1024)), dim3(256), 0, st, a);
-    SFA_LAUNCH_CHECK();
-  }
-  return SFA_OK;
+  const int rc = with_bool(a.nseg == 2, [&](auto TWO) {
+    return launch({grid, (BM / WM) * 64, st}, conv_r3_kernel<BM, BN, WM, EPI, OCC, NSTAGE, TWO.value ? 2 : 1, ABL, TERMS>,
+                  b);
+  });
+  if (rc != SFA_OK || ksplit_of(a) == 1) return rc;
+  return launch_splitk_reduce(a, st);
 }
 
 }  // namespace sfa

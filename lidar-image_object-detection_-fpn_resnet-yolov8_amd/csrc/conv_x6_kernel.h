@@ -25,6 +25,8 @@
 #include <type_traits>
 
 #include "conv.h"
+#include "conv_plan.h"
+#include "dispatch.h"
 
 namespace sfa {
 
@@ -715,48 +717,17 @@ __global__ void __launch_bounds__((BM / WM) * (BN / WNT) * 64, OCC) conv_x6g_ker
 template <int BM, int BN, int WM, int EPI, int OCC, int BK = 16, int NSTAGE = 3, int ABL = 0,
           int WNT = BN, int PREC = 0>
 inline int launch_conv_x6g_cfg(const ConvArgs& a, hipStream_t st) {
-  if (!(PREC ? a.wh != nullptr && a.winv != nullptr : a.wx != nullptr) || a.Kpad % BK != 0 || (a.nseg == 2 && a.kseg1 % BK != 0) || a.N % BN != 0) {
-    set_error("conv_x6g: K/N not aligned to the tile or no split weights (Kpad=%d kseg1=%d N=%d)",
-              a.Kpad, a.kseg1, a.N);
-    return SFA_E_UNSUPPORTED;
-  }
-  if (3ull * a.N * a.Kpad * 2ull >= (1ull << 31)) {
-    set_error("conv_x6g: split weights >= 2 GiB");
-    return SFA_E_UNSUPPORTED;
-  }
-  const long long nblocks = (long long)ceil_div(a.M, BM) * (a.N / BN);
-  if (nblocks <= 0 || nblocks > 0x7fffffffll) {
-    set_error("conv_x6g: bad grid (M=%d N=%d)", a.M, a.N);
-    return SFA_E_INVALID;
-  }
-  hipLaunchKernelGGL((conv_x6g_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, ABL, WNT, PREC>),
-                     dim3((unsigned)nblocks), dim3((BM / WM) * (BN / WNT) * 64), 0, st, a);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  unsigned grid;
+  if (int rc = conv_x6_check("conv_x6g", a, PREC ? a.wh && a.winv : a.wx != nullptr, BM, BN, BK, &grid)) return rc;
+  return launch({grid, (BM / WM) * (BN / WNT) * 64, st}, conv_x6g_kernel<BM, BN, WM, EPI, OCC, BK, NSTAGE, ABL, WNT, PREC>,
+                a);
 }
 
 template <int BM, int BN, int WM, int WN, int BK, int EPI, int OCC>
 inline int launch_conv_x6_cfg(const ConvArgs& a, hipStream_t st) {
-  if (!a.wx || a.Kpad % BK != 0 || (a.nseg == 2 && a.kseg1 % BK != 0) || a.N % BN != 0) {
-    set_error("conv_x6: K/N not aligned to the tile or no split weights (Kpad=%d kseg1=%d N=%d)",
-              a.Kpad, a.kseg1, a.N);
-    return SFA_E_UNSUPPORTED;
-  }
-  if (3ull * a.N * a.Kpad * 2ull >= (1ull << 31)) {
-    set_error("conv_x6: split weights >= 2 GiB");
-    return SFA_E_UNSUPPORTED;
-  }
-  const int mt = ceil_div(a.M, BM);
-  const long long nblocks = (long long)mt * (a.N / BN);
-  if (nblocks <= 0 || nblocks > 0x7fffffffll) {
-    set_error("conv_x6: bad grid (M=%d N=%d)", a.M, a.N);
-    return SFA_E_INVALID;
-  }
-  constexpr int NT = (BM / WM) * (BN / WN) * 64;
-  hipLaunchKernelGGL((conv_x6_kernel<BM, BN, WM, WN, BK, EPI, OCC>), dim3((unsigned)nblocks), dim3(NT),
-                     0, st, a);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  unsigned grid;
+  if (int rc = conv_x6_check("conv_x6", a, a.wx != nullptr, BM, BN, BK, &grid)) return rc;
+  return launch({grid, (BM / WM) * (BN / WN) * 64, st}, conv_x6_kernel<BM, BN, WM, WN, BK, EPI, OCC>, a);
 }
 
 }  // namespace sfa

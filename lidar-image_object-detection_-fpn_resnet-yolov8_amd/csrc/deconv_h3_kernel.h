@@ -238,36 +238,12 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) deconv_h3_kernel(const De
 // four waves of 32 rows, two blocks per CU.
 inline int launch_deconv_h3_cfg(const DeconvArgs& a, int B, hipStream_t st) {
   constexpr int BM = 128, BN = 128, WM = 32;
-  if (!a.x || !a.wh || !a.winv || !a.bias || !a.y || B < 1 || a.H < 1 || a.W < 1) {
-    set_error("deconv: null argument or empty input");
-    return SFA_E_INVALID;
-  }
-  if (a.C < 32 || (a.C & (a.C - 1)) || (1 << a.logC) != a.C || a.K != 4 * a.C || a.N % BN != 0 || a.N <= 0) {
-    set_error("deconv: unsupported shape C=%d N=%d K=%d", a.C, a.N, a.K);
-    return SFA_E_UNSUPPORTED;
-  }
-  const unsigned long long in_bytes = (unsigned long long)B * a.H * a.W * a.C * 4ull;
-  const unsigned long long out_elems = (unsigned long long)B * a.H * a.W * 4ull * a.N;
-  if (in_bytes >= (1ull << 31) || in_bytes != a.bytes || (unsigned long long)a.M != (unsigned long long)B * a.H * a.W ||
-      out_elems >= (1ull << 40) || a.H >= 16384 || a.W >= 16384) {
-    set_error("deconv: input (%d, %d, %d, %d) is >= 2 GiB (32-bit buffer offsets) or inconsistent", B, a.H, a.W, a.C);
-    return SFA_E_UNSUPPORTED;
-  }
-  if (4ull * a.N * a.K * 2ull >= (1ull << 31)) {
-    set_error("deconv: split weights >= 2 GiB");
-    return SFA_E_UNSUPPORTED;
-  }
-  const long long nblocks = 4ll * ceil_div(a.M, BM) * (a.N / BN);
-  if (nblocks > 0x7fffffffll) {
-    set_error("deconv: bad grid (M=%d N=%d)", a.M, a.N);
-    return SFA_E_INVALID;
-  }
+  unsigned grid;
+  if (int rc = deconv_check(a, B, BM, BN, &grid)) return rc;
   DeconvArgs c = a;
   c.fd_w = make_fast_div((unsigned)a.W);
   c.fd_h = make_fast_div((unsigned)a.H);
-  hipLaunchKernelGGL((deconv_h3_kernel<BM, BN, WM, 2>), dim3((unsigned)nblocks), dim3((BM / WM) * 64), 0, st, c);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({grid, (BM / WM) * 64, st}, deconv_h3_kernel<BM, BN, WM, 2>, c);
 }
 
 }  // namespace sfa

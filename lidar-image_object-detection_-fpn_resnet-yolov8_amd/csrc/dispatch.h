@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "common.h"
+#include "conv_args.h"
 
 namespace sfa {
 
@@ -33,6 +34,16 @@ int with_bev_layout(int layout, F&& f) {
 template <typename F>
 int with_f32_layout(int layout, F&& f) {
   return layout == SFA_BEV_NHWC4_F32 ? f(int_c<SFA_BEV_NHWC4_F32>{}) : f(int_c<SFA_BEV_NCHW3_F32>{});
+}
+
+// the patch stem's three input layouts (conv_args.h StemInput)
+template <typename F>
+int with_stem_in(int stem_in, F&& f) {
+  switch (stem_in) {
+    case STEM_IN_NCHW3: return f(int_c<STEM_IN_NCHW3>{});
+    case STEM_IN_NCHW3_FLIP: return f(int_c<STEM_IN_NCHW3_FLIP>{});
+    default: return f(int_c<STEM_IN_NHWC4>{});
+  }
 }
 
 struct LaunchCfg {

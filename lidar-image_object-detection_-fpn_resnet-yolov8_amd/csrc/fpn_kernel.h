@@ -260,18 +260,12 @@ template <int K, int BN, bool RU, int OCC>
 inline int launch_fpn_gemm_cfg(const ConvArgs& a, hipStream_t st) {
   using G = FpnGeom<K, BN, RU, OCC>;
   static_assert(OCC * G::LDS <= 160 * 1024, "blocks per CU vs LDS");
-  const ConvSeg& g = a.seg[0];
-  if (a.nseg != 1 || g.KH != 1 || g.KW != 1 || g.stride != 1 || g.pad != 0 || g.C != K || a.Kpad != K ||
-      a.N % BN != 0 || !a.wh || !a.winv || a.res || a.ksplit > 1 || a.OH != g.H || a.OW != g.W ||
-      (a.res_up != nullptr) != RU || (a.wstride && (a.wstride < a.wk0 + K || a.wk0 % 8 != 0))) {
+  if (!fpn_1x1_ok(a, K, BN) || (a.res_up != nullptr) != RU) {
     set_error("fpn_gemm: not a 1x1 conv with C = %d (N=%d)", K, a.N);
     return SFA_E_UNSUPPORTED;
   }
   const int P = a.OH * a.OW;
-  if (2ull * a.N * (a.wstride ? a.wstride : a.Kpad) * 2ull >= (1ull << 31)) {
-    set_error("fpn_gemm: weights >= 2 GiB");
-    return SFA_E_UNSUPPORTED;
-  }
+  if (int rc = check_weight_bytes("fpn_gemm", 2, a.N, weight_row(a), "weights")) return rc;
   const int frames = (a.M + P - 1) / P;
   if (frames > kFpnMaxFrames) {
     // the per-frame scale table holds kFpnMaxFrames frames: launch frame chunks of that size. A row's
@@ -302,10 +296,7 @@ inline int launch_fpn_gemm_cfg(const ConvArgs& a, hipStream_t st) {
   int gx = (ncu * OCC + n_nt - 1) / n_nt;  // blocks per column tile
   if (gx > n_mt) gx = n_mt;
   if (gx < 1) return SFA_OK;
-  hipLaunchKernelGGL((fpn_gemm_kernel<K, BN, RU, OCC>), dim3((unsigned)gx, (unsigned)n_nt), dim3(G::NT), 0, st, a,
-                     n_mt);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({dim3((unsigned)gx, (unsigned)n_nt), G::NT, st}, fpn_gemm_kernel<K, BN, RU, OCC>, a, n_mt);
 }
 
 
@@ -508,21 +499,15 @@ __global__ void __launch_bounds__(256, OCC) fpn_row_kernel(const ConvArgs a, int
 template <int K, int RB, int OCC>
 inline int launch_fpn_row_cfg(const ConvArgs& a, hipStream_t st) {
   using namespace fpn_row;
-  const ConvSeg& g = a.seg[0];
-  if (a.nseg != 1 || g.KH != 1 || g.KW != 1 || g.stride != 1 || g.pad != 0 || g.C != K || a.Kpad != K ||
-      a.N % NB != 0 || !a.wh || !a.winv || a.res || !a.res_up || a.ksplit > 1 || a.OH != g.H || a.OW != g.W ||
-      a.OH % 2 || a.OW % 2 || a.OW > 16 * RB || (a.wstride && (a.wstride < a.wk0 + K || a.wk0 % 8 != 0)))
-    return SFA_E_UNSUPPORTED;
+  if (!fpn_skip_ok(a, K, NB) || a.OW > 16 * RB) return SFA_E_UNSUPPORTED;
   const int frames = a.M / (a.OH * a.OW);
   if (frames <= 0) return SFA_OK;
-  if ((size_t)frames * (a.OH / 2) * (a.OW / 2) * a.N * 4 >= (1ull << 31)) return SFA_E_UNSUPPORTED;
+  if (!frames_fit(frames, (size_t)(a.OH / 2) * (a.OW / 2) * a.N)) return SFA_E_UNSUPPORTED;
   const int ncu = cu_count(st);
   const int nct = a.N / NB;
   int segs = (OCC * ncu + frames * nct - 1) / (frames * nct);  // about OCC blocks per CU
   segs = segs < 1 ? 1 : (segs > a.OH ? a.OH : segs);
-  hipLaunchKernelGGL((fpn_row_kernel<K, RB, OCC>), dim3((unsigned)(frames * segs * nct)), dim3(NT), 0, st, a, segs);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({(unsigned)(frames * segs * nct), NT, st}, fpn_row_kernel<K, RB, OCC>, a, segs);
 }
 
 // FPN skip convs of the narrow levels (round 5): fpn_row_kernel walks one output
@@ -719,15 +704,10 @@ template <int K, int OCC>
 inline int launch_fpn_seg_cfg(const ConvArgs& a, hipStream_t st) {
   using namespace fpn_seg;
   static_assert(OCC * lds_bytes(K) <= 160 * 1024, "blocks per CU vs LDS");
-  const ConvSeg& g = a.seg[0];
-  if (a.nseg != 1 || g.KH != 1 || g.KW != 1 || g.stride != 1 || g.pad != 0 || g.C != K || a.Kpad != K ||
-      a.N % NB != 0 || !a.wh || !a.winv || a.res || !a.res_up || a.ksplit > 1 || a.OH != g.H || a.OW != g.W ||
-      a.OH % 2 || a.OW % 2 || a.OW / 2 > WHMAX || (a.wstride && (a.wstride < a.wk0 + K || a.wk0 % 8 != 0)))
-    return SFA_E_UNSUPPORTED;
+  if (!fpn_skip_ok(a, K, NB) || a.OW / 2 > WHMAX) return SFA_E_UNSUPPORTED;
   const int frames = a.M / (a.OH * a.OW);
   if (frames <= 0) return SFA_OK;
-  if ((size_t)frames * a.OH * a.OW * K * 4 >= (1ull << 31) ||
-      (size_t)frames * (a.OH / 2) * (a.OW / 2) * a.N * 4 >= (1ull << 31))
+  if (!frames_fit(frames, (size_t)a.OH * a.OW * K) || !frames_fit(frames, (size_t)(a.OH / 2) * (a.OW / 2) * a.N))
     return SFA_E_UNSUPPORTED;
   const int ncu = cu_count(st);
   const int nct = a.N / NB;
@@ -744,9 +724,7 @@ inline int launch_fpn_seg_cfg(const ConvArgs& a, hipStream_t st) {
       if (max(hi, hi2) - lo + 1 > NSLOT || (p + P < pe && lo2 < lo)) return SFA_E_UNSUPPORTED;
     }
   }
-  hipLaunchKernelGGL((fpn_seg_kernel<K, OCC>), dim3((unsigned)(frames * segs * nct)), dim3(NT), 0, st, a, segs);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({(unsigned)(frames * segs * nct), NT, st}, fpn_seg_kernel<K, OCC>, a, segs);
 }
 
 // the skip conv of each KFPN level by its input channel count (the 608-input widths 152 / 76 / 38 and

@@ -15,6 +15,7 @@
 // Arithmetic is IEEE f64 with no FMA contraction (pragma below + -ffp-contract=off), so every
 // box, confidence and keep decision is bit-identical to the Python reference.
 #include "common.h"
+#include "dispatch.h"
 
 // Plain f64 operators under contract(off): hipcc's default -ffp-contract=fast would
 // fuse m1*i1 + m2*i2 into an FMA (HIP's __dadd_rn/__dmul_rn are plain operators in a
@@ -274,11 +275,8 @@ extern "C" int sfa_iou_matrix(const int32_t* boxes_a, int na, const int32_t* box
                 "iou_matrix: bad arguments");
   const long long n = (long long)na * nb;
   if (n == 0) return SFA_OK;
-  hipLaunchKernelGGL(iou_matrix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const int4*>(boxes_a),
-                     na, reinterpret_cast<const int4*>(boxes_b), nb, out);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({(unsigned)((n + 255) / 256), 256, reinterpret_cast<hipStream_t>(stream)}, iou_matrix_kernel,
+                reinterpret_cast<const int4*>(boxes_a), na, reinterpret_cast<const int4*>(boxes_b), nb, out);
 }
 
 extern "C" int sfa_fuse_detections(int batch, const int32_t* yolo_boxes, const double* yolo_conf,
@@ -296,13 +294,10 @@ extern "C" int sfa_fuse_detections(int batch, const int32_t* yolo_boxes, const d
                 "fuse: bad mode %d", params->mode);
   FuseArgs a{params->conf_threshold, params->fusion_iou_threshold, params->nms_threshold,
              params->mode, params->apply_nms};
-  hipLaunchKernelGGL(fuse_kernel, dim3(batch), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const int4*>(yolo_boxes), yolo_conf, yolo_cls, yolo_offsets,
-                     reinterpret_cast<const int4*>(sfa_boxes), sfa_conf, sfa_offsets, a,
-                     reinterpret_cast<int4*>(out_boxes), out_conf, out_cls, out_src, out_origin,
-                     out_match, out_count, out_keep, out_keep_count);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({batch, 64, reinterpret_cast<hipStream_t>(stream)}, fuse_kernel,
+                reinterpret_cast<const int4*>(yolo_boxes), yolo_conf, yolo_cls, yolo_offsets,
+                reinterpret_cast<const int4*>(sfa_boxes), sfa_conf, sfa_offsets, a, reinterpret_cast<int4*>(out_boxes),
+                out_conf, out_cls, out_src, out_origin, out_match, out_count, out_keep, out_keep_count);
 }
 
 extern "C" int sfa_gaussian_nms(int batch, const int32_t* boxes, double* conf, const int32_t* starts,
@@ -310,9 +305,6 @@ extern "C" int sfa_gaussian_nms(int batch, const int32_t* boxes, double* conf, c
   SFA_CHECK_ARG(batch >= 0 && (batch == 0 || (boxes && conf && starts && counts)), "gaussian_nms: bad arguments");
   SFA_CHECK_ARG(sigma > 0.0, "gaussian_nms: sigma must be > 0 (got %g)", sigma);
   if (batch == 0) return SFA_OK;
-  hipLaunchKernelGGL(gaussian_nms_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), batch, reinterpret_cast<const int4*>(boxes), conf,
-                     starts, counts, sigma);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({(unsigned)((batch + 3) / 4), 256, reinterpret_cast<hipStream_t>(stream)}, gaussian_nms_kernel, batch,
+                reinterpret_cast<const int4*>(boxes), conf, starts, counts, sigma);
 }

@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "dispatch.h"
 
 #pragma clang fp contract(off)
 
@@ -340,11 +341,8 @@ extern "C" int sfa_post_process(const float* dets, int batch, int K, const sfa_p
   SFA_CHECK_ARG(params->num_classes >= 0 && params->bev_h > 0 && params->bev_w > 0 &&
                     params->arith >= SFA_REAL_F32 && params->arith <= SFA_REAL_F64,
                 "post_process: bad params");
-  hipLaunchKernelGGL(post_process_kernel, dim3(1), dim3(64 * kWaves), 0,
-                     reinterpret_cast<hipStream_t>(stream), dets, batch, K, *params, out_preds,
-                     out_real, out_offsets);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({1, 64 * kWaves, reinterpret_cast<hipStream_t>(stream)}, post_process_kernel, dets, batch, K, *params,
+                out_preds, out_real, out_offsets);
 }
 
 extern "C" int sfa_project_boxes(const double* real, const float* preds, const int32_t* offsets,
@@ -358,12 +356,9 @@ extern "C" int sfa_project_boxes(const double* real, const float* preds, const i
   SFA_CHECK_ARG(params->conf_source == SFA_CONF_CLASS_ID ||
                     (params->conf_source == SFA_CONF_SCORE && preds),
                 "project_boxes: SFA_CONF_SCORE needs preds");
-  hipLaunchKernelGGL(project_boxes_kernel, dim3(1), dim3(64 * kWaves), 0,
-                     reinterpret_cast<hipStream_t>(stream), real, preds, offsets, batch, calib,
-                     *params, reinterpret_cast<int4*>(out_boxes), out_conf, out_row, out_extent,
-                     out_offsets);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({1, 64 * kWaves, reinterpret_cast<hipStream_t>(stream)}, project_boxes_kernel, real, preds, offsets,
+                batch, calib, *params, reinterpret_cast<int4*>(out_boxes), out_conf, out_row, out_extent,
+                out_offsets);
 }
 
 static bool argo_cam(const double* T_l2c, const double* P2, ArgoCam* c) {
@@ -384,12 +379,9 @@ extern "C" int sfa_argo_project_boxes(const float* preds, const int32_t* offsets
   if (capacity == 0) return SFA_OK;
   SFA_CHECK_ARG(preds && out_pixels && out_all8, "argo_project_boxes: null buffer");
   const int threads = capacity * 8;
-  hipLaunchKernelGGL(argo_project_boxes_kernel, dim3((threads + 255) / 256), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), preds, offsets, batch, capacity, (float)boundary[1],
-                     (float)boundary[2], (float)boundary[4], (float)discretization, cam, out_pixels, out_all8,
-                     out_corners3d);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return launch({(threads + 255) / 256, 256, reinterpret_cast<hipStream_t>(stream)}, argo_project_boxes_kernel, preds,
+                offsets, batch, capacity, (float)boundary[1], (float)boundary[2], (float)boundary[4],
+                (float)discretization, cam, out_pixels, out_all8, out_corners3d);
 }
 
 extern "C" int sfa_argo_project_points(const void* points, int points_f64, int64_t n, const double* T_l2c,
@@ -398,14 +390,10 @@ extern "C" int sfa_argo_project_points(const void* points, int points_f64, int64
   SFA_CHECK_ARG(n >= 0 && n <= (1ll << 30) && argo_cam(T_l2c, P2, &cam), "argo_project_points: bad arguments");
   if (n == 0) return SFA_OK;
   SFA_CHECK_ARG(points && out_pixels, "argo_project_points: null buffer");
-  const dim3 g((unsigned)((n + 255) / 256)), b(256);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (points_f64)
-    hipLaunchKernelGGL(argo_project_points_kernel<double>, g, b, 0, st, reinterpret_cast<const double*>(points), n,
-                       cam, out_pixels);
-  else
-    hipLaunchKernelGGL(argo_project_points_kernel<float>, g, b, 0, st, reinterpret_cast<const float*>(points), n, cam,
-                       out_pixels);
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  return with_bool(points_f64 != 0, [&](auto F64) {
+    using T = std::conditional_t<F64.value, double, float>;
+    return launch({(unsigned)((n + 255) / 256), 256, reinterpret_cast<hipStream_t>(stream)},
+                  argo_project_points_kernel<T>,
+                  reinterpret_cast<const T*>(points), n, cam, out_pixels);
+  });
 }

@@ -735,78 +735,47 @@ __global__ void __launch_bounds__(512, 1) stem_patch_pool2_kernel(const ConvArgs
   finish_prev((k - 1) & 1);
 }
 
-// Grid = one block per CU (each loops over tiles); needs the stem's fp16x3 split weights
-// (Kpad >= 196), the input as a.stem_in says (seg 0 describes it as 4 channels), conv output
-// divisible into 16 x 16 tiles.
+// Grid = one block per CU (each loops over tiles); stem_patch_check (conv_plan.h) names what it needs.
 inline int launch_stem_patch_pool(const ConvArgs& a, hipStream_t st) {
+  if (int rc = stem_patch_check(a)) return rc;
   const ConvSeg& g = a.seg[0];
-  if (!a.wh || !a.winv || a.nseg != 1 || a.N != 64 || g.C != 4 || g.KH != 7 || g.KW != 7 || g.stride != 2 ||
-      g.pad != 3 || a.Kpad < 196 || a.OH % 16 != 0 || a.OW % 16 != 0 || a.OH * 2 != g.H || a.OW * 2 != g.W ||
-      a.res || !a.relu || (a.part && a.part_floats < (size_t)a.M / 256 * 17 * 64)) {
-    set_error("stem_patch: unsupported stem (C=%d k=%d OH=%d OW=%d)", g.C, g.KH, a.OH, a.OW);
-    return SFA_E_UNSUPPORTED;
-  }
   const int frames = a.M / (a.OH * a.OW);
   const int ntiles = frames * (a.OH / 16) * (a.OW / 16);
   const int ncu = cu_count(st);
-  const int grid = ntiles < ncu ? ntiles : ncu;
-  if (grid <= 0) return SFA_OK;
-  const dim3 gd((unsigned)grid), bd(stem_patch::NT);
+  if (ntiles <= 0) return SFA_OK;
+  const dim3 bd(stem_patch::NT);
   // the one-barrier kernel with waves 4-7 issuing their MFMAs first (it reads NCHW3 planes as
   // aligned float4 column groups); an NCHW3 input that is not 16-B aligned takes the round-3a
   // three-barrier kernel (4-B plane reads). The timing ablations and the rejected variants live in
   // tools/experiments/r03/stem_patch_kernel.h.
-  const bool al16 = (reinterpret_cast<uintptr_t>(a.seg[0].x) & 15) == 0;
-  if (!a.part) {
-    set_error("stem_patch: the pooled tile-border parts need the side buffer (a.part)");
-    return SFA_E_INVALID;
-  }
+  const bool al16 = (reinterpret_cast<uintptr_t>(g.x) & 15) == 0;
   if (al16 || a.stem_in == STEM_IN_NHWC4) {
-    // the kernel reads the input through a buffer resource with 32-bit offsets: batches whose input
-    // reaches 2 GiB run in frame chunks (the side-buffer slots keep their global tile index)
-    const size_t fbytes = (size_t)(a.stem_in == STEM_IN_NHWC4 ? 4 : 3) * g.H * g.W * 4;
-    const int fchunk = (int)std::min<size_t>((size_t)frames, ((1ull << 31) - 1) / fbytes);
-    if (fchunk < 1) {
-      set_error("stem_patch: one %d x %d frame exceeds the 32-bit buffer offsets", g.H, g.W);
-      return SFA_E_UNSUPPORTED;
-    }
-    const int tpf = (a.OH / 16) * (a.OW / 16);
-    for (int f0 = 0; f0 < frames; f0 += fchunk) {
-      const int nf = std::min(fchunk, frames - f0);
+    StemChunks plan;
+    if (int rc = stem_chunk_plan(frames, a.stem_in == STEM_IN_NHWC4 ? 4 : 3, g.H, g.W, &plan)) return rc;
+    for (int i = 0; i < plan.count(); ++i) {
+      const StemChunk k = stem_chunk(plan, i, g.H, g.W);
       ConvArgs c = a;
-      c.seg[0].x = g.x + (size_t)f0 * (fbytes / 4);
-      c.seg[0].bytes = (size_t)nf * fbytes;
-      c.y = a.y + (size_t)f0 * (a.OH / 2) * (a.OW / 2) * 64;
-      c.part = a.part + (size_t)f0 * tpf * 17 * 64;
-      if (a.amax_out) c.amax_out = a.amax_out + (size_t)f0 * SFA_AMAX_WORDS;
-      c.M = nf * a.OH * a.OW;
-      const int nt = nf * tpf;
-      const dim3 gc((unsigned)(nt < ncu ? nt : ncu));
-      switch (a.stem_in) {
-        case STEM_IN_NCHW3:
-          hipLaunchKernelGGL((stem_patch_pool2_kernel<STEM_IN_NCHW3, stem2opt::LATE_HALF>), gc, bd, 0, st, c, nt);
-          break;
-        case STEM_IN_NCHW3_FLIP:
-          hipLaunchKernelGGL((stem_patch_pool2_kernel<STEM_IN_NCHW3_FLIP, stem2opt::LATE_HALF>), gc, bd, 0, st, c, nt);
-          break;
-        default:
-          hipLaunchKernelGGL((stem_patch_pool2_kernel<STEM_IN_NHWC4, stem2opt::LATE_HALF>), gc, bd, 0, st, c, nt);
-          break;
-      }
-      SFA_LAUNCH_CHECK();
+      c.seg[0].x = g.x + k.x_floats;
+      c.seg[0].bytes = k.x_bytes;
+      c.y = a.y + k.y_floats;
+      c.part = a.part + k.part_floats;
+      if (a.amax_out) c.amax_out = a.amax_out + (size_t)k.f0 * SFA_AMAX_WORDS;
+      c.M = k.frames * a.OH * a.OW;
+      const int rc = with_stem_in(a.stem_in, [&](auto IN) {
+        return launch({std::min(k.tiles, ncu), bd, st}, stem_patch_pool2_kernel<IN.value, stem2opt::LATE_HALF>, c,
+                      k.tiles);
+      });
+      if (rc != SFA_OK) return rc;
     }
-  } else if (a.stem_in == STEM_IN_NCHW3) {
-    hipLaunchKernelGGL((stem_patch_pool_kernel<0, STEM_IN_NCHW3>), gd, bd, 0, st, a, ntiles);
   } else {
-    hipLaunchKernelGGL((stem_patch_pool_kernel<0, STEM_IN_NCHW3_FLIP>), gd, bd, 0, st, a, ntiles);
+    const int rc = with_bool(a.stem_in == STEM_IN_NCHW3, [&](auto PLAIN) {
+      return launch({std::min(ntiles, ncu), bd, st},
+                    stem_patch_pool_kernel<0, PLAIN.value ? STEM_IN_NCHW3 : STEM_IN_NCHW3_FLIP>, a, ntiles);
+    });
+    if (rc != SFA_OK) return rc;
   }
-  SFA_LAUNCH_CHECK();
-  {
-    const long long n = (long long)ntiles * 15 * 16;
-    hipLaunchKernelGGL(stem_pool_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, frames);
-  }
-  SFA_LAUNCH_CHECK();
-  return SFA_OK;
+  const long long n = (long long)ntiles * 15 * 16;
+  return launch({(unsigned)((n + 255) / 256), 256, st}, stem_pool_merge_kernel, a, frames);
 }
 
 }  // namespace sfa

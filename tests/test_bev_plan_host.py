@@ -1,7 +1,9 @@
 """The host-only plan checks, built with ASan + UBSan and run as stand-alone programs:
-tools/bev_plan_check.cpp (csrc/bev_plan.h: the voxelisers' paths and scratch regions) and
-tools/decode_plan_check.cpp (csrc/decode_plan.h: tile plans and workspace layouts).  CPU only:
-the headers are plain C++, so neither program needs HIP or a GPU."""
+tools/bev_plan_check.cpp (csrc/bev_plan.h: the voxelisers' paths and scratch regions),
+tools/decode_plan_check.cpp (csrc/decode_plan.h: tile plans and workspace layouts) and
+tools/conv_plan_check.cpp (csrc/conv_args.h, csrc/conv_plan.h: the conv launchers' checks, the stem's
+frame chunks, the dispatch predicates).  CPU only: the headers are plain C++, so no program needs HIP
+or a GPU."""
 import os
 import shutil
 import subprocess
@@ -11,7 +13,8 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("name,expect", [("bev_plan_check", " plans, 0 bad"), ("decode_plan_check", " 0 bad")])
+@pytest.mark.parametrize("name,expect", [("bev_plan_check", " plans, 0 bad"), ("decode_plan_check", " 0 bad"),
+                                         ("conv_plan_check", " checks, 0 bad")])
 def test_plan_check_under_host_sanitizers(tmp_path, name, expect):
     gxx = shutil.which("g++")
     if gxx is None:

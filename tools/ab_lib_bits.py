@@ -20,18 +20,19 @@ sys.path.insert(0, os.path.join(REPO, "lidar-image_object-detection_-fpn_resnet-
 
 SMALL = [(2, 96, 96), (3, 160, 192)]  # multiples of 32 with more than one tile per map at every level
 BIG = (10, 608, 608)  # the big-M conv_r3 body tiles and the tile_rows >= 50000 branches
+L4STRIP = (1, 384, 384)  # the smallest input whose layer4 maps (144 rows) take the strip kernel: split-K 2 and its tickets
 # (tag, setup, cases): setup is a list of (what, argument), applied to a fresh engine through the
 # runtime's public setters. The default-option fp16x3 maps keep their bare keys.
 CONFIGS = [
-    ("", [], SMALL + [BIG]),
-    ("fp16/", [("math", "MATH_FP16")], SMALL + [BIG]),
+    ("", [], SMALL + [BIG, L4STRIP]),
+    ("fp16/", [("math", "MATH_FP16")], SMALL + [BIG, L4STRIP]),
     ("bf16x6/", [("math", "MATH_BF16X6")], SMALL),
     ("f32/", [("math", "MATH_F32")], SMALL),
     ("stem_patch=0/", [("option", ("OPT_STEM_PATCH", 0))], SMALL),
     ("fpn_commute=0/", [("option", ("OPT_FPN_COMMUTE", 0))], SMALL),
     ("fpn_commute=5/", [("option", ("OPT_FPN_COMMUTE", 5))], SMALL),  # a commuted and a concat level in one pass
     ("fpn_gemm=0/", [("option", ("OPT_FPN_GEMM", 0))], SMALL),
-    ("splitk_tickets=0/", [("option", ("OPT_SPLITK_TICKETS", 0))], SMALL),
+    ("splitk_tickets=0/", [("option", ("OPT_SPLITK_TICKETS", 0))], SMALL + [L4STRIP]),
     ("side_streams=0/", [("side_streams", False)], SMALL[1:]),
     ("probe_serial/", [("probe", ("PROBE_HEADS", "PROBE_SERIAL"))], SMALL[1:]),
     ("nhwc4/", [("layout", "IN_NHWC4")], SMALL[:1]),

@@ -27,6 +27,7 @@
 #pragma once
 
 #include "conv_h3_kernel.h"
+#include "../launch_check.h"
 
 namespace sfa {
 

@@ -17,6 +17,7 @@
 #pragma once
 
 #include "conv_r3_kernel.h"
+#include "../launch_check.h"
 
 namespace sfa {
 

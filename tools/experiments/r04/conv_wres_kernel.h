@@ -25,6 +25,7 @@
 #pragma once
 
 #include "conv_r3_kernel.h"  // (-I<pkg>/csrc)
+#include "../launch_check.h"
 
 namespace sfa {
 

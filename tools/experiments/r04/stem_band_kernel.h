@@ -39,6 +39,7 @@
 #pragma once
 
 #include "../../../lidar-image_object-detection_-fpn_resnet-yolov8_amd/csrc/stem_patch_kernel.h"
+#include "../launch_check.h"
 
 namespace sfa {
 

@@ -23,6 +23,7 @@
 #pragma once
 
 #include "../../../lidar-image_object-detection_-fpn_resnet-yolov8_amd/csrc/conv_h3s_kernel.h"
+#include "../launch_check.h"
 
 namespace sfa {
 

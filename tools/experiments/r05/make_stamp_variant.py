@@ -19,7 +19,7 @@ s = open(SRC).read()
 s = rep(s, '#include "conv_r3_kernel.h"', '#include "../../../lidar-image_object-detection_-fpn_resnet-yolov8_amd/csrc/conv_h3s_kernel.h"')
 s = s[:s.index("namespace h3sopt {")] + s[s.index("}  // namespace h3sopt\n") + len("}  // namespace h3sopt\n"):]
 s = s.replace("conv_h3s_kernel(", "conv_h3s_stamp_kernel(").replace("launch_conv_h3s_cfg", "launch_conv_h3s_stamp_cfg")
-s = s.replace("(conv_h3s_kernel<", "(conv_h3s_stamp_kernel<")
+s = s.replace(" conv_h3s_kernel<", " conv_h3s_stamp_kernel<")
 s = rep(s, "__global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_stamp_kernel(const ConvArgs a) {",
         """__global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_stamp_kernel(const ConvArgs a) {
   // DIAGNOSTIC BUILD: s_memtime stamps per k-step of every wave into the buffer passed as a.hout
