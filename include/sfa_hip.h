@@ -727,7 +727,8 @@ int sfa_kfpn_combine_grad(const float* const* levels, const int* channels, int n
  *   dA[b,p,o] = Hd[b,p,o] > 0 ? sum_c W2[c,o] g[b,c,p] : 0   (strict, torch's ReLU backward)
  *   db1[o] = sum_{b,p} dA[b,p,o]
  *   dW1[o,i,ky,kx] = sum_{b,y,x} dA[b,y,x,o] x[b,y+ky-1,x+kx-1,i], zero outside the map
- * The gradient with respect to x is not formed (fine-tuning the heads on a frozen backbone needs none).
+ * The gradient with respect to x is a separate entry, sfa_model_heads_input_grad below, on the dA this one writes to
+ * dhidden_out (fine-tuning the heads on a frozen backbone needs none).
  *   model, level   a SFA_BACKBONE_KFPN handle and its level 0, 1, 2: Cin = 256, 128, 64 and the level's head
  *                  weights inside the handle (SFA_BACKBONE_DECONV: SFA_E_UNSUPPORTED)
  *   x              DEVICE f32 (B, h, w, Cin) NHWC, 16-byte aligned: SFA_BUF_UP_LEVEL2 / 3 / 4 after a forward,
@@ -761,6 +762,38 @@ int sfa_model_heads_grad(const sfa_model* model, int level, const float* x, int 
                          const float* const* grad_levels, float* const* grad_w1, float* const* grad_b1,
                          float* const* grad_w2, float* const* grad_b2, float* hidden_out, float* dhidden_out,
                          int max_chunk_pixels, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------- the heads as an operator (one KFPN level) --
+ * sfa_model_heads_input_grad: the gradient at the heads' input x, summed over the level's heads (every head
+ * reads the same x), from dA (B, h, w, 64 num_heads) as sfa_model_heads_grad writes it to dhidden_out:
+ *   dX[b,y,x,i] = sum_o sum_{ky,kx} dA[b, y+1-ky, x+1-kx, o] W1[o,i,ky,kx]     (dA zero outside the map)
+ *   dhidden, grad_x   DEVICE f32 (B, h, w, 64 num_heads) and (B, h, w, Cin) NHWC, 16-byte aligned
+ * One launch on the caller's stream: an implicit GEMM on v_mfma_f32_32x32x2_f32 whose whole K = 9 * 64 num_heads
+ * is walked inside one workgroup per tile of sfa_heads_dgrad_pixel_tile() pixels of one image row x 64 input
+ * channels, accumulated in float32 in a fixed order.  No workspace, no partial tiles, no atomics, no memset;
+ * every byte of grad_x is written; two runs are bit-identical; graph-capturable.
+ *
+ * sfa_model_heads_forward: the level's heads on a caller's x: Hd = ReLU(conv3x3(x; W1) + b1) by the very launches
+ * sfa_model_heads_grad recomputes it with (fp16x3, the frames' own max |x|), so for the same x the two Hd are
+ * bit-equal and a ReLU edge falls the same way in the forward and in the gradient; then y = W2 Hd + b2 per pixel
+ * and channel in float64 from the float32 operands (b2 first, the 64 products in hidden-channel order), rounded
+ * once.  y is NOT promised bit-equal to sfa_model_forward's level maps: those come from another kernel (the
+ * fused head epilogue) with another summation order.
+ *   y_levels     HOST array [num_heads] of DEVICE f32 (B, c_j, h, w) NCHW, forward head order, every byte written
+ *   hidden_out   NULL, or DEVICE f32 (B, h, w, 64 num_heads), 16-byte aligned: Hd
+ *   workspace    DEVICE, 16-byte aligned, sfa_model_heads_forward_workspace_size(...) bytes (0 for arguments the
+ *                entry refuses); smaller: SFA_E_WORKSPACE
+ * Five launches (four for an even head count) on the caller's stream; graph-capturable.
+ *
+ * Both, before any launch: SFA_E_INVALID for a NULL pointer, a level outside 0..2, non-positive B, h or w, a
+ * misaligned buffer, or B h w max(Cin, 64 num_heads) 4 >= 2^31; SFA_E_UNSUPPORTED for a SFA_BACKBONE_DECONV model. */
+int sfa_heads_dgrad_pixel_tile(void);
+int sfa_model_heads_input_grad(const sfa_model* model, int level, const float* dhidden, int B, int h, int w,
+                               float* grad_x, void* stream);
+size_t sfa_model_heads_forward_workspace_size(const sfa_model* model, int level, int B, int h, int w);
+int sfa_model_heads_forward(const sfa_model* model, int level, const float* x, int B, int h, int w,
+                            float* const* y_levels, float* hidden_out, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,11 @@
 //   heads_wgrad_fold_kernel  per dW1 element: the chunks added in chunk order in float64, rounded once, written
 //                            as (64, Cin, 3, 3) per head
 //
+//   heads_dgrad_kernel       dX, the heads' input gradient (sfa_model_heads_input_grad): an implicit GEMM on the same
+//                            instruction with rows = pixels of one image row, columns = input channels and the
+//                            whole K = (tap, o) inside one workgroup; described at the kernel
+//   heads_out_kernel         y = W2 Hd + b2 of sfa_model_heads_forward, float64 from the float32 operands
+//
 // No atomics; every sum has a fixed order, so runs are bit-identical.
 #pragma once
 
@@ -29,6 +34,7 @@
 namespace sfa {
 
 typedef float hg_f32x16 __attribute__((ext_vector_type(16)));
+typedef float hg_f32x4 __attribute__((ext_vector_type(4)));
 
 // Per head of the level: g = d total / d y (B, ch, h, w) and the four gradient outputs in torch's layouts.
 struct HgHeads {
@@ -37,6 +43,13 @@ struct HgHeads {
   float* gb1[SFA_MAX_HEADS];  // (64)
   float* gw2[SFA_MAX_HEADS];  // (ch, 64)
   float* gb2[SFA_MAX_HEADS];  // (ch)
+  int ch[SFA_MAX_HEADS];
+  int num_heads;
+};
+
+// heads_out_kernel's table: per head the output map y (B, ch, h, w)
+struct HoHeads {
+  float* y[SFA_MAX_HEADS];
   int ch[SFA_MAX_HEADS];
   int num_heads;
 };
@@ -249,6 +262,132 @@ __global__ void __launch_bounds__(256) heads_wgrad_fold_kernel(HgHeads t, const 
   float* dst = nullptr;
   HG_PICK(dst, gw1, o >> 6);
   dst[(size_t)(o & 63) * per_o + rem] = (float)s;
+}
+
+// The heads' input gradient dX[b,y,x,i] = sum_o sum_{ky,kx} dA[b, y+1-ky, x+1-kx, o] W1[o,i,ky,kx] (dA zero outside
+// the map) as an implicit GEMM on v_mfma_f32_32x32x2_f32: rows = kHgDgPix pixels of one image row, columns =
+// kHgDgCin input channels, K = (o, tap) = 9 M, all of it walked by this one workgroup (2 x 2 waves of 32 x 32, one
+// 16-register accumulator each): no split-K, no partials, every element of dX written once by one lane.  Lane (r, k)
+// takes dA[pixel r shifted by the flipped tap][o + k] and W1[o + k][tap][i + r]; w3 is [o][tap = ky * 3 + kx][i]
+// (model.hip put_conv), so the W1 rows are the B operand as they lie.  Per step of kHgDgSlice hidden channels the
+// workgroup stages the 3 x (kHgDgPix + 2) pixel window of dA, transposed to [o][row][pixel] so that the 32 pixels
+// of a half-wave read 32 consecutive words, and the W1 slice [o][tap][i]: 12,672 + 36,864 = 49,536 bytes of LDS.
+// The next step's global loads are issued into registers before the step's 72 MFMAs per wave.
+// grid (blocks of heads_dgrad_plan), block (256)
+__global__ void __launch_bounds__(256, 2) heads_dgrad_kernel(const float* __restrict__ dA, const float* __restrict__ w3,
+                                                             float* __restrict__ dX, int h, int w, int Cin, int M,
+                                                             int tiles_per_row, int chan_tiles) {
+  constexpr int P = kHgDgPix, C = kHgDgCin, OS = kHgDgSlice, XW = P + 2;
+  constexpr int SA_O = 3 * XW;                // words of one hidden channel's window
+  constexpr int NA4 = 3 * XW * (OS / 4);      // float4 loads of one window slice
+  constexpr int NW4 = OS * 9 * (C / 4);       // float4 loads of one weight slice
+  constexpr int LA = (NA4 + 255) / 256, LW = NW4 / 256;
+  static_assert(NW4 % 256 == 0 && OS % 4 == 0 && C == 64 && P == 64, "the staging loops assume these");
+  __shared__ __attribute__((aligned(16))) float sA[OS * SA_O];    // [o][row y - 1 .. y + 1][column c0 - 1 ..]
+  __shared__ __attribute__((aligned(16))) float sW[OS * 9 * C];   // [o][tap][i]
+  const HeadsDgradTile tl = heads_dgrad_tile_at((int)blockIdx.x, w, tiles_per_row, chan_tiles);
+  const int b = tl.row / h, y = tl.row - b * h, c0 = tl.col0, i0 = tl.chan0;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wp = wave & 1, wc = wave >> 1, r = lane & 31, hh = lane >> 5;
+
+  // where this thread's staging loads come from (-1: zero, outside the map) and go to
+  int a_src[LA], a_dst[LA];
+#pragma unroll
+  for (int k = 0; k < LA; ++k) {
+    const int e = tid + k * 256;
+    const int q4 = e & (OS / 4 - 1), pc = e / (OS / 4);
+    const int dy = pc / XW, col = pc - dy * XW;
+    const int yy = y + dy - 1, xx = c0 + col - 1;
+    const bool in = e < NA4 && (unsigned)yy < (unsigned)h && (unsigned)xx < (unsigned)w;
+    a_src[k] = in ? ((b * h + yy) * w + xx) * M + q4 * 4 : -1;  // < 2^29 words: the plan's offset limit
+    a_dst[k] = e < NA4 ? (q4 * 4) * SA_O + pc : -1;
+  }
+  hg_f32x4 ra[LA], rw[LW];
+  const float* wsrc = w3 + (size_t)(tid >> 4) * Cin + i0 + (tid & 15) * 4;  // e = tid + 256 k: row o * 9 + tap = e / 16
+#define HG_DG_LOAD(o_first)                                                                                       \
+  do {                                                                                                            \
+    _Pragma("unroll") for (int k = 0; k < LA; ++k) ra[k] =                                                        \
+        a_src[k] >= 0 ? *reinterpret_cast<const hg_f32x4*>(dA + (size_t)a_src[k] + (o_first)) : hg_f32x4{0.f, 0.f, 0.f, 0.f}; \
+    _Pragma("unroll") for (int k = 0; k < LW; ++k) rw[k] =                                                        \
+        *reinterpret_cast<const hg_f32x4*>(wsrc + ((size_t)(o_first) * 9 + k * 16) * Cin);                        \
+  } while (0)
+
+  hg_f32x16 acc;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+  const bool live = wp * 32 < tl.cols;  // a short last tile: the waves of an empty pixel half only stage
+  const int p = wp * 32 + r;
+
+  HG_DG_LOAD(0);
+  for (int o0 = 0; o0 < M; o0 += OS) {
+    __syncthreads();  // the previous step's fragment reads are done
+#pragma unroll
+    for (int k = 0; k < LA; ++k)
+      if (a_dst[k] >= 0) {
+        float* d = sA + a_dst[k];
+        d[0] = ra[k].x, d[SA_O] = ra[k].y, d[2 * SA_O] = ra[k].z, d[3 * SA_O] = ra[k].w;
+      }
+#pragma unroll
+    for (int k = 0; k < LW; ++k) *reinterpret_cast<hg_f32x4*>(sW + (tid + k * 256) * 4) = rw[k];
+    __syncthreads();
+    const int o_next = o0 + OS < M ? o0 + OS : o0;  // the last step loads its own slice again and drops it
+    HG_DG_LOAD(o_next);
+    if (live) {
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const int ky = tap / 3, kx = tap - ky * 3;
+        const float* A = sA + (2 - ky) * XW + p + 2 - kx + hh * SA_O;  // row y + 1 - ky, column c0 + p + 1 - kx
+        const float* Wt = sW + tap * C + wc * 32 + r + hh * 9 * C;
+#pragma unroll
+        for (int s = 0; s < OS / 2; ++s)
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(A[2 * s * SA_O], Wt[2 * s * 9 * C], acc, 0, 0, 0);
+      }
+    }
+  }
+#undef HG_DG_LOAD
+  if (!live) return;
+  float* out = dX + ((size_t)tl.row * w + c0) * Cin + i0 + wc * 32 + r;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int q = wp * 32 + (v & 3) + 8 * (v >> 2) + 4 * hh;
+    if (q < tl.cols) out[(size_t)q * Cin] = acc[v];
+  }
+}
+
+// y = W2 Hd + b2 of every head of the level: one thread per pixel and output slot (head j, channel c < 4), the 64
+// products added to b2 in hidden-channel order in float64 from the float32 operands, rounded once, written NCHW per
+// head.  HdA / HdB: the two column parts of the hidden recompute; Hd_out: null, or the joined (B, h, w, M) copy,
+// written by the threads of slot c = 0.  w2: the packed 1x1 weights [head][4][64], b2: [head][4].
+// grid (ceil(npix heads 4 / 256)), block (256)
+__global__ void __launch_bounds__(256) heads_out_kernel(HoHeads t, const float* __restrict__ HdA,
+                                                        const float* __restrict__ HdB, int Na, int M,
+                                                        float* __restrict__ Hd_out, const float* __restrict__ w2,
+                                                        const float* __restrict__ b2, int npix, int hw) {
+  const int slots = t.num_heads * 4;
+  const int e = (int)blockIdx.x * 256 + (int)threadIdx.x;  // < 2^29: the plan's offset limit
+  if (e >= npix * slots) return;
+  const int p = e / slots, slot = e - p * slots, j = slot >> 2, c = slot & 3;
+  int ch = 0;
+  HG_PICK(ch, ch, j);
+  if (c >= ch && !(c == 0 && Hd_out)) return;
+  const int o0 = j * 64;
+  const float* hd = o0 < Na ? HdA + (size_t)p * Na + o0 : HdB + (size_t)p * (M - Na) + (o0 - Na);
+  const float* wr = w2 + (j * 4 + c) * 64;
+  double s = (double)b2[j * 4 + c];
+  for (int k = 0; k < 64; k += 4) {
+    const float4 hv = *reinterpret_cast<const float4*>(hd + k);
+    const float4 wv = *reinterpret_cast<const float4*>(wr + k);
+    s += (double)wv.x * (double)hv.x;
+    s += (double)wv.y * (double)hv.y;
+    s += (double)wv.z * (double)hv.z;
+    s += (double)wv.w * (double)hv.w;
+    if (c == 0 && Hd_out) *reinterpret_cast<float4*>(Hd_out + (size_t)p * M + o0 + k) = hv;
+  }
+  if (c >= ch) return;
+  float* y = nullptr;
+  HG_PICK(y, y, j);
+  const int bb = p / hw, q = p - bb * hw;
+  y[((size_t)bb * ch + c) * hw + q] = (float)s;
 }
 
 }  // namespace sfa

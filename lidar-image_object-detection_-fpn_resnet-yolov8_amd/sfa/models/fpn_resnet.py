@@ -103,6 +103,33 @@ class _TrainableHeadsForward(torch.autograd.Function):
         return (None, None, None) + tuple(t if need else None for t, need in zip(flat, ctx.needs_input_grad[3:]))
 
 
+class _LevelHeads(torch.autograd.Function):
+    """One KFPN level's heads as an operator over the level's input and its 20 head parameters: forward is
+    sfa_model_heads_forward on ``x`` (NHWC view of a channels-last tensor), backward runs sfa_model_heads_grad
+    (which recomputes the forward's own Hd, bit for bit) and sfa_model_heads_input_grad on the dA it leaves."""
+
+    @staticmethod
+    def forward(ctx, eng, level, x, *params):
+        xn = x.permute(0, 2, 3, 1)
+        with torch.cuda.device(x.device):
+            ys = eng.heads_forward(level, xn)
+        ctx.eng, ctx.level = eng, level
+        ctx.save_for_backward(xn)
+        return tuple(ys[n] for n, _ in eng.heads)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        eng, level, (xn,) = ctx.eng, ctx.level, ctx.saved_tensors
+        B, h, w, _ = xn.shape
+        with torch.cuda.device(xn.device):
+            g = {n: (gr.contiguous() if gr is not None else torch.zeros((B, c, h, w), device=xn.device))
+                 for (n, c), gr in zip(eng.heads, grads)}
+            res, _, dA = eng.heads_param_grad(level, xn, g, want_hidden=True)
+            dx = eng.heads_input_grad(level, dA).permute(0, 3, 1, 2) if ctx.needs_input_grad[2] else None
+        flat = [t for n, _ in eng.heads for t in res[n]]
+        return (None, None, dx) + tuple(t if need else None for t, need in zip(flat, ctx.needs_input_grad[3:]))
+
+
 class PoseResNet(nn.Module):
     def __init__(self, block, layers, heads, head_conv, **kwargs):
         self.inplanes = 64
@@ -220,6 +247,31 @@ class PoseResNet(nn.Module):
                 seq = getattr(self, f"fpn{f}_{head}")
                 out += [seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias]
         return out
+
+    def level_heads(self, level, x):
+        """The heads of KFPN ``level`` (0, 1, 2: ``fpn{level}_{head}``, Cin 256 / 128 / 64) on a caller's feature map
+        ``x``, a (B, Cin, h, w) float32 GPU tensor taken as channels-last bytes (a channels-last producer costs no
+        copy): {head: (B, c, h, w)}.  Differentiable with respect to ``x`` and the level's 20 head parameters
+        (sfa_model_heads_forward; sfa_model_heads_grad and sfa_model_heads_input_grad in backward), so a torch-built
+        backbone and neck can sit under the HIP heads and train.  Parameters that do not require grad get None."""
+        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+            raise _lib.SfaNativeError("PoseResNet.level_heads runs on the GPU (HIP) only")
+        if level not in (0, 1, 2) or x.dim() != 4 or x.shape[1] != _lib.HEADS_LEVEL_CIN[level]:
+            raise ValueError(f"level_heads: expected (B, {_lib.HEADS_LEVEL_CIN[level] if level in (0, 1, 2) else '?'}, "
+                             f"h, w) at level {level!r}, got {tuple(x.shape)}")
+        eng = self._engine(x.device)
+        x = x.float().contiguous(memory_format=torch.channels_last)
+        params = self.head_parameters()[20 * level:20 * level + 20]
+        res = _LevelHeads.apply(eng, int(level), x, *params)
+        return {n: t for (n, _), t in zip(eng.heads, res)}
+
+    def heads_from_levels(self, up_level2, up_level3, up_level4):
+        """The loop of models/fpn_resnet.py:219-244 on a caller's three level inputs (B, 256, h / 2, w / 2),
+        (B, 128, h, w), (B, 64, h, w): :meth:`level_heads` per level, then the KFPN combine (level 0 read at half
+        resolution).  Returns the five maps {head: (B, c, h, w)} whose grad_fn reaches the three inputs and the 60
+        head parameters."""
+        per_level = [self.level_heads(f, x) for f, x in enumerate((up_level2, up_level3, up_level4))]
+        return kfpn_heads({n: [lv[n] for lv in per_level] for n in per_level[0]}, level0_half=True)
 
     def forward_layout(self, x, in_layout):
         """forward() with the input read as ``in_layout``: _lib.IN_NCHW3 (the reference's), or

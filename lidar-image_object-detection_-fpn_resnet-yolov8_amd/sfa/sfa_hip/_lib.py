@@ -232,6 +232,12 @@ _PROTOS["sfa_model_heads_grad_workspace_size"] = (_c_size, [_vp] + [_c_int] * 5)
 _PROTOS["sfa_model_heads_grad_chunk_pixels"] = (_c_int, [_vp] + [_c_int] * 5)
 _PROTOS["sfa_model_heads_grad"] = (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_int] + [ctypes.POINTER(_vp)] * 5
                                    + [_vp, _vp, _c_int, _vp, _c_size, _vp])
+# the heads as an operator: input gradient and forward of one level on a caller's x
+_PROTOS["sfa_heads_dgrad_pixel_tile"] = (_c_int, [])
+_PROTOS["sfa_model_heads_input_grad"] = (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp])
+_PROTOS["sfa_model_heads_forward_workspace_size"] = (_c_size, [_vp] + [_c_int] * 4)
+_PROTOS["sfa_model_heads_forward"] = (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_int, ctypes.POINTER(_vp), _vp, _vp,
+                                               _c_size, _vp])
 HEADS_LEVEL_CIN = (256, 128, 64)  # input channels of KFPN level 0, 1, 2 (SFA_BUF_UP_LEVEL2 / 3 / 4)
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -263,6 +269,11 @@ def lib():
         raise SfaNativeError("libsfa_hip ABI version mismatch")
     _lib = L
     return L
+
+
+def heads_dgrad_pixel_tile() -> int:
+    """Pixels of one image row that a workgroup of heads_dgrad_kernel owns (csrc/heads_grad_plan.h kHgDgPix)."""
+    return int(lib().sfa_heads_dgrad_pixel_tile())
 
 
 def check(rc: int, what: str) -> None:

@@ -325,6 +325,56 @@ class KfpnEngine:
         grads = {n: tuple(r) for n, r in zip(names, res)}
         return (grads, hid[0], hid[1]) if want_hidden else grads
 
+    # ------------------------------------------------ the heads as an operator (one level on a caller's x)
+    def _level_nhwc(self, level, t, channels, what):
+        t = _require_gpu_tensor(t, what)
+        if self.deconv or level not in (0, 1, 2) or t.dim() != 4 or int(t.shape[3]) != channels(level):
+            raise ValueError(f"{what}: {tuple(t.shape)} is not (B, h, w, {channels(level) if level in (0, 1, 2) else '?'})"
+                             f" of KFPN level {level!r}")
+        return t
+
+    def heads_forward_workspace_bytes(self, level: int, B, h, w) -> int:
+        return int(lib().sfa_model_heads_forward_workspace_size(self._h, int(level), B, h, w))
+
+    def heads_forward(self, level: int, x: torch.Tensor, out: dict = None, want_hidden: bool = False,
+                      workspace: torch.Tensor = None):
+        """KFPN ``level``'s heads on a caller's ``x`` (sfa_model_heads_forward): float32 NHWC (B, h, w, Cin) on the
+        GPU.  Returns {head: y (B, c, h, w)}; with ``want_hidden`` also Hd (B, h, w, 64 * heads), bit-equal to the
+        Hd :meth:`heads_param_grad` recomputes for the same ``x``.  y is not promised bit-equal to the model's own
+        fused forward (another kernel, another summation order).  With ``out`` ({head: contiguous tensor}) and
+        ``workspace`` given the call only enqueues its launches (graph-capturable)."""
+        x = self._level_nhwc(level, x, lambda f: _lib.HEADS_LEVEL_CIN[f], "heads_forward x")
+        B, h, w, _ = (int(v) for v in x.shape)
+        names = [n for n, _ in self.heads]
+        ys = _kfpn_buffers(out, names, [(B, c, h, w) for _, c in self.heads], x, "heads_forward out")
+        hid = torch.empty((B, h, w, 64 * len(names)), dtype=torch.float32, device=x.device) if want_hidden else None
+        need = self.heads_forward_workspace_bytes(level, B, h, w)
+        if need == 0:
+            msg = lib().sfa_last_error_string()
+            raise ValueError(f"heads_forward: B={B}, h={h}, w={w} refused: {msg.decode() if msg else ''}")
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            check(lib().sfa_model_heads_forward(self._h, level, x.data_ptr(), B, h, w, _ptr_array(ys),
+                                                hid.data_ptr() if want_hidden else None, workspace.data_ptr(),
+                                                workspace.numel(), _lib.stream_ptr(x.device)), "sfa_model_heads_forward")
+        res = dict(zip(names, ys))
+        return (res, hid) if want_hidden else res
+
+    def heads_input_grad(self, level: int, dhidden: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """The gradient at the input of KFPN ``level``'s heads (sfa_model_heads_input_grad) from ``dhidden`` = dA,
+        float32 (B, h, w, 64 * heads) on the GPU as :meth:`heads_param_grad` returns it with ``want_hidden``.
+        Returns dX (B, h, w, Cin) NHWC, every element written; ``out`` (contiguous, that shape) receives it
+        instead.  One launch on the current stream, no workspace (graph-capturable)."""
+        d = self._level_nhwc(level, dhidden, lambda f: 64 * len(self.heads), "heads_input_grad dhidden")
+        B, h, w, _ = (int(v) for v in d.shape)
+        shape = (B, h, w, _lib.HEADS_LEVEL_CIN[level])
+        gx = _kfpn_buffers(None if out is None else {0: out}, [0], [shape], d, "heads_input_grad out")[0]
+        with torch.cuda.device(d.device):
+            check(lib().sfa_model_heads_input_grad(self._h, level, d.data_ptr(), B, h, w, gx.data_ptr(),
+                                                   _lib.stream_ptr(d.device)), "sfa_model_heads_input_grad")
+        return gx
+
     def forward(self, x: torch.Tensor, in_layout: int = _lib.IN_NCHW3) -> dict:
         x = _require_gpu_tensor(x, "PoseResNet.forward")
         if in_layout != _lib.IN_NHWC4:

@@ -2,7 +2,9 @@
 // input widths, 1..8 heads and max_chunk_pixels in {0, 1, 7, 64} and checks for every plan that the split-K
 // chunks tile every frame's rows exactly once, that no chunk crosses a frame, that K_c is the largest chunk,
 // that the column split of the hidden recompute is 128 k + (0 | 64), and that the workspace regions are disjoint, aligned and inside the reported size; then two known answers
-// and the refused shapes.  Built with -fsanitize=address,undefined by tests/test_heads_grad_host.py.
+// and the refused shapes.  For the same shapes (once per shape, not per chunking) the tiles of heads_dgrad_kernel: every
+// pixel of every row and every input channel covered exactly once, the last tile of a row short, never empty; and
+// the workspace regions of sfa_model_heads_forward: disjoint, aligned, inside the size.  Built with -fsanitize=address,undefined by tests/test_heads_grad_host.py.
 #include <cstdio>
 #include <vector>
 
@@ -62,6 +64,37 @@ static void check_plan(int B, int h, int w, int Cin, int heads, int mcp) {
   }
 }
 
+static void check_dgrad(int B, int h, int w, int Cin, int heads) {
+  HeadsDgradPlan p;
+  const bool ok = heads_dgrad_plan(B, h, w, Cin, heads, &p);
+  EXPECT(ok, "dgrad refused B %d h %d w %d Cin %d heads %d", B, h, w, Cin, heads);
+  if (!ok) return;
+  EXPECT(p.tiles_per_row == (w + kHgDgPix - 1) / kHgDgPix && p.chan_tiles * kHgDgCin == Cin &&
+             p.blocks == (int64_t)p.tiles_per_row * p.chan_tiles * B * h,
+         "dgrad tile counts");
+  std::vector<unsigned char> seen((size_t)B * h * w * p.chan_tiles, 0);
+  for (int c = 0; c < (int)p.blocks; ++c) {
+    const HeadsDgradTile t = heads_dgrad_tile_at(c, w, p.tiles_per_row, p.chan_tiles);
+    const bool in = t.row >= 0 && t.row < B * h && t.col0 >= 0 && t.cols >= 1 && t.cols <= kHgDgPix &&
+                    t.col0 + t.cols <= w && t.chan0 >= 0 && t.chan0 % kHgDgCin == 0 && t.chan0 + kHgDgCin <= Cin;
+    EXPECT(in, "dgrad tile %d leaves the map (row %d col0 %d cols %d chan0 %d; w %d)", c, t.row, t.col0, t.cols, t.chan0, w);
+    if (!in) continue;
+    EXPECT(t.col0 + t.cols == w || t.cols == kHgDgPix, "dgrad tile %d is short inside a row", c);
+    for (int q = 0; q < t.cols; ++q) seen[((size_t)t.row * w + t.col0 + q) * p.chan_tiles + t.chan0 / kHgDgCin]++;
+  }
+  for (unsigned char v : seen) EXPECT(v == 1, "a dgrad pixel is covered %d times (B %d h %d w %d Cin %d)", (int)v, B, h, w, Cin);
+  HeadsForwardPlan f;
+  EXPECT(heads_forward_plan(B, h, w, Cin, heads, &f), "forward plan refused");
+  const size_t npix = (size_t)B * h * w;
+  const size_t off[4] = {f.off_hidden, f.off_terms, f.off_amax, f.total};
+  const size_t len[3] = {npix * f.M * 4, (size_t)2 * f.M * 9 * Cin * 2, (size_t)B * kHgAmaxWords * 4};
+  EXPECT(f.M == 64 * heads && f.Na + f.Nb == f.M && f.Na % 128 == 0 && off[0] == 0, "forward plan columns");
+  for (int i = 0; i < 3; ++i) {
+    EXPECT(off[i] % kHgAlign == 0, "forward region %d misaligned", i);
+    EXPECT(off[i] + len[i] <= off[i + 1], "forward region %d overlaps the next / the end", i);
+  }
+}
+
 int main() {
   long plans = 0;
   const int cins[3] = {256, 128, 64}, mcps[4] = {0, 1, 7, 64};
@@ -70,10 +103,16 @@ int main() {
       for (int w = 1; w <= 40; ++w)
         for (int Cin : cins)
           for (int heads = 1; heads <= 8; ++heads)
+          {
             for (int mcp : mcps) {
               check_plan(B, h, w, Cin, heads, mcp);
               ++plans;
             }
+            check_dgrad(B, h, w, Cin, heads);
+          }
+  // widths around the dgrad pixel tile: one short, exact, one over, two tiles + 5
+  for (int w : {kHgDgPix - 1, kHgDgPix, kHgDgPix + 1, 2 * kHgDgPix + 5, 152})
+    for (int Cin : cins) check_dgrad(2, 3, w, Cin, 5);
   // known answers, by hand.  B 2, 6 x 8, Cin 128, 5 heads, cap 7: one row per chunk, 6 chunks per frame, K_c 8;
   // 96 pixels in 3 blocks of 32; regions 96 * 320 * 4 = 122880 (= 480 * 256) twice, 12 * 320 * 9 * 128 * 4 =
   // 17694720 (= 69120 * 256), 3 * 1620 * 8 = 38880 -> 38912, the fp16 terms 2 * 320 * 1152 * 2 = 1474560 (= 5760 * 256),
@@ -96,6 +135,20 @@ int main() {
   const HeadsGradChunk k5 = heads_grad_chunk(p, 5), k6 = heads_grad_chunk(p, 6);
   EXPECT(k5.frame == 0 && k5.row0 == 130 && k5.rows == 22 && k6.frame == 1 && k6.row0 == 0 && k6.rows == 26,
          "known answer 2 chunks 5, 6");
+  // dgrad known answer, by hand: 16 frames of 152 x 152 at Cin 128: 3 tiles per row (64, 64, 24), 2 channel tiles,
+  // 16 * 152 * 6 = 14592 blocks; block 11 = channel tile 1 of pixel tile 2 of row 1
+  HeadsDgradPlan dp;
+  EXPECT(heads_dgrad_plan(16, 152, 152, 128, 5, &dp) && dp.tiles_per_row == 3 && dp.chan_tiles == 2 && dp.blocks == 14592,
+         "dgrad known answer counts");
+  const HeadsDgradTile t11 = heads_dgrad_tile_at(11, 152, 3, 2);
+  EXPECT(t11.row == 1 && t11.col0 == 128 && t11.cols == 24 && t11.chan0 == 64, "dgrad known answer tile 11");
+  HeadsForwardPlan fp;
+  EXPECT(heads_forward_plan(2, 6, 8, 128, 5, &fp) && fp.off_terms == 122880 && fp.off_amax == 122880 + 1474560 &&
+             fp.total == 122880 + 1474560 + 2048 && fp.Na == 256 && fp.Nb == 64,
+         "forward plan known answer");
+  EXPECT(!heads_dgrad_plan(0, 4, 4, 64, 5, &dp) && !heads_dgrad_plan(1, 4, 4, 48, 5, &dp) &&
+             !heads_dgrad_plan(64, 512, 512, 64, 5, &dp) && !heads_forward_plan(1, 4, 0, 64, 5, &fp),
+         "dgrad / forward refusals");
   // refused
   EXPECT(!heads_grad_plan(0, 4, 4, 64, 5, 0, &p) && !heads_grad_plan(1, 0, 4, 64, 5, 0, &p) &&
              !heads_grad_plan(1, 4, -1, 64, 5, 0, &p) && !heads_grad_plan(1, 4, 4, 48, 5, 0, &p) &&

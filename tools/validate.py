@@ -11,6 +11,8 @@ total_loss over the frames, one JSON line.
   --timing --grad --kfpn   also that graph with the KFPN gradient (sfa_kfpn_combine_grad) behind the loss gradient
   --timing --grad --kfpn --heads   also that graph with the head parameter gradients (sfa_model_heads_grad) of one,
                            two and all three KFPN levels behind the KFPN gradient
+  --timing --grad --kfpn --heads --dgrad   also that last graph with the heads' input gradient
+                           (sfa_model_heads_input_grad) of one, two and all three levels added
 
 The loop is evaluation only (the gradient at the heads is only timed).  With a data set, the labels of a batch are read with the
 data set's own helpers (get_label, camera_to_lidar_box, filter_labels: a reference tree on sys.path or in
@@ -127,11 +129,13 @@ def evaluate(model, batches, args, device):
     return losses.avg, {k: v / max(frames, 1) for k, v in parts.items()}, frames
 
 
-def timing(device, args, frames=16, reps=50, grad=False, kfpn=False, heads_levels=0, engine=None):
+def timing(device, args, frames=16, reps=50, grad=False, kfpn=False, heads_levels=0, engine=None, dgrad_levels=0):
     """Median microseconds of sfa_build_targets + sfa_compute_loss (with ``grad`` also sfa_compute_loss_grad, with
     ``kfpn`` also sfa_kfpn_combine_grad from the head gradients to the 15 per-level maps, level 0 at half
     resolution; with ``heads_levels`` = n also sfa_model_heads_grad of KFPN levels 0 .. n - 1 of ``engine`` from those
-    level gradients and a synthetic heads' input) for ``frames`` frames, one HIP graph."""
+    level gradients and a synthetic heads' input; with ``dgrad_levels`` = n also sfa_model_heads_input_grad of levels
+    0 .. n - 1 on a synthetic dA of the level's shape: its time does not depend on the values) for ``frames`` frames,
+    one HIP graph."""
     hm = args.input_size // 4
     labels, offsets = synthetic.synthetic_labels(frames, seed=args.seed)
     builder = runtime.TargetBuilder(device, runtime.DEFAULT_BOUNDARY, (hm, hm), 3, args.max_objects)
@@ -158,6 +162,13 @@ def timing(device, args, frames=16, reps=50, grad=False, kfpn=False, heads_level
         ws = torch.empty(engine.heads_grad_workspace_bytes(level, frames, n, n), dtype=torch.uint8, device=device)
         hg.append((level, x, {h: lv[level] for h, lv in level_grads.items()}, out, ws))
 
+    dg = []
+    for level in range(dgrad_levels):
+        n = sizes[level]
+        dA = torch.from_numpy(synthetic.synthetic_logits((frames, n, n, 64 * len(runtime.DEFAULT_HEADS)), args.seed,
+                                                         140 + level)).to(device)
+        dg.append((level, dA, torch.empty((frames, n, n, _lib.HEADS_LEVEL_CIN[level]), dtype=torch.float32, device=device)))
+
     def step():
         builder(d_labels, d_offsets, None, out=tg, verify=False)
         ev(outs, tg, apply_sigmoid=True, verify=False)
@@ -167,6 +178,8 @@ def timing(device, args, frames=16, reps=50, grad=False, kfpn=False, heads_level
             runtime.kfpn_combine_grad(levels, grads, level0_half=True, out=level_grads)
         for level, x, g, out, ws in hg:
             engine.heads_param_grad(level, x, g, out=out, workspace=ws)
+        for level, dA, gx in dg:
+            engine.heads_input_grad(level, dA, out=gx)
 
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -221,6 +234,9 @@ def main(argv=None):
     ap.add_argument("--heads", action="store_true",
                     help="with --timing --grad --kfpn: also time that graph with the head parameter gradients of KFPN "
                          "levels 0, 0-1 and 0-2 added (one run, no threshold)")
+    ap.add_argument("--dgrad", action="store_true",
+                    help="with --timing --grad --kfpn --heads: also time the three-level graph with the heads' input "
+                         "gradient of levels 0, 0-1 and 0-2 added (one run, no threshold)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gpu_idx", type=int, default=0)
     args = ap.parse_args(argv)
@@ -252,6 +268,10 @@ def main(argv=None):
                     for n in (1, 2, 3):
                         result[f"plus_heads_grad_levels_0_to_{n - 1}_graph"] = timing(
                             device, args, grad=True, kfpn=True, heads_levels=n, engine=eng)
+                    if args.dgrad:
+                        for n in (1, 2, 3):
+                            result[f"plus_heads_input_grad_levels_0_to_{n - 1}_graph"] = timing(
+                                device, args, grad=True, kfpn=True, heads_levels=3, engine=eng, dgrad_levels=n)
             result["bench"] = run_bench()
     print(json.dumps(result))
     return result
