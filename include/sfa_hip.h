@@ -214,7 +214,28 @@ int sfa_model_create(const sfa_arch* arch, const float* packed_device, sfa_model
  * streams, every launch of its forward is on the caller's stream and sfa_model_set_side_streams is a
  * no-op on it (returns SFA_OK). */
 int sfa_model_create_ex(const sfa_arch_ex* arch, const float* packed_device, sfa_model** out);
+/* A second handle over the SAME packed weights as `model` (its own side stream and events, the same
+ * family, math left at the default, options seeded as at create), sharing `model`'s derived weight
+ * images (below) instead of building them again.  Either handle may be destroyed first. */
+int sfa_model_create_twin(const sfa_model* model, sfa_model** out);
 void sfa_model_destroy(sfa_model* model);
+
+/* Derived weight images.  For the fp16x3 kernels that stage W by LDS-DMA, create builds a second device
+ * buffer owned by the handle: the fp16 terms of those convs permuted once into the byte order of the
+ * kernel's LDS tiles, K-tile by K-tile (today: the detection heads' 3x3 convs, ~5.2 MB for the default
+ * heads).  The packed buffer itself is never changed.  The images are built at sfa_model_create(_ex)
+ * from the packed weights as they are at that moment (on the null stream, waited for), so the upload of
+ * `packed_device` must be complete by then; they are built only when `packed_device` is device memory
+ * of the current device covering sfa_packed_floats floats (otherwise the handle keeps the kernels that
+ * read the packed terms directly, with the same results).  The packed buffer stays the caller's: after
+ * ANY later change of its contents, call sfa_model_refresh_weight_images(model, stream) before the next
+ * forward; it rebuilds every image on `stream` (stream-ordered, no allocation, capturable) for this
+ * handle and its twins.  A stale image cannot be detected.  A caller that updates weights in place and
+ * cannot make that call turns the images off with SFA_OPT_W_IMAGES = 0.  (The Python model creates a new
+ * handle from freshly packed weights whenever a parameter changes, heads_trainable() steps included.) */
+int sfa_model_refresh_weight_images(sfa_model* model, void* stream);
+/* Bytes of device memory the handle's derived weight images take (shared with its twins); 0: it has none. */
+size_t sfa_model_weight_image_bytes(const sfa_model* model);
 
 /* Side streams on (1, the default; env SFA_SIDE_STREAMS=0 at create time turns them off) or
  * off (0: every launch of the forward on the caller's stream).  Off destroys them (after their
@@ -281,9 +302,12 @@ int sfa_model_get_math(const sfa_model* model);
  *                                         their slices in the conv kernel (the last slice of a tile to
  *                                         finish, by an atomic ticket); 0: a reduce launch per conv; the
  *                                         same bits
+ *   SFA_OPT_W_IMAGES    (SFA_W_IMAGES)    1 (default): the fp16x3 heads read W from the derived weight
+ *                                         images (above), when the handle has them; 0: from the packed
+ *                                         terms; the same bits
  */
 enum sfa_model_option { SFA_OPT_STEM_PATCH = 0, SFA_OPT_FPN_COMMUTE = 1, SFA_OPT_FPN_GEMM = 2,
-                        SFA_OPT_SPLITK_TICKETS = 3 };
+                        SFA_OPT_SPLITK_TICKETS = 3, SFA_OPT_W_IMAGES = 16 };
 int sfa_model_set_option(sfa_model* model, int key, int value);
 int sfa_model_get_option(const sfa_model* model, int key, int* value);
 

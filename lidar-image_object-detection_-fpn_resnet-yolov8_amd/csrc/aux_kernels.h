@@ -1,6 +1,7 @@
 #pragma once
 
 #include "common.h"
+#include "conv_wimage.h"
 
 namespace sfa {
 
@@ -28,5 +29,8 @@ int launch_sigmoid_clamp(float* x, long long n, hipStream_t st);
 // kernel-argument slot that later launches reuse, so the replayed node zeroes whatever that slot
 // then points at (tools/debug/graph_repro.py); kernel nodes keep their own arguments.
 int launch_zero_words(void* p, size_t bytes, hipStream_t st);
+// Builds the pre-tiled LDS image (conv_wimage.h) of the packed fp16 terms `wh` ([terms][N][wstride]) into
+// `img` (wimage_bytes(g) bytes, 16-B aligned).
+int launch_wimage_build(const WImageGeom& g, const uint16_t* wh, unsigned char* img, hipStream_t st);
 
 }  // namespace sfa

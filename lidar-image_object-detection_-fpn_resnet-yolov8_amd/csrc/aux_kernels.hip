@@ -318,6 +318,35 @@ int launch_zero_words(void* p, size_t bytes, hipStream_t st) {
   return zero(n4 > 64 ? n4 : 64, c + head, n4, c + done, bytes - done);
 }
 
+// The pre-tiled LDS image of a conv's fp16 terms (conv_wimage.h): one thread per 16 bytes of the
+// image, a 16-B load of its source quad from the row-major terms and one 16-B vector store.
+__global__ void __launch_bounds__(256) wimage_build_kernel(const WImageGeom g, const uint16_t* __restrict__ wh,
+                                                           uint4* __restrict__ img, long long units) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= units) return;
+  const int pieces = wimage_pieces(g), ktiles = wimage_ktiles(g);
+  const int lane = (int)(i & 63);
+  const long long pe = i >> 6;
+  const int e = (int)(pe % pieces);
+  const long long t = pe / pieces;
+  const int kt = (int)(t % ktiles), nt = (int)(t / ktiles);
+  const size_t src = wimage_source(g, nt, kt, e, lane, nullptr, nullptr, nullptr);
+  img[i] = *reinterpret_cast<const uint4*>(wh + src);
+}
+
+int launch_wimage_build(const WImageGeom& g, const uint16_t* wh, unsigned char* img, hipStream_t st) {
+  if (const char* err = wimage_check(g)) {
+    set_error("%s", err);
+    return SFA_E_INVALID;
+  }
+  if (!wh || !img || (reinterpret_cast<uintptr_t>(wh) & 15) || (reinterpret_cast<uintptr_t>(img) & 15)) {
+    set_error("wimage: null or unaligned buffer");
+    return SFA_E_INVALID;
+  }
+  const long long units = (long long)(wimage_bytes(g) / 16);
+  return launch({grid_of(units), 256, st}, wimage_build_kernel, g, wh, reinterpret_cast<uint4*>(img), units);
+}
+
 int launch_sigmoid_clamp(float* x, long long n, hipStream_t st) {
   if (n <= 0) return SFA_OK;
   return launch({grid_of(n), 256, st}, sigmoid_clamp_kernel, x, n);

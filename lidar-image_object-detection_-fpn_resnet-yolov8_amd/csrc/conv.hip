@@ -65,6 +65,9 @@ constexpr int R3_FPN = r3opt::ALWAYS | r3opt::RES_UP;
 constexpr int R3_HEAD_STAG = r3opt::ALWAYS | r3opt::PRIO_HALF | r3opt::MIX_SPLIT | r3opt::READ_AHEAD3 |
                              r3opt::SCALAR_TAPS | r3opt::PACKED_HEAD | r3opt::CHUNK_MAJOR | r3opt::STAGGER |
                              r3opt::DELAYED_DMA;
+// heads with W from the conv's pre-tiled LDS image (r3opt::W_IMAGE; ConvArgs::wimg set by the model:
+// DESIGN.md §25)
+constexpr int R3_HEAD_STAG_IMG = R3_HEAD_STAG | r3opt::W_IMAGE;
 // strip kernel: the pre-split strip and the residual prefetch on every tile shape (round 5: with the
 // one-latency presplit the 128-wide tiles gain from them too, layer2 -4.6 % / -6.5 % with a residual,
 // layer3 -1 / -2 %, bit-identical: profiles/r05j_*; the names of the former two forms stay), the strip in
@@ -78,7 +81,8 @@ constexpr int H3S_128W = h3sopt::ALWAYS | h3sopt::PRESPLIT | h3sopt::STRIP_REGS;
 // conv_h3: the 64-wide instances as they are, the 128-wide ones with a sched_barrier per column block
 constexpr int H3_PLAIN = 0;
 constexpr int H3_PIPE = h3opt::PIPE;
-static_assert(R3_BODY == 526592 && R3_FPN == 35072 && R3_HEAD_STAG == 3766532, "conv_r3 instance names");
+static_assert(R3_BODY == 526592 && R3_FPN == 35072 && R3_HEAD_STAG == 3766532 && R3_HEAD_STAG_IMG == 7960836,
+              "conv_r3 instance names");
 static_assert(H3S_64 == 1166 && H3S_128 == 1166 && H3S_128W == 1038, "conv_h3s instance names");
 static_assert(H3_PLAIN == 0 && H3_PIPE == 2, "conv_h3 instance names");
 
@@ -124,7 +128,11 @@ static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
   int rc = SFA_E_UNSUPPORTED;
   const bool strip = strip_ok(a) && !sliced;
   if (epilogue == EPI_HEAD) {
-    if (a.N == 320) rc = launch_conv_r3_cfg<256, 320, 32, EPI_HEAD, 1, 3, R3_HEAD_STAG, TERMS>(a, st);
+    bool image = false;  // fp16x3 with the model's W image (the one-product mode keeps row-major W)
+    if constexpr (TERMS == 2) image = a.wimg != nullptr;
+    if (a.N == 320)
+      rc = image ? launch_conv_r3_cfg<256, 320, 32, EPI_HEAD, 1, 3, R3_HEAD_STAG_IMG>(a, st)
+                 : launch_conv_r3_cfg<256, 320, 32, EPI_HEAD, 1, 3, R3_HEAD_STAG, TERMS>(a, st);
     if constexpr (TERMS == 2)
       if (!ok(rc)) rc = launch_conv_x6g_cfg<256, 64, 32, EPI_HEAD, 1, 16, 3, 0, 64, 1>(a, st);  // other head counts
     return rc;

@@ -141,6 +141,11 @@ struct ConvArgs {
   // multiply-high divisions by the input width / height (filled by the strip kernel's launch) and by
   // the output width / height (conv_r3's)
   FastDiv fd_w, fd_h, fd_ow, fd_oh;
+  // fp16x3: the pre-tiled LDS image of wh for the kernel instance this conv runs on (conv_wimage.h:
+  // the instance's tile width and K order), wimg_bytes long, or null: the kernels gather their W
+  // pieces from the row-major terms. Kernel instances without an image form never read it.
+  const unsigned char* wimg;
+  unsigned wimg_bytes;
 };
 
 // Transposed convolution k=4 / s=2 / p=1 + folded BN + ReLU, fp16x3 (deconv_h3_kernel.h): the four

@@ -27,6 +27,7 @@
 #pragma once
 
 #include "conv_h3_kernel.h"
+#include "conv_wimage.h"
 
 namespace sfa {
 
@@ -335,9 +336,15 @@ constexpr int STAGGER = 1048576;
 // each barrier ~1,100 cycles early and idled there, the leading half now sheds its DMA issue
 // (heads -2.2 %, same bits: profiles/r05ah_*)
 constexpr int DELAYED_DMA = 2097152;
+// W pieces from the conv's pre-tiled LDS image (a.wimg, conv_wimage.h) instead of gathered from the
+// row-major terms: piece e of K-tile kt is the 1,024 contiguous bytes at (kt * ND_B + e) * 1024 of
+// column tile nt's image, lane l takes bytes 16 l .. of it (eight whole 128-B lines per piece, where
+// the gather reads sixteen 64-B row segments wstride * 2 bytes apart); the lane part of the source
+// offset is 16 l, the rest wave-uniform. Same LDS bytes, so the same fragments and products: bit-identical.
+constexpr int W_IMAGE = 4194304;
 constexpr int ALWAYS = SPREAD_DMA | TRANSPOSED;  // set in every product instance
 constexpr int ALLOWED = ALWAYS | PRIO_HALF | MIX_SPLIT | READ_AHEAD3 | SCALAR_TAPS | RES_UP | PACKED_HEAD |
-                        CHUNK_MAJOR | STAGGER | DELAYED_DMA;
+                        CHUNK_MAJOR | STAGGER | DELAYED_DMA | W_IMAGE;
 }  // namespace r3opt
 
 // The kernel body for output tile (and split-K slice) lbid; conv_r3_kernel maps blockIdx to lbid
@@ -360,6 +367,8 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
   constexpr bool CMAJ = (ABL & r3opt::CHUNK_MAJOR) != 0;
   constexpr bool STAG = (ABL & r3opt::STAGGER) != 0;
   constexpr bool DMA_DEL = (ABL & r3opt::DELAYED_DMA) != 0;
+  constexpr bool WIMG = (ABL & r3opt::W_IMAGE) != 0;
+  static_assert(!WIMG || TERMS == 2, "W images: fp16x3 only");
   static_assert(STAG ? NSTAGE == 3 : NSTAGE == 2, "W ring depth: 3 stages with the stagger, else 2");
   static_assert(NSEG == 1 || NSEG == 2, "segments");
   static_assert(EPI == EPI_STD || EPI == EPI_HEAD, "epilogue");
@@ -433,18 +442,28 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
   // ---- W DMA slots: pieces e = wave + NW * j (term e / ND_BT, rows (e % ND_BT) * 16 + lane / 4) ----
   const int wst = a.wstride ? a.wstride : a.Kpad;  // row stride of the fp16 terms
   const unsigned term_bytes = (unsigned)a.N * (unsigned)wst * 2u;
+  // WIMG (r3opt::W_IMAGE): the conv's LDS image, checked against this instance's geometry at launch
   const __amdgpu_buffer_rsrc_t rsw =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.wh), (short)0, (int)(2 * term_bytes), 0x00020000);
+      WIMG ? __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.wimg), (short)0, (int)a.wimg_bytes,
+                                               0x00020000)
+           : __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.wh), (short)0, (int)(2 * term_bytes),
+                                               0x00020000);
   // row R = 16 (e % ND_BT) + lane / 4 of piece e has swzB(R) = swzB(lane / 4), so the lane part
   // of the source offset is the same for every piece and the piece part is wave-uniform
   // (one VGPR for all NB pieces; a non-constant soffset operand of the LDS-DMA builtin makes
   // hipcc's host pass drop the kernel stub, so the uniform part is added to the VGPR offset)
-  const int wlane = (((n0 + lane / 4) * wst + a.wk0 + 8 * ((lane % 4) ^ swzB(lane / 4))) << 1);
+  // (WIMG: the lane's 16 bytes of a piece + column tile nt's image; the pieces 1 KiB apart)
+  const int wlane = WIMG ? 16 * lane + nt * (a.Kpad / BK) * STAGE
+                         : (((n0 + lane / 4) * wst + a.wk0 + 8 * ((lane % 4) ^ swzB(lane / 4))) << 1);
+  auto piece_off = [&](int e) -> int {  // uniform: wave, j, args
+    if constexpr (WIMG) return e * 1024;
+    return (int)((e / ND_BT) * term_bytes) + (e % ND_BT) * 16 * wst * 2;
+  };
   int boff_s[NB];
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
     const int e = wave + NW * j < ND_B ? wave + NW * j : ND_B - 1;
-    boff_s[j] = (int)((e / ND_BT) * term_bytes) + (e % ND_BT) * 16 * wst * 2;  // uniform: wave, j, args
+    boff_s[j] = piece_off(e);
   }
 
   // fp16x3 scale of the frame of this lane's A row in each 16-row sub-tile: the block's first two
@@ -544,11 +563,16 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
       load_a_seg(std::integral_constant<int, 0>(), rs0, k0);
     }
   };
+  // K-tile kt's part of the source offset: its weight columns, or (WIMG) its block of the image
+  auto wkoff = [&](int kt) -> int {
+    if constexpr (WIMG) return kt * STAGE;
+    return 2 * kcol(kt);
+  };
   auto load_w_piece = [&](int j, int kt, unsigned char* S) {
     if (NB_REM == 0 || j < NB - 1 || wave < NB_REM)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           rsw, (__attribute__((address_space(3))) void*)(S + (wave + NW * j) * 1024), 16,
-          (unsigned)(wlane + boff_s[j] + 2 * kcol(kt)), 0, 0, 0);
+          (unsigned)(wlane + boff_s[j] + wkoff(kt)), 0, 0, 0);
   };
   auto load_w = [&](int kt, unsigned char* S) {
 #pragma unroll
@@ -562,14 +586,14 @@ __device__ __forceinline__ void conv_r3_body(const ConvArgs& a, int lbid) {
     for (int j = 0; j < NB; ++j) {
       int e = (wave >= NW / 2 ? wave - NW / 2 : wave) + NW * j;
       if constexpr (NB_REM != 0) e = e < ND_B ? e : ND_B - 1;  // (a piece past the tile is never issued)
-      boff_p[j] = (int)((e / ND_BT) * term_bytes) + (e % ND_BT) * 16 * wst * 2;
+      boff_p[j] = piece_off(e);
     }
   }
   auto load_w_piece_p = [&](int j, int kt, unsigned char* S) {
     const int e = wave - NW / 2 + NW * j;
     if (NB_REM == 0 || e < ND_B)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void*)(S + e * 1024), 16,
-                                               (unsigned)(wlane + boff_p[j] + 2 * kcol(kt)), 0, 0, 0);
+                                               (unsigned)(wlane + boff_p[j] + wkoff(kt)), 0, 0, 0);
   };
   f16x8_t hf[TERMS][TM];  // split A of this K-tile
   auto split_a = [&](f16x8_t (&h)[TERMS][TM]) {
@@ -792,6 +816,16 @@ inline int launch_conv_r3_cfg(const ConvArgs& a, hipStream_t st) {
   if (int rc = conv_r3_check(a, BM, BN, EPI, (ABL & r3opt::RES_UP) != 0, (ABL & r3opt::SCALAR_TAPS) != 0,
                              (ABL & r3opt::CHUNK_MAJOR) != 0, &grid))
     return rc;
+  if constexpr ((ABL & r3opt::W_IMAGE) != 0) {  // the image must be this instance's (tile width, K order)
+    WImageGeom g = {a.N, a.Kpad, a.wstride ? a.wstride : a.Kpad, a.wk0, BN, TERMS, 0, a.seg[0].C};
+    if ((ABL & r3opt::CHUNK_MAJOR) != 0) g.cmaj_tiles = (a.nseg == 2 ? a.kseg1 : a.Kpad) / 32;
+    const char* err = wimage_check(g);
+    if (!err && (!a.wimg || a.wimg_bytes != wimage_bytes(g))) err = "conv_r3: W image does not fit this kernel instance";
+    if (err) {
+      set_error("%s", err);
+      return SFA_E_INVALID;
+    }
+  }
   ConvArgs b = a;  // the row decomposition's multiply-high divisions
   b.fd_ow = make_fast_div((unsigned)a.OW);
   b.fd_oh = make_fast_div((unsigned)a.OH);

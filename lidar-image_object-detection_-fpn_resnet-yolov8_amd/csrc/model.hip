@@ -11,6 +11,7 @@
 #include <cstring>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -330,6 +331,18 @@ static void split_terms_h3(const float* w, int N, int K, uint16_t* out, float* w
 
 using namespace sfa;
 
+// Pre-tiled LDS images (conv_wimage.h) of the convs whose fp16x3 kernel reads its W pieces from one: the
+// detection heads' 3x3 convs on conv_r3_kernel<256, 320> (image i = head level i). One device buffer,
+// shared by a model and the handles created from it by sfa_model_create_twin.
+struct WImages {
+  unsigned char* dev = nullptr;
+  sfa::WImageGeom geom[sfa::WIMG_MAX];
+  sfa::WImagePlan plan;
+  ~WImages() {
+    if (dev) (void)hipFree(dev);
+  }
+};
+
 struct sfa_model {
   sfa_arch arch;
   int backbone = SFA_BACKBONE_KFPN;  // sfa_backbone: what follows layer4
@@ -353,6 +366,11 @@ struct sfa_model {
   // the conv kernel (tickets, conv_h3_kernel.h splitk_ticket), 0 = splitk_reduce_kernel launches; the
   // same bits (env SFA_SPLITK_TICKETS). conv_h3's split convs keep the reduce launch.
   int splitk_tickets = 1;
+  // fp16x3 heads read W from the pre-tiled LDS images (1, env SFA_W_IMAGES) or gather it from the packed
+  // row-major terms (0); the same bits. `wimg` is null when the images could not be built (no device, the
+  // packed weights not in device memory, another head count): the row-major kernels run.
+  int w_images = 1;
+  std::shared_ptr<WImages> wimg;
   // Side stream for the level-0 heads (they only need up_level2, so they overlap the rest
   // of the FPN and the level-1/2 heads); created with the model on the current device,
   // used only when the forward's stream is on that device.
@@ -389,6 +407,56 @@ static void make_side_streams(sfa_model* m) {
       hipEventCreateWithFlags(&m->mid, hipEventDisableTiming) != hipSuccess) {
     (void)hipGetLastError();
     drop_side_streams(m);
+  }
+}
+
+// The geometry of head level f's image: the whole 3x3 conv, conv_r3_kernel<256, 320>'s chunk-major K order.
+static sfa::WImageGeom head_wimage_geom(const PHeads& hp, int Cin) {
+  return sfa::WImageGeom{hp.N, hp.K, hp.K, 0, 320, 2, hp.K / 32, Cin};
+}
+
+// (Re)builds every image from the packed weights, on `st`.
+static int fill_wimages(const sfa_model* m, hipStream_t st) {
+  const WImages& wi = *m->wimg;
+  for (int f = 0; f < wi.plan.count; ++f)
+    if (int rc = sfa::launch_wimage_build(wi.geom[f], reinterpret_cast<const uint16_t*>(m->w + m->plan.heads[f].wh),
+                                          wi.dev + wi.plan.off[f], st))
+      return rc;
+  return SFA_OK;
+}
+
+// Allocates and builds the images at create. Only from packed weights that are device memory of the
+// current device and cover the plan (a handle over anything else, or created without a device, keeps the
+// row-major kernels); built on the null stream and waited for, so a forward on any stream finds them.
+static void make_wimages(sfa_model* m) {
+  if (m->plan.heads[0].N != 320) return;  // the image instance is the five-head 256 x 320 tile
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  void* base = nullptr;
+  size_t range = 0;
+  int dev = -1;
+  const bool device_weights =
+      hipGetDevice(&dev) == hipSuccess && hipPointerGetAttributes(&at, m->w) == hipSuccess &&
+      at.type == hipMemoryTypeDevice && at.device == dev &&
+      hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &range, const_cast<float*>(m->w)) == hipSuccess &&
+      (reinterpret_cast<uintptr_t>(m->w) & 15) == 0 &&
+      (size_t)(reinterpret_cast<const char*>(m->w) - static_cast<const char*>(base)) + m->plan.total * 4 <= range;
+  if (!device_weights) {
+    (void)hipGetLastError();
+    return;
+  }
+  auto wi = std::make_shared<WImages>();
+  const int nlev = m->backbone == SFA_BACKBONE_DECONV ? 1 : 3;
+  for (int f = 0; f < nlev; ++f) wi->geom[f] = head_wimage_geom(m->plan.heads[f], kFpnC[f]);
+  if (sfa::wimage_plan(wi->geom, nlev, &wi->plan) != nullptr || hipMalloc(&wi->dev, wi->plan.total) != hipSuccess) {
+    (void)hipGetLastError();
+    wi->dev = nullptr;
+    return;
+  }
+  m->wimg = wi;
+  if (fill_wimages(m, nullptr) != SFA_OK || hipStreamSynchronize(nullptr) != hipSuccess) {
+    (void)hipGetLastError();
+    m->wimg.reset();
   }
 }
 
@@ -589,7 +657,8 @@ extern "C" int sfa_pack_weights_ex(const sfa_arch_ex* x, const float* state, siz
   return pack_weights(&x->base, x->backbone, state, state_floats, packed);
 }
 
-static int model_create(const sfa_arch* arch, int backbone, const float* packed_device, sfa_model** out) {
+static int model_create(const sfa_arch* arch, int backbone, const float* packed_device, sfa_model** out,
+                        const sfa_model* twin_of = nullptr) {
   SFA_CHECK_ARG(packed_device && out, "model_create: null argument");
   sfa_model* m = new sfa_model;
   m->arch = *arch;
@@ -603,6 +672,11 @@ static int model_create(const sfa_arch* arch, int backbone, const float* packed_
   if (const char* e = getenv("SFA_FPN_COMMUTE")) m->fpn_commute = atoi(e) & 7;
   if (const char* e = getenv("SFA_FPN_GEMM")) m->fpn_gemm = atoi(e) & 63;
   if (const char* e = getenv("SFA_SPLITK_TICKETS")) m->splitk_tickets = atoi(e) != 0;
+  if (const char* e = getenv("SFA_W_IMAGES")) m->w_images = atoi(e) != 0;
+  if (twin_of)
+    m->wimg = twin_of->wimg;  // the same weights: the same images
+  else
+    make_wimages(m);
   bool side_streams = true;  // env SFA_SIDE_STREAMS=0: every launch on the caller's stream (A/B)
   if (const char* e = getenv("SFA_SIDE_STREAMS")) side_streams = strcmp(e, "0") != 0;
   // the deconv family has no parallel branch: no side streams, every launch on the caller's stream
@@ -621,6 +695,21 @@ extern "C" int sfa_model_create_ex(const sfa_arch_ex* x, const float* packed_dev
   int rc = check_arch_ex(x);
   if (rc != SFA_OK) return rc;
   return model_create(&x->base, x->backbone, packed_device, out);
+}
+
+extern "C" int sfa_model_create_twin(const sfa_model* model, sfa_model** out) {
+  SFA_CHECK_ARG(model && out, "create_twin: null argument");
+  return model_create(&model->arch, model->backbone, model->w, out, model);
+}
+
+extern "C" int sfa_model_refresh_weight_images(sfa_model* model, void* stream) {
+  SFA_CHECK_ARG(model, "refresh_weight_images: null model");
+  if (!model->wimg) return SFA_OK;  // nothing derived from the weights
+  return fill_wimages(model, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t sfa_model_weight_image_bytes(const sfa_model* model) {
+  return model && model->wimg ? model->wimg->plan.total : 0;
 }
 
 extern "C" void sfa_model_destroy(sfa_model* model) {
@@ -667,6 +756,10 @@ extern "C" int sfa_model_set_option(sfa_model* model, int key, int value) {
       SFA_CHECK_ARG(value == 0 || value == 1, "set_option: SPLITK_TICKETS %d not 0 / 1", value);
       model->splitk_tickets = value;
       break;
+    case SFA_OPT_W_IMAGES:
+      SFA_CHECK_ARG(value == 0 || value == 1, "set_option: W_IMAGES %d not 0 / 1", value);
+      model->w_images = value;
+      break;
     default: set_error("set_option: unknown key %d", key); return SFA_E_INVALID;
   }
   return SFA_OK;
@@ -679,6 +772,7 @@ extern "C" int sfa_model_get_option(const sfa_model* model, int key, int* value)
     case SFA_OPT_FPN_COMMUTE: *value = model->fpn_commute; break;
     case SFA_OPT_FPN_GEMM: *value = model->fpn_gemm; break;
     case SFA_OPT_SPLITK_TICKETS: *value = model->splitk_tickets; break;
+    case SFA_OPT_W_IMAGES: *value = model->w_images; break;
     default: set_error("get_option: unknown key %d", key); return SFA_E_INVALID;
   }
   return SFA_OK;
@@ -1079,6 +1173,11 @@ struct Pass {
       a.hoff[j] = ko.off[j];
     }
     a.hout = out;
+    if (m->w_images && m->wimg) {  // this level's pre-tiled W image (fp16x3: conv.hip reads it, the other modes do not)
+      const int f = (int)(&hp - p.heads);
+      a.wimg = m->wimg->dev + m->wimg->plan.off[f];
+      a.wimg_bytes = (unsigned)m->wimg->plan.bytes[f];
+    }
     return a;
   }
 

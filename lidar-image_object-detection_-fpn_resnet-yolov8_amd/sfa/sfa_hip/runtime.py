@@ -121,6 +121,19 @@ class KfpnEngine:
         check(lib().sfa_model_get_option(self._h, int(key), ctypes.byref(v)), "sfa_model_get_option")
         return int(v.value)
 
+    def weight_image_bytes(self) -> int:
+        """Device bytes of this handle's derived weight images (include/sfa_hip.h; shared with its twins), 0
+        if it has none."""
+        return int(lib().sfa_model_weight_image_bytes(self._h))
+
+    def refresh_weight_images(self, stream: int = None):
+        """Rebuild the derived weight images from ``self.weights`` on ``stream`` (default: the current one):
+        after any in-place change of the packed device weights, before the next forward."""
+        with torch.cuda.device(self.device):
+            check(lib().sfa_model_refresh_weight_images(
+                self._h, _lib.stream_ptr(self.device) if stream is None else stream),
+                "sfa_model_refresh_weight_images")
+
     def set_side_streams(self, on: bool):
         """Side stream for the level-0 heads on (default) or off (sfa_model_set_side_streams):
         off when several forwards are kept in flight beside a copy stream, so the process's
@@ -130,24 +143,23 @@ class KfpnEngine:
         self.side_streams = bool(on)
 
     def twin(self) -> "KfpnEngine":
-        """A second model handle over the SAME device weights (sfa_model_create does not copy
-        them): its own side stream and events (or none, like this engine), so two forwards can be
-        in flight (or captured in two graphs) on two streams. Workspaces are per engine /
-        pipeline as usual."""
+        """A second model handle over the SAME device weights and derived weight images
+        (sfa_model_create_twin copies neither): its own side stream and events (or none, like this
+        engine), so two forwards can be in flight (or captured in two graphs) on two streams.
+        Workspaces are per engine / pipeline as usual."""
         t = object.__new__(KfpnEngine)
         t.arch, t.device, t.heads, t.weights = self.arch, self.device, self.heads, self.weights
         t.deconv = self.deconv
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            check(_lib.arch_fn(self.arch, "sfa_model_create")(ctypes.byref(self.arch), self.weights.data_ptr(),
-                                                              ctypes.byref(h)), "sfa_model_create")
+            check(lib().sfa_model_create_twin(self._h, ctypes.byref(h)), "sfa_model_create_twin")
         t._h = h
         t._ws = {}
         t.side_streams = True
         t.set_math(self.math)
         if not self.side_streams:
             t.set_side_streams(False)
-        for key in range(_lib.OPT_COUNT):  # the same kernel choices (every option key)
+        for key in _lib.OPTION_KEYS:  # the same kernel choices (every option key)
             if t.get_option(key) != self.get_option(key):
                 t.set_option(key, self.get_option(key))
         return t
