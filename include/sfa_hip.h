@@ -819,6 +819,58 @@ int sfa_model_heads_forward(const sfa_model* model, int level, const float* x, i
                             float* const* y_levels, float* hidden_out, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* ------------------------------------------- the FPN neck as an operator (fpn_resnet_18) --
+ * models/fpn_resnet.py:197-210: three 1x1 convolutions with bias over cat(up(x), skip) and three bilinear x2
+ * (align_corners=True) resizes, no BatchNorm, no non-linearity.  All maps are DEVICE float32 NHWC, 16-byte
+ * aligned: l4 (B, h4, w4, 512), l3 (B, 2 h4, 2 w4, 256), l2 (B, 4 h4, 4 w4, 128), l1 (B, 8 h4, 8 w4, 64) in;
+ * u2 (B, 4 h4, 4 w4, 256), u3 (B, 8 h4, 8 w4, 128), u4 (B, 8 h4, 8 w4, 64) = up_level2 / 3 / 4.  W_f, b_f are
+ * conv_up_level{f}.weight / .bias as float32 inside the handle; U is the resize as the model's own forward
+ * evaluates it (float32 source index scale * o, scale 0 for a one-row or one-column source):
+ *   z1 = W1 cat(U l4, l3) + b1,  u2 = U z1;   z2 = W2 cat(u2, l2) + b2,  u3 = U z2;   u4 = W3 cat(u3, l1) + b3
+ *
+ * sfa_model_neck_forward: U l4 is written to the workspace, each convolution is one pointwise GEMM on
+ * v_mfma_f32_32x32x2_f32 (rows = sfa_neck_pixel_tile() flat pixels, K = the input channels read as two segments,
+ * no concat buffer, bias in the epilogue), each resize one launch of the forward's kernel: six launches.  The
+ * arithmetic is float32 MFMA; u2 / u3 / u4 are NOT promised bit-equal to sfa_model_forward's maps, which come
+ * from the fused fp16x3 FPN stage.
+ *
+ * sfa_model_neck_grad: from g2, g3, g4 = d total / d u2, u3, u4 (g2 and g3 may be NULL: zero; g4 is required)
+ *   dZ3 = g4            dW3 = dZ3^T cat(u3, l1)   db3 = sum dZ3   d_l1 = dZ3 W3b   d_u3 = g3 + dZ3 W3a
+ *   dZ2 = U^T d_u3      dW2 = dZ2^T cat(u2, l2)   db2 = sum dZ2   d_l2 = dZ2 W2b   d_u2 = g2 + dZ2 W2a
+ *   dZ1 = U^T d_u2      dW1b = dZ1^T l3           db1 = sum dZ1   d_l3 = dZ1 W1b
+ *   dL  = U^T dZ1       dW1a = dL^T l4                            d_l4 = dL W1a
+ * (Wfa: the first, "up", input columns of W_f; Wfb the rest; U and a 1x1 convolution commute, so stage 1's up
+ * half runs at l4's resolution.)  U^T is a gather: every low-resolution element adds, in float64 in (row, column)
+ * order, the high-resolution elements whose footprint reaches it, times the float32 coefficients the forward's
+ * kernel computes for that pixel, rounded once.  The data gradients walk their whole K (<= 256) inside one
+ * workgroup; the weight gradients are split-K over chunks of flat pixels (max_chunk_pixels caps a chunk, 0: the
+ * plan's own size) whose float32 partial tiles a fold adds in chunk order in float64, rounded once; the bias
+ * gradients are float64 sums in pixel order, rounded once.
+ *   d_l1 .. d_l4   each NULL (not wanted) or the shape of l1 .. l4; every byte written
+ *   dparams        NULL, or a HOST array of 6 DEVICE pointers dW1 (256, 768), db1 (256), dW2 (128, 384), db2 (128),
+ *                  dW3 (64, 192), db3 (64) in torch's layouts, each may be NULL; every byte written
+ *   l1 .. l4, u2, u3   read only by the weight gradients: NULL is allowed for the maps no wanted output reads
+ *                  (all of them when dparams is NULL)
+ *   workspace      DEVICE, 16-byte aligned, sfa_model_neck_grad_workspace_size(...) bytes (0 for refused arguments)
+ * sfa_model_neck_grad_chunk_pixels(f = 1, 2, 3) is K_c of dW_f, the pixels of its largest chunk: the K of the
+ * longest float32 accumulation, which the error bound of dW_f uses.  No atomics, no memset, nothing allocates or
+ * synchronises; two runs are bit-identical; graph-capturable.
+ *
+ * Both entries, before any launch: SFA_E_INVALID for a NULL required pointer, a NULL g4, no output wanted,
+ * non-positive B, h4 or w4, a negative max_chunk_pixels, a misaligned buffer, a workspace that is too small, or a
+ * shape whose largest map passes 2^31 bytes; SFA_E_UNSUPPORTED for a SFA_BACKBONE_DECONV model (it has no neck). */
+int sfa_neck_pixel_tile(void);
+size_t sfa_model_neck_forward_workspace_size(const sfa_model* model, int B, int h4, int w4);
+int sfa_model_neck_forward(const sfa_model* model, const float* l1, const float* l2, const float* l3, const float* l4,
+                           int B, int h4, int w4, float* u2, float* u3, float* u4, void* workspace,
+                           size_t workspace_bytes, void* stream);
+size_t sfa_model_neck_grad_workspace_size(const sfa_model* model, int B, int h4, int w4, int max_chunk_pixels);
+int sfa_model_neck_grad_chunk_pixels(const sfa_model* model, int f, int B, int h4, int w4, int max_chunk_pixels);
+int sfa_model_neck_grad(const sfa_model* model, const float* l1, const float* l2, const float* l3, const float* l4,
+                        const float* u2, const float* u3, const float* g2, const float* g3, const float* g4, int B,
+                        int h4, int w4, float* d_l1, float* d_l2, float* d_l3, float* d_l4, float* const* dparams,
+                        int max_chunk_pixels, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

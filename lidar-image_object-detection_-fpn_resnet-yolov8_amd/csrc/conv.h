@@ -173,4 +173,13 @@ struct HeadsLevel {
 };
 int model_heads_level(const sfa_model* m, int level, HeadsLevel* out);
 
+// conv_up_level{f + 1} inside a model handle's packed weights, for sfa_model_neck_forward / sfa_model_neck_grad
+// (neck.hip): the float32 (N, K) matrix in torch's (out, in) order and its bias.
+// SFA_E_INVALID for f outside 0..2, SFA_E_UNSUPPORTED for a SFA_BACKBONE_DECONV model.
+struct FpnLevel {
+  const float *w, *b;
+  int N, K;
+};
+int model_fpn_level(const sfa_model* m, int f, FpnLevel* out);
+
 }  // namespace sfa

@@ -987,6 +987,22 @@ int sfa::model_heads_level(const sfa_model* m, int level, HeadsLevel* out) {
   return SFA_OK;
 }
 
+// conv_up_level{f + 1} inside the handle (conv.h FpnLevel).
+int sfa::model_fpn_level(const sfa_model* m, int f, FpnLevel* out) {
+  if (m->backbone == SFA_BACKBONE_DECONV) {
+    set_error("neck: a SFA_BACKBONE_DECONV model has no FPN neck");
+    return SFA_E_UNSUPPORTED;
+  }
+  SFA_CHECK_ARG(f >= 0 && f < 3, "neck: stage %d outside 0..2", f);
+  const PConv& pc = m->plan.fpn[f];
+  SFA_CHECK_ARG(pc.Kpad == pc.K, "neck: conv_up_level%d is packed with padded rows", f + 1);
+  out->w = m->w + pc.w;
+  out->b = m->w + pc.b;
+  out->N = pc.N;
+  out->K = pc.K;
+  return SFA_OK;
+}
+
 #define SFA_RC(expr)            \
   do {                          \
     int rc_ = (expr);           \

@@ -70,6 +70,48 @@ class BasicBlock(nn.Module):
         raise RuntimeError("BasicBlock runs fused inside PoseResNet's HIP forward")
 
 
+def _trainable_forward(ctx, eng, in_layout, x):
+    """The engine's forward into a workspace this call keeps for backward: the five maps in head order."""
+    B, _, H, W = x.shape
+    with torch.cuda.device(x.device):
+        outs = eng.alloc_outputs(B, H, W)
+        ws = torch.empty(eng.workspace_bytes(B, H, W), dtype=torch.uint8, device=x.device)
+        eng.forward_into(x, outs, in_layout, ws)
+    ctx.eng, ctx.ws, ctx.shape = eng, ws, (B, H, W)
+    return tuple(outs[n] for n, _ in eng.heads)
+
+
+def _trainable_backward(ctx, grads, neck_need=()):
+    """sfa_kfpn_combine_grad, then sfa_model_heads_grad per level on the workspace's level maps and heads' inputs: the
+    60 head gradients, level-major.  With any of ``neck_need`` (which of the six neck parameters want a gradient)
+    also sfa_model_heads_input_grad per level on the dA that leaves, and sfa_model_neck_grad on those three gradients
+    and the workspace's layer1..4, up_level2 and up_level3 maps: (the six neck gradients or Nones, the 60)."""
+    eng, ws, (B, H, W) = ctx.eng, ctx.ws, ctx.shape
+    neck = any(neck_need)
+    with torch.cuda.device(ws.device):
+        views = eng.debug_views(ws, B, H, W)
+        levels = {n: [t.contiguous() for t in lv] for n, lv in views["levels"].items()}
+        gout = {n: (g.contiguous() if g is not None else torch.zeros_like(levels[n][1]))
+                for (n, _), g in zip(eng.heads, grads)}
+        glev = kfpn_combine_grad(levels, gout, level0_half=True)
+        flat, gx = [], []
+        for level in range(3):
+            res = eng.heads_param_grad(level, eng.level_input(ws, B, H, W, level),
+                                       {n: glev[n][level] for n, _ in eng.heads}, want_hidden=neck)
+            if neck:
+                res, _, dA = res
+                gx.append(eng.heads_input_grad(level, dA))
+            for n, _ in eng.heads:
+                flat += list(res[n])
+        dp = [None] * 6
+        if neck:
+            nhwc = lambda k: views[k].permute(0, 2, 3, 1)  # noqa: E731
+            _, dp = eng.neck_grad(*gx, layers=[nhwc(f"layer{i}") for i in (1, 2, 3, 4)],
+                                  ups=[nhwc("up_level2"), nhwc("up_level3")], want_layers=(False,) * 4,
+                                  want_params=tuple(neck_need))
+    return list(dp), flat
+
+
 class _TrainableHeadsForward(torch.autograd.Function):
     """PoseResNet.forward with the 60 head parameters as differentiable inputs (heads_trainable()).  forward is
     the engine's forward into a workspace this call keeps; backward takes the level maps and the heads' inputs
@@ -78,28 +120,11 @@ class _TrainableHeadsForward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, in_layout, x, *params):
-        B, _, H, W = x.shape
-        with torch.cuda.device(x.device):
-            outs = eng.alloc_outputs(B, H, W)
-            ws = torch.empty(eng.workspace_bytes(B, H, W), dtype=torch.uint8, device=x.device)
-            eng.forward_into(x, outs, in_layout, ws)
-        ctx.eng, ctx.ws, ctx.shape = eng, ws, (B, H, W)
-        return tuple(outs[n] for n, _ in eng.heads)
+        return _trainable_forward(ctx, eng, in_layout, x)
 
     @staticmethod
     def backward(ctx, *grads):
-        eng, ws, (B, H, W) = ctx.eng, ctx.ws, ctx.shape
-        with torch.cuda.device(ws.device):
-            levels = {n: [t.contiguous() for t in lv] for n, lv in eng.debug_views(ws, B, H, W)["levels"].items()}
-            gout = {n: (g.contiguous() if g is not None else torch.zeros_like(levels[n][1]))
-                    for (n, _), g in zip(eng.heads, grads)}
-            glev = kfpn_combine_grad(levels, gout, level0_half=True)
-            flat = []
-            for level in range(3):
-                res = eng.heads_param_grad(level, eng.level_input(ws, B, H, W, level),
-                                           {n: glev[n][level] for n, _ in eng.heads})
-                for n, _ in eng.heads:
-                    flat += list(res[n])
+        _, flat = _trainable_backward(ctx, grads)
         return (None, None, None) + tuple(t if need else None for t, need in zip(flat, ctx.needs_input_grad[3:]))
 
 
@@ -128,6 +153,58 @@ class _LevelHeads(torch.autograd.Function):
             dx = eng.heads_input_grad(level, dA).permute(0, 3, 1, 2) if ctx.needs_input_grad[2] else None
         flat = [t for n, _ in eng.heads for t in res[n]]
         return (None, None, dx) + tuple(t if need else None for t, need in zip(flat, ctx.needs_input_grad[3:]))
+
+
+def _nhwc_grad(g, shape, device):
+    """An upstream NCHW gradient as a contiguous NHWC tensor (zeros for None)."""
+    if g is None:
+        return torch.zeros(shape, dtype=torch.float32, device=device)
+    return g.permute(0, 2, 3, 1).contiguous()
+
+
+class _NeckFromLayers(torch.autograd.Function):
+    """The FPN neck as an operator over the four backbone maps and the six conv_up_level parameters: forward is
+    sfa_model_neck_forward on the NHWC views of channels-last tensors, backward one sfa_model_neck_grad for the
+    inputs that require grad (the operator is linear: besides the maps its convolutions read, nothing is saved)."""
+
+    @staticmethod
+    def forward(ctx, eng, l1, l2, l3, l4, *params):
+        ls = [t.permute(0, 2, 3, 1) for t in (l1, l2, l3, l4)]
+        with torch.cuda.device(l4.device):
+            u2, u3, u4 = eng.neck_forward(*ls)
+        ctx.eng = eng
+        ctx.save_for_backward(*ls, u2, u3)
+        return tuple(t.permute(0, 3, 1, 2) for t in (u2, u3, u4))
+
+    @staticmethod
+    def backward(ctx, g2, g3, g4):
+        eng = ctx.eng
+        l1, l2, l3, l4, u2, u3 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[1:]):
+            return (None,) * len(need)
+        with torch.cuda.device(l4.device):
+            g4 = _nhwc_grad(g4, l1.shape, l4.device)
+            g2, g3 = (None if g is None else _nhwc_grad(g, None, None) for g in (g2, g3))
+            dl, dp = eng.neck_grad(g2, g3, g4, layers=(l1, l2, l3, l4), ups=(u2, u3), want_layers=need[1:5],
+                                   want_params=need[5:11])
+        return (None,) + tuple(None if t is None else t.permute(0, 3, 1, 2) for t in dl) + tuple(dp)
+
+
+class _TrainableNeckForward(torch.autograd.Function):
+    """PoseResNet.forward with the 6 neck and the 60 head parameters as differentiable inputs (neck_trainable()):
+    _TrainableHeadsForward one stage deeper (_trainable_backward with the neck's part).  The input image and the
+    backbone get no gradient."""
+
+    @staticmethod
+    def forward(ctx, eng, in_layout, x, *params):
+        return _trainable_forward(ctx, eng, in_layout, x)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        need = ctx.needs_input_grad[3:]
+        dp, flat = _trainable_backward(ctx, grads, need[:6])
+        return (None, None, None) + tuple(t if n else None for t, n in zip(dp + flat, need))
 
 
 class PoseResNet(nn.Module):
@@ -170,6 +247,7 @@ class PoseResNet(nn.Module):
         self._sig = None
         self._state_tensors = None  # (structure generation, [state tensors]) cache of _signature
         self._heads_trainable = False
+        self._neck_trainable = False
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
@@ -273,6 +351,57 @@ class PoseResNet(nn.Module):
         per_level = [self.level_heads(f, x) for f, x in enumerate((up_level2, up_level3, up_level4))]
         return kfpn_heads({n: [lv[n] for lv in per_level] for n in per_level[0]}, level0_half=True)
 
+    def neck_trainable(self, flag=True):
+        """:meth:`heads_trainable` one stage deeper: fine-tuning of the FPN neck and the detection heads on a frozen
+        backbone.  On, with grad mode enabled, forward returns the same five maps (bit for bit) carrying a grad_fn
+        whose backward leaves ``.grad`` at ``conv_up_level{1,2,3}.{weight,bias}`` and at the 60 head parameters
+        that require grad (sfa_kfpn_combine_grad, per level sfa_model_heads_grad and sfa_model_heads_input_grad, then
+        sfa_model_neck_grad on the forward's own layer1..4, up_level2 and up_level3 maps).  The input image and the
+        backbone get no gradient, and BatchNorm stays folded with its running statistics.  A batch above one forward
+        pass (``max_batch``) is refused in this mode.  Returns self."""
+        self._no_neck("neck_trainable")
+        self._neck_trainable = bool(flag)
+        return self
+
+    def neck_parameters(self):
+        """conv_up_level1.weight, .bias, conv_up_level2.weight, .bias, conv_up_level3.weight, .bias."""
+        self._no_neck("neck_parameters")
+        return [p for m in (self.conv_up_level1, self.conv_up_level2, self.conv_up_level3) for p in (m.weight, m.bias)]
+
+    def _no_neck(self, what):
+        if not hasattr(self, "conv_up_level1"):
+            raise AttributeError(f"{what}: the plain resnet has no FPN neck (models/resnet.py)")
+
+    def neck_from_layers(self, out_layer1, out_layer2, out_layer3, out_layer4):
+        """Lines 197-210 of models/fpn_resnet.py on a caller's four backbone maps (B, 64, 8 h, 8 w), (B, 128, 4 h, 4 w),
+        (B, 256, 2 h, 2 w), (B, 512, h, w), float32 GPU tensors taken as channels-last bytes (a channels-last producer
+        costs no copy): returns (up_level2, up_level3, up_level4) = (B, 256, 4 h, 4 w), (B, 128, 8 h, 8 w),
+        (B, 64, 8 h, 8 w).  Differentiable with respect to the four maps and the six neck parameters
+        (sfa_model_neck_forward; sfa_model_neck_grad in backward); parameters that do not require grad get None.
+        float32 MFMA arithmetic: not bit-equal to the model's own fused FPN stage."""
+        self._no_neck("neck_from_layers")
+        layers = (out_layer1, out_layer2, out_layer3, out_layer4)
+        for i, t in enumerate(layers):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+                raise _lib.SfaNativeError("PoseResNet.neck_from_layers runs on the GPU (HIP) only")
+            if t.dim() != 4 or t.shape[1] != _lib.NECK_LAYER_C[i]:
+                raise ValueError(f"neck_from_layers: out_layer{i + 1} is {tuple(t.shape)}, expected "
+                                 f"(B, {_lib.NECK_LAYER_C[i]}, h, w)")
+        B, _, h4, w4 = out_layer4.shape
+        for i, t in enumerate(layers):
+            want = (B, _lib.NECK_LAYER_C[i], h4 << (3 - i), w4 << (3 - i))
+            if tuple(t.shape) != want:
+                raise ValueError(f"neck_from_layers: out_layer{i + 1} is {tuple(t.shape)}, expected {want}")
+        eng = self._engine(out_layer4.device)
+        layers = [t.float().contiguous(memory_format=torch.channels_last) for t in layers]
+        return _NeckFromLayers.apply(eng, *layers, *self.neck_parameters())
+
+    def detect_from_layers(self, out_layer1, out_layer2, out_layer3, out_layer4):
+        """The whole HIP detector top on a caller's four backbone maps: :meth:`heads_from_levels` of
+        :meth:`neck_from_layers`.  The five maps {head: (B, c, 8 h, 8 w)} carry a grad_fn reaching the four maps and
+        all 66 neck and head parameters."""
+        return self.heads_from_levels(*self.neck_from_layers(out_layer1, out_layer2, out_layer3, out_layer4))
+
     def forward_layout(self, x, in_layout):
         """forward() with the input read as ``in_layout``: _lib.IN_NCHW3 (the reference's), or
         _lib.IN_NCHW3_FLIP_HW = forward(torch.flip(x, [2, 3])) with the flip fused in."""
@@ -285,12 +414,17 @@ class PoseResNet(nn.Module):
             raise ValueError(f"unsupported input layout {in_layout}")
         eng = self._engine(x.device)
         x = x.contiguous().float()
-        if self._heads_trainable and torch.is_grad_enabled():
+        if (self._neck_trainable or self._heads_trainable) and torch.is_grad_enabled():
             B, _, H, W = x.shape
+            mode = "neck_trainable" if self._neck_trainable else "heads_trainable"
             if B > eng.max_batch(H, W):
-                raise ValueError(f"heads_trainable: batch {B} is above one forward pass ({eng.max_batch(H, W)} frames "
+                raise ValueError(f"{mode}: batch {B} is above one forward pass ({eng.max_batch(H, W)} frames "
                                  f"at {H}x{W}); the workspace holds one pass only")
-            res = _TrainableHeadsForward.apply(eng, in_layout, x.detach(), *self.head_parameters())
+            if self._neck_trainable:
+                res = _TrainableNeckForward.apply(eng, in_layout, x.detach(), *self.neck_parameters(),
+                                                  *self.head_parameters())
+            else:
+                res = _TrainableHeadsForward.apply(eng, in_layout, x.detach(), *self.head_parameters())
             self.kfpn_features, self.fpn_outputs = [], {}
             self.kfpn_weights, self.backbone_features = {}, {}
             return {n: t for (n, _), t in zip(eng.heads, res)}

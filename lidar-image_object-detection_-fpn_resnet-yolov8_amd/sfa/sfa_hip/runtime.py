@@ -387,6 +387,110 @@ class KfpnEngine:
                                                    _lib.stream_ptr(d.device)), "sfa_model_heads_input_grad")
         return gx
 
+    # ------------------------------------------------ the FPN neck as an operator (four backbone maps in)
+    def _neck_refused(self, what, B, h4, w4):
+        if self.deconv:
+            raise ValueError(f"{what}: a resnet_18 model has no FPN neck")
+        msg = lib().sfa_last_error_string()
+        raise ValueError(f"{what}: B={B}, h4={h4}, w4={w4} refused: {msg.decode() if msg else ''}")
+
+    @staticmethod
+    def _neck_shapes(B, h4, w4):
+        """NHWC shapes of l1..l4, then u2, u3, u4."""
+        return ([(B, h4 << (3 - i), w4 << (3 - i), c) for i, c in enumerate(_lib.NECK_LAYER_C)]
+                + [(B, 4 * h4, 4 * w4, 256), (B, 8 * h4, 8 * w4, 128), (B, 8 * h4, 8 * w4, 64)])
+
+    def _neck_maps(self, what, maps, names, shapes, optional=False):
+        out = []
+        for t, n, s in zip(maps, names, shapes):
+            if t is None and optional:
+                out.append(None)
+                continue
+            t = _require_gpu_tensor(t, f"{what} {n}")
+            if tuple(t.shape) != tuple(s):
+                raise ValueError(f"{what} {n}: {tuple(t.shape)} is not the NHWC {tuple(s)}")
+            out.append(t)
+        return out
+
+    def neck_forward_workspace_bytes(self, B, h4, w4) -> int:
+        return 0 if self.deconv else int(lib().sfa_model_neck_forward_workspace_size(self._h, B, h4, w4))
+
+    def neck_grad_workspace_bytes(self, B, h4, w4, max_chunk_pixels: int = 0) -> int:
+        return 0 if self.deconv else int(lib().sfa_model_neck_grad_workspace_size(self._h, B, h4, w4, int(max_chunk_pixels)))
+
+    def neck_grad_chunk_pixels(self, f: int, B, h4, w4, max_chunk_pixels: int = 0) -> int:
+        """K_c of dW_f (f = 1, 2, 3) in :meth:`neck_grad`: the pixel count of its largest split-K chunk, the length
+        of the float32 accumulation inside it (0 for a shape the entry refuses)."""
+        return 0 if self.deconv else int(
+            lib().sfa_model_neck_grad_chunk_pixels(self._h, int(f), B, h4, w4, int(max_chunk_pixels)))
+
+    def neck_forward(self, l1, l2, l3, l4, out=None, workspace: torch.Tensor = None):
+        """The FPN neck (models/fpn_resnet.py:197-210, sfa_model_neck_forward) on a caller's four backbone maps,
+        float32 NHWC on the GPU: l4 (B, h4, w4, 512), l3 (B, 2 h4, 2 w4, 256), l2 (B, 4 h4, 4 w4, 128),
+        l1 (B, 8 h4, 8 w4, 64).  Returns (u2, u3, u4) = up_level2 / 3 / 4, NHWC (B, 4 h4, 4 w4, 256),
+        (B, 8 h4, 8 w4, 128), (B, 8 h4, 8 w4, 64); ``out`` (three contiguous tensors) receives them instead.  float32
+        MFMA arithmetic: not promised bit-equal to the model's own fused fp16x3 FPN stage.  With ``out`` and
+        ``workspace`` given the call only enqueues its launches (graph-capturable)."""
+        l4 = _require_gpu_tensor(l4, "neck_forward l4")
+        if l4.dim() != 4:
+            raise ValueError(f"neck_forward l4: {tuple(l4.shape)} is not (B, h4, w4, 512)")
+        B, h4, w4, _ = (int(v) for v in l4.shape)
+        sh = self._neck_shapes(B, h4, w4)
+        ls = self._neck_maps("neck_forward", (l1, l2, l3, l4), ("l1", "l2", "l3", "l4"), sh[:4])
+        us = _kfpn_buffers(None if out is None else dict(enumerate(out)), range(3), sh[4:], l4, "neck_forward out")
+        need = self.neck_forward_workspace_bytes(B, h4, w4)
+        if need == 0:
+            self._neck_refused("neck_forward", B, h4, w4)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=l4.device)
+        with torch.cuda.device(l4.device):
+            check(lib().sfa_model_neck_forward(self._h, *(t.data_ptr() for t in ls), B, h4, w4,
+                                               *(t.data_ptr() for t in us), workspace.data_ptr(), workspace.numel(),
+                                               _lib.stream_ptr(l4.device)), "sfa_model_neck_forward")
+        return tuple(us)
+
+    def neck_grad(self, g2, g3, g4, layers=None, ups=None, want_layers=(True,) * 4, want_params=(True,) * 6, out=None,
+                  max_chunk_pixels: int = 0, workspace: torch.Tensor = None):
+        """The neck's gradients (sfa_model_neck_grad) from ``g2``, ``g3``, ``g4`` = d total / d u2, u3, u4 (NHWC,
+        the shapes :meth:`neck_forward` returns; g2 and g3 may be None: zero).  ``layers`` = (l1, l2, l3, l4) and
+        ``ups`` = (u2, u3) are what the weight gradients multiply (an entry may be None when no wanted dW reads
+        it; both may be None when no dW is wanted).  Returns (d_layers, d_params): d_l1..d_l4 NHWC and dW1, db1, dW2,
+        db2, dW3, db3 in torch's shapes, None where ``want_layers`` / ``want_params`` is False; every element of a
+        wanted output is written.  ``out`` = (4 tensors or Nones, 6 tensors or Nones) receives them instead of
+        fresh tensors.  With ``out`` and ``workspace`` given the call only enqueues its launches."""
+        g4 = _require_gpu_tensor(g4, "neck_grad g4")
+        if g4.dim() != 4 or g4.shape[1] % 8 or g4.shape[2] % 8:
+            raise ValueError(f"neck_grad g4: {tuple(g4.shape)} is not (B, 8 h4, 8 w4, 64)")
+        B, h4, w4 = int(g4.shape[0]), int(g4.shape[1]) // 8, int(g4.shape[2]) // 8
+        sh = self._neck_shapes(B, h4, w4)
+        gs = self._neck_maps("neck_grad", (g2, g3, g4), ("g2", "g3", "g4"), sh[4:], optional=True)
+        ls = self._neck_maps("neck_grad", layers or (None,) * 4, ("l1", "l2", "l3", "l4"), sh[:4], optional=True)
+        us = self._neck_maps("neck_grad", ups or (None,) * 2, ("u2", "u3"), sh[4:6], optional=True)
+        want = list(want_layers) + list(want_params)
+        shapes = sh[:4] + list(_lib.NECK_PARAM_SHAPES)
+        given = (list(out[0]) + list(out[1])) if out is not None else [None] * 10
+        res = []
+        for k, (wnt, s) in enumerate(zip(want, shapes)):
+            if not wnt:
+                res.append(None)
+            elif given[k] is None:
+                res.append(torch.empty(s, dtype=torch.float32, device=g4.device))
+            else:
+                res.append(_kfpn_buffers({0: given[k]}, [0], [s], g4, f"neck_grad out[{k}]")[0])
+        need = self.neck_grad_workspace_bytes(B, h4, w4, max_chunk_pixels)
+        if need == 0:
+            self._neck_refused("neck_grad", B, h4, w4)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=g4.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        dparams = (ctypes.c_void_p * 6)(*[ptr(t) for t in res[4:]]) if any(t is not None for t in res[4:]) else None
+        with torch.cuda.device(g4.device):
+            check(lib().sfa_model_neck_grad(self._h, *(ptr(t) for t in ls), *(ptr(t) for t in us),
+                                            *(ptr(t) for t in gs), B, h4, w4, *(ptr(t) for t in res[:4]), dparams,
+                                            int(max_chunk_pixels), workspace.data_ptr(), workspace.numel(),
+                                            _lib.stream_ptr(g4.device)), "sfa_model_neck_grad")
+        return res[:4], res[4:]
+
     def forward(self, x: torch.Tensor, in_layout: int = _lib.IN_NCHW3) -> dict:
         x = _require_gpu_tensor(x, "PoseResNet.forward")
         if in_layout != _lib.IN_NHWC4:

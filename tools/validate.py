@@ -13,6 +13,8 @@ total_loss over the frames, one JSON line.
                            two and all three KFPN levels behind the KFPN gradient
   --timing --grad --kfpn --heads --dgrad   also that last graph with the heads' input gradient
                            (sfa_model_heads_input_grad) of one, two and all three levels added
+  --timing --grad --kfpn --heads --dgrad --neck   also that last graph with the FPN neck's gradient
+                           (sfa_model_neck_grad: the four maps' and the six parameters' gradients) added
 
 The loop is evaluation only (the gradient at the heads is only timed).  With a data set, the labels of a batch are read with the
 data set's own helpers (get_label, camera_to_lidar_box, filter_labels: a reference tree on sys.path or in
@@ -129,13 +131,15 @@ def evaluate(model, batches, args, device):
     return losses.avg, {k: v / max(frames, 1) for k, v in parts.items()}, frames
 
 
-def timing(device, args, frames=16, reps=50, grad=False, kfpn=False, heads_levels=0, engine=None, dgrad_levels=0):
+def timing(device, args, frames=16, reps=50, grad=False, kfpn=False, heads_levels=0, engine=None, dgrad_levels=0,
+           neck=False):
     """Median microseconds of sfa_build_targets + sfa_compute_loss (with ``grad`` also sfa_compute_loss_grad, with
     ``kfpn`` also sfa_kfpn_combine_grad from the head gradients to the 15 per-level maps, level 0 at half
     resolution; with ``heads_levels`` = n also sfa_model_heads_grad of KFPN levels 0 .. n - 1 of ``engine`` from those
     level gradients and a synthetic heads' input; with ``dgrad_levels`` = n also sfa_model_heads_input_grad of levels
-    0 .. n - 1 on a synthetic dA of the level's shape: its time does not depend on the values) for ``frames`` frames,
-    one HIP graph."""
+    0 .. n - 1 on a synthetic dA of the level's shape: its time does not depend on the values; with ``neck`` also
+    sfa_model_neck_grad, all ten outputs, from the three input gradients and synthetic backbone maps) for ``frames``
+    frames, one HIP graph."""
     hm = args.input_size // 4
     labels, offsets = synthetic.synthetic_labels(frames, seed=args.seed)
     builder = runtime.TargetBuilder(device, runtime.DEFAULT_BOUNDARY, (hm, hm), 3, args.max_objects)
@@ -169,6 +173,16 @@ def timing(device, args, frames=16, reps=50, grad=False, kfpn=False, heads_level
                                                          140 + level)).to(device)
         dg.append((level, dA, torch.empty((frames, n, n, _lib.HEADS_LEVEL_CIN[level]), dtype=torch.float32, device=device)))
 
+    nk = None
+    if neck:
+        h4 = args.input_size // 32
+        shapes = engine._neck_shapes(frames, h4, h4)
+        maps = [torch.from_numpy(synthetic.synthetic_logits(sh, args.seed, 160 + i)).to(device)
+                for i, sh in enumerate(shapes[:6])]
+        mk = lambda shs: [torch.empty(sh, dtype=torch.float32, device=device) for sh in shs]  # noqa: E731
+        nk = (maps[:4], maps[4:6], (mk(shapes[:4]), mk(_lib.NECK_PARAM_SHAPES)),
+              torch.empty(engine.neck_grad_workspace_bytes(frames, h4, h4), dtype=torch.uint8, device=device))
+
     def step():
         builder(d_labels, d_offsets, None, out=tg, verify=False)
         ev(outs, tg, apply_sigmoid=True, verify=False)
@@ -180,6 +194,8 @@ def timing(device, args, frames=16, reps=50, grad=False, kfpn=False, heads_level
             engine.heads_param_grad(level, x, g, out=out, workspace=ws)
         for level, dA, gx in dg:
             engine.heads_input_grad(level, dA, out=gx)
+        if nk:
+            engine.neck_grad(*(gx for _, _, gx in dg), layers=nk[0], ups=nk[1], out=nk[2], workspace=nk[3])
 
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -237,6 +253,9 @@ def main(argv=None):
     ap.add_argument("--dgrad", action="store_true",
                     help="with --timing --grad --kfpn --heads: also time the three-level graph with the heads' input "
                          "gradient of levels 0, 0-1 and 0-2 added (one run, no threshold)")
+    ap.add_argument("--neck", action="store_true",
+                    help="with --timing --grad --kfpn --heads --dgrad: also time the last graph with the FPN neck's "
+                         "gradient added (one run, no threshold)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gpu_idx", type=int, default=0)
     args = ap.parse_args(argv)
@@ -272,6 +291,9 @@ def main(argv=None):
                         for n in (1, 2, 3):
                             result[f"plus_heads_input_grad_levels_0_to_{n - 1}_graph"] = timing(
                                 device, args, grad=True, kfpn=True, heads_levels=3, engine=eng, dgrad_levels=n)
+                        if args.neck:
+                            result["plus_neck_grad_graph"] = timing(
+                                device, args, grad=True, kfpn=True, heads_levels=3, engine=eng, dgrad_levels=3, neck=True)
             result["bench"] = run_bench()
     print(json.dumps(result))
     return result
