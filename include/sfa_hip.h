@@ -871,6 +871,67 @@ int sfa_model_neck_grad(const sfa_model* model, const float* l1, const float* l2
                         int h4, int w4, float* d_l1, float* d_l2, float* d_l3, float* d_l4, float* const* dparams,
                         int max_chunk_pixels, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------- one BasicBlock as an operator (fpn_resnet_18, layer1..4) --
+ * models/fpn_resnet.py:42-71 with every BatchNorm as the handle holds it: running statistics, folded into the
+ * convolution before it (W' = s W, b' = beta - mean s, s = gamma / sqrt(var + 1e-5)).  Block layer{layer}.{block},
+ * layer = 1..4, block = 0, 1: Cout = 64 2^(layer-1); for block == 0 && layer > 1 the stride s is 2, Cin = Cout / 2
+ * and the skip is the 1x1 stride-2 downsample, else s = 1, Cin = Cout and the skip is x itself.  All maps are DEVICE
+ * float32 NHWC, 16-byte aligned: x (B, h, w, Cin); mid, y, gy (B, oh, ow, Cout), oh = ceil(h / s), ow = ceil(w / s).
+ *   mid = ReLU(conv3x3_s(x; W1') + b1')
+ *   y   = ReLU(conv3x3_1(mid; W2') + b2' + skip),   skip = x  or  conv1x1_s(x; Wd')   (b2' holds both BN shifts)
+ *
+ * sfa_model_block_forward: the model's own convolution launches in fp16x3 whatever the handle's math mode is, each
+ * frame scaled by its own max |x| (and max |mid|), which the call measures; mid_out and y_out are both written.
+ * Any positive h and w, odd ones at stride 2 included (the launches read the input's and the output's sizes
+ * separately).  workspace: sfa_model_block_forward_workspace_size(...) bytes.
+ *
+ * sfa_model_block_grad: from gy = d total / d y and the maps the caller passes (the ReLU masks are read from them)
+ *   dZ  = y > 0 ? gy : 0       db2' = sum dZ     dW2' = wgrad_1(dZ, mid)     dApost = dgrad_1(dZ; W2')
+ *   dA  = mid > 0 ? dApost : 0 db1' = sum dA     dW1' = wgrad_s(dA, x)       dWd' = wgrad1x1_s(dZ, x)
+ *   dx  = dgrad_s(dA; W1') + (dZ  or  dgrad1x1_s(dZ; Wd'))
+ * on v_mfma_f32_32x32x2_f32.  dZ is never stored: the mask is applied where gy is loaded; dA's mask and the + dZ
+ * term sit in the data gradients' epilogues; the 1x1 downsample is the centre tap of the 3x3 window, a second K
+ * segment of the same kernels.  The data gradients walk their whole K (9 Cout, + Cout with a downsample) inside
+ * one workgroup in (tap, channel) order; the weight gradients are split-K over chunks of output pixels
+ * (max_chunk_pixels caps a chunk, 0: the plan's own size) whose float32 partial tiles a fold adds in chunk order in
+ * float64, rounded once; the bias gradients are float64 sums in pixel order, rounded once.
+ *   grad_x       NULL (not wanted) or (B, h, w, Cin); every byte written
+ *   dparams      NULL, or a HOST array of 5 DEVICE pointers dW1' (Cout, Cin, 3, 3), db1' (Cout), dW2' (Cout, Cout, 3, 3),
+ *                db2' (Cout), dWd' (Cout, Cin, 1, 1) in torch's layouts, each may be NULL; dWd' must be NULL on a
+ *                block without a downsample; every byte of a wanted output is written
+ *   x            may be NULL when neither dW1' nor dWd' is wanted; mid, y, gy are required
+ *   h, w         any positive sizes, odd ones included
+ *   workspace    DEVICE, 16-byte aligned, sfa_model_block_grad_workspace_size(...) bytes (0 for refused arguments)
+ * sfa_model_block_grad_chunk_pixels(which = 0: dW1', 1: dW2', 2: dWd') is K_c, the pixels of that gradient's largest
+ * chunk: the K of its longest float32 accumulation (0 when refused, or which = 2 without a downsample).
+ * No atomics, no memset, nothing allocates or synchronises; two runs are bit-identical; graph-capturable.
+ *
+ * All of these, before any launch: SFA_E_INVALID for a NULL required pointer, no output wanted, layer outside 1..4,
+ * block outside 0..1, non-positive B, h or w, a negative max_chunk_pixels, a misaligned buffer, a workspace that is
+ * too small, a dWd' pointer on a block without a downsample, or a map of 2^31 bytes or more; SFA_E_UNSUPPORTED for a
+ * SFA_BACKBONE_DECONV model.
+ *
+ * sfa_bn_unfold_grad: the gradients of a convolution weight W (Cout, K) and of the BatchNorm after it from the
+ * gradients dWf (Cout, K), dbf (Cout) of their folded form, in float64 from the float32 operands, rounded once:
+ *   s = gamma / sqrt(var + eps)    dW[o][k] = s[o] dWf[o][k]    dbeta = dbf
+ *   dgamma[o] = (sum_k W[o][k] dWf[o][k] - mean[o] dbf[o]) / sqrt(var[o] + eps)
+ * dW, dgamma, dbeta: each NULL or a DEVICE buffer, every element written; an operand no wanted output reads may be
+ * NULL.  One launch, fixed summation order.  SFA_E_INVALID: Cout or K <= 0, Cout K >= 2^29, a negative eps, no
+ * output wanted, or a NULL operand that a wanted output reads. */
+size_t sfa_model_block_forward_workspace_size(const sfa_model* model, int layer, int block, int B, int h, int w);
+int sfa_model_block_forward(const sfa_model* model, int layer, int block, const float* x, int B, int h, int w,
+                            float* mid_out, float* y_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t sfa_model_block_grad_workspace_size(const sfa_model* model, int layer, int block, int B, int h, int w,
+                                           int max_chunk_pixels);
+int sfa_model_block_grad_chunk_pixels(const sfa_model* model, int layer, int block, int which, int B, int h, int w,
+                                      int max_chunk_pixels);
+int sfa_model_block_grad(const sfa_model* model, int layer, int block, const float* x, const float* mid, const float* y,
+                         const float* gy, int B, int h, int w, float* grad_x, float* const* dparams,
+                         int max_chunk_pixels, void* workspace, size_t workspace_bytes, void* stream);
+int sfa_bn_unfold_grad(const float* W, const float* gamma, const float* mean, const float* var, double eps,
+                       const float* dWf, const float* dbf, int Cout, int K, float* dW, float* dgamma, float* dbeta,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

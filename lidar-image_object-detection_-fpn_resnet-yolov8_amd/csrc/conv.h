@@ -182,4 +182,21 @@ struct FpnLevel {
 };
 int model_fpn_level(const sfa_model* m, int f, FpnLevel* out);
 
+// BasicBlock layer{layer}.{block} (layer 1..4, block 0, 1) inside a model handle's packed weights, for
+// sfa_model_block_forward / sfa_model_block_grad (block.hip): per convolution c = 0 (conv1 + bn1), 1 (conv2 + bn2,
+// with downsample.0 + downsample.1 as the columns from kds on when the block has one) the BN-folded float32 rows
+// [o][(kh * 3 + kw) C + c] of K[c] words, the folded shift, and the bf16x6 / fp16x3 forms launch_conv reads.
+// SFA_E_INVALID for a layer or block out of range, SFA_E_UNSUPPORTED for a SFA_BACKBONE_DECONV model.
+struct BlockLevel {
+  const float *w[2], *b[2], *winv[2];
+  const uint16_t *wx[2], *wh[2];
+  int K[2];
+  int cin, cout, stride, downsample, kds;
+};
+int model_block_level(const sfa_model* m, int layer, int block, BlockLevel* out);
+
+// max |x| of each of B frames of n4 float4s into the frames' records (heads_amax_kernel, heads_grad.hip): what an
+// fp16x3 convolution on a caller's map reads as amax_in, measured without atomics or a zeroed record.
+int launch_frame_amax(const float* x, unsigned* amax, int B, int n4, hipStream_t st);
+
 }  // namespace sfa

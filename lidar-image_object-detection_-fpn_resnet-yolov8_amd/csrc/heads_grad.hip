@@ -22,6 +22,10 @@
 
 using namespace sfa;
 
+int sfa::launch_frame_amax(const float* x, unsigned* amax, int B, int n4, hipStream_t st) {
+  return launch({dim3(8, (unsigned)B), dim3(256), st}, heads_amax_kernel, reinterpret_cast<const float4*>(x), amax, n4);
+}
+
 namespace {
 
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
@@ -49,9 +53,7 @@ int heads_hidden_stage(const HeadsLevel& hl, const float* x, int B, int h, int w
                       reinterpret_cast<const uint32_t*>(hl.wh), reinterpret_cast<uint32_t*>(terms),
                       reinterpret_cast<uint32_t*>(terms + (size_t)2 * Na * K), M, Na, K / 2))
     return rc;
-  if (int rc = launch({dim3(8, (unsigned)B), dim3(256), st}, heads_amax_kernel, reinterpret_cast<const float4*>(x), amax,
-                      h * w * Cin / 4))
-    return rc;
+  if (int rc = launch_frame_amax(x, amax, B, h * w * Cin / 4, st)) return rc;
   for (int part_i = 0; part_i < 2; ++part_i) {
     const int n0 = part_i ? Na : 0, N = part_i ? Nb : Na;
     if (N == 0) continue;

@@ -1003,6 +1003,32 @@ int sfa::model_fpn_level(const sfa_model* m, int f, FpnLevel* out) {
   return SFA_OK;
 }
 
+// layer{layer}.{block} inside the handle (conv.h BlockLevel).
+int sfa::model_block_level(const sfa_model* m, int layer, int block, BlockLevel* out) {
+  if (m->backbone == SFA_BACKBONE_DECONV) {
+    set_error("block: the gradients of a SFA_BACKBONE_DECONV model's blocks are not covered");
+    return SFA_E_UNSUPPORTED;
+  }
+  SFA_CHECK_ARG(layer >= 1 && layer <= 4 && block >= 0 && block <= 1, "block: layer%d.%d outside layer1..4, block 0..1",
+                layer, block);
+  for (int c = 0; c < 2; ++c) {
+    const PConv& pc = m->plan.blk[layer - 1][block][c];
+    SFA_CHECK_ARG(pc.Kpad == pc.K, "block: layer%d.%d conv%d is packed with padded rows", layer, block, c + 1);
+    out->w[c] = m->w + pc.w;
+    out->b[c] = m->w + pc.b;
+    out->winv[c] = m->w + pc.winv;
+    out->wx[c] = reinterpret_cast<const uint16_t*>(m->w + pc.wx);
+    out->wh[c] = reinterpret_cast<const uint16_t*>(m->w + pc.wh);
+    out->K[c] = pc.K;
+  }
+  out->cout = 64 << (layer - 1);
+  out->downsample = block == 0 && layer > 1;
+  out->cin = out->downsample ? out->cout / 2 : out->cout;
+  out->stride = out->downsample ? 2 : 1;
+  out->kds = 9 * out->cout;
+  return SFA_OK;
+}
+
 #define SFA_RC(expr)            \
   do {                          \
     int rc_ = (expr);           \

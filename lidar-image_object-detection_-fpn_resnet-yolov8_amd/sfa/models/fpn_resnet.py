@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from sfa_hip import _lib
 from sfa_hip import dropin as _dropin
-from sfa_hip.runtime import KfpnEngine, kfpn_combine_grad, kfpn_heads, pack_state_dict
+from sfa_hip.runtime import KfpnEngine, bn_unfold_grad, kfpn_combine_grad, kfpn_heads, pack_state_dict
 
 BN_MOMENTUM = 0.1
 
@@ -189,6 +189,49 @@ class _NeckFromLayers(torch.autograd.Function):
             dl, dp = eng.neck_grad(g2, g3, g4, layers=(l1, l2, l3, l4), ups=(u2, u3), want_layers=need[1:5],
                                    want_params=need[5:11])
         return (None,) + tuple(None if t is None else t.permute(0, 3, 1, 2) for t in dl) + tuple(dp)
+
+
+class _BlockFromInput(torch.autograd.Function):
+    """One BasicBlock as an operator over its input and its 6 (9 with a downsample) parameters: forward is
+    sfa_model_block_forward on the NHWC view of a channels-last tensor, BatchNorm folded with the running statistics;
+    backward one sfa_model_block_grad on the saved x, mid and y, then sfa_bn_unfold_grad per convolution.  ``mods``:
+    the (conv, bn) pairs conv1 / bn1, conv2 / bn2 and, with a downsample, downsample.0 / downsample.1; ``params``:
+    their weight, bn.weight, bn.bias in that order."""
+
+    @staticmethod
+    def forward(ctx, eng, layer, block, mods, x, *params):
+        xn = x.permute(0, 2, 3, 1)
+        with torch.cuda.device(x.device):
+            mid, y = eng.block_forward(layer, block, xn)
+        ctx.eng, ctx.layer, ctx.block, ctx.mods = eng, layer, block, mods
+        ctx.save_for_backward(xn, mid, y)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        eng, mods = ctx.eng, ctx.mods
+        xn, mid, y = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        pneed = [need[5 + 3 * i:8 + 3 * i] for i in range(len(mods))]
+        if not need[4] and not any(any(n) for n in pneed):
+            return (None,) * len(need)
+        with torch.cuda.device(xn.device):
+            g = _nhwc_grad(gy, y.shape, xn.device)
+            # dW' of conv i feeds its dW and dgamma, db' its dgamma and dbeta; the downsample's db' is conv2's
+            want = [False] * 5
+            for i, n in enumerate(pneed):
+                want[(0, 2, 4)[i]] = n[0] or n[1]
+                want[(1, 3, 3)[i]] = want[(1, 3, 3)[i]] or n[1] or n[2]
+            dx, dp = eng.block_grad(ctx.layer, ctx.block, xn, mid, y, g, want_x=need[4], want_params=want)
+            out = []
+            for i, ((conv, bn), n) in enumerate(zip(mods, pneed)):
+                if not any(n):
+                    out += [None, None, None]
+                    continue
+                out += list(bn_unfold_grad(conv.weight, bn.weight, bn.running_mean, bn.running_var, bn.eps,
+                                           dp[(0, 2, 4)[i]] if (n[0] or n[1]) else torch.empty_like(conv.weight),
+                                           dp[(1, 3, 3)[i]] if (n[1] or n[2]) else torch.empty_like(bn.weight), want=n))
+        return (None, None, None, None, None if dx is None else dx.permute(0, 3, 1, 2)) + tuple(out)
 
 
 class _TrainableNeckForward(torch.autograd.Function):
@@ -401,6 +444,58 @@ class PoseResNet(nn.Module):
         :meth:`neck_from_layers`.  The five maps {head: (B, c, 8 h, 8 w)} carry a grad_fn reaching the four maps and
         all 66 neck and head parameters."""
         return self.heads_from_levels(*self.neck_from_layers(out_layer1, out_layer2, out_layer3, out_layer4))
+
+    def _block_mods(self, layer, block):
+        blk = getattr(self, f"layer{layer}")[block]
+        mods = [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2)]
+        if blk.downsample is not None:
+            mods.append((blk.downsample[0], blk.downsample[1]))
+        return tuple(mods)
+
+    def block_parameters(self):
+        """The 57 parameters of the eight BasicBlocks in the order :meth:`block_from_input` differentiates them: layer,
+        block, then conv1.weight, bn1.weight, bn1.bias, conv2.weight, bn2.weight, bn2.bias and, on a block with a
+        downsample, downsample.0.weight, downsample.1.weight, downsample.1.bias."""
+        self._no_neck("block_parameters")
+        return [p for L in (1, 2, 3, 4) for b in (0, 1) for conv, bn in self._block_mods(L, b)
+                for p in (conv.weight, bn.weight, bn.bias)]
+
+    def block_from_input(self, layer, block, x):
+        """BasicBlock ``layer{layer}.{block}`` (models/fpn_resnet.py:42-71) on a caller's ``x``, a (B, Cin, h, w) float32
+        GPU tensor taken as channels-last bytes: returns the block's output (B, Cout, ceil(h / s), ceil(w / s)).
+        BatchNorm uses its running statistics whatever ``.training`` says, folded into the convolutions, exactly as
+        :meth:`forward` does; the gradients are those of the block in ``eval()``.  Differentiable with respect to ``x``
+        and the block's 6 parameters (9 with a downsample): sfa_model_block_forward; sfa_model_block_grad and
+        sfa_bn_unfold_grad in backward.  Parameters that do not require grad get None.  x, mid and y are saved for
+        backward.  A parameter changed in place is seen by the next call (the engine repacks)."""
+        self._no_neck("block_from_input")
+        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+            raise _lib.SfaNativeError("PoseResNet.block_from_input runs on the GPU (HIP) only")
+        cin = KfpnEngine.block_shape(layer, block)[0]
+        if x.dim() != 4 or x.shape[1] != cin:
+            raise ValueError(f"block_from_input: expected (B, {cin}, h, w) at layer{layer}.{block}, got {tuple(x.shape)}")
+        eng = self._engine(x.device)
+        x = x.float().contiguous(memory_format=torch.channels_last)
+        mods = self._block_mods(layer, block)
+        params = [p for conv, bn in mods for p in (conv.weight, bn.weight, bn.bias)]
+        return _BlockFromInput.apply(eng, int(layer), int(block), mods, x, *params)
+
+    def layers_from_pooled(self, x):
+        """``layer1..4`` (models/fpn_resnet.py:184-187) on a caller's pooled stem output ``x`` (B, 64, h, w): the eight
+        blocks chained through :meth:`block_from_input`.  Returns (out_layer1, out_layer2, out_layer3, out_layer4)
+        whose grad_fn reaches ``x`` and the 57 :meth:`block_parameters`."""
+        outs = []
+        for layer in (1, 2, 3, 4):
+            for block in (0, 1):
+                x = self.block_from_input(layer, block, x)
+            outs.append(x)
+        return tuple(outs)
+
+    def detect_from_pooled(self, x):
+        """:meth:`detect_from_layers` of :meth:`layers_from_pooled`: everything behind the stem on a caller's pooled map
+        (B, 64, h, w), h and w multiples of 8.  The five maps carry a grad_fn reaching ``x`` and 123 of the model's 126
+        parameters (all but the stem's conv1.weight, bn1.weight, bn1.bias)."""
+        return self.detect_from_layers(*self.layers_from_pooled(x))
 
     def forward_layout(self, x, in_layout):
         """forward() with the input read as ``in_layout``: _lib.IN_NCHW3 (the reference's), or

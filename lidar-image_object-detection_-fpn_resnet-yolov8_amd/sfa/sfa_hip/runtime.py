@@ -491,6 +491,102 @@ class KfpnEngine:
                                             _lib.stream_ptr(g4.device)), "sfa_model_neck_grad")
         return res[:4], res[4:]
 
+    # ------------------------------------------------ one BasicBlock as an operator (a caller's input in)
+    @staticmethod
+    def block_shape(layer: int, block: int):
+        """(Cin, Cout, stride, has_downsample) of layer{layer}.{block}."""
+        if layer not in (1, 2, 3, 4) or block not in (0, 1):
+            raise ValueError(f"block: layer{layer!r}.{block!r} is outside layer1..4, block 0..1")
+        cout = 64 << (layer - 1)
+        ds = block == 0 and layer > 1
+        return (cout // 2 if ds else cout), cout, (2 if ds else 1), ds
+
+    def _block_dims(self, what, layer, block, x):
+        if self.deconv:
+            raise ValueError(f"{what}: the blocks of a resnet_18 model are not covered")
+        cin, cout, s, ds = self.block_shape(layer, block)
+        x = _require_gpu_tensor(x, f"{what} x")
+        if x.dim() != 4 or int(x.shape[3]) != cin:
+            raise ValueError(f"{what} x: {tuple(x.shape)} is not the NHWC (B, h, w, {cin}) of layer{layer}.{block}")
+        B, h, w, _ = (int(v) for v in x.shape)
+        return x, B, h, w, cin, cout, s, ds, (B, -(-h // s), -(-w // s), cout)
+
+    def _block_refused(self, what, B, h, w):
+        msg = lib().sfa_last_error_string()
+        raise ValueError(f"{what}: B={B}, h={h}, w={w} refused: {msg.decode() if msg else ''}")
+
+    def block_forward_workspace_bytes(self, layer, block, B, h, w) -> int:
+        return 0 if self.deconv else int(lib().sfa_model_block_forward_workspace_size(self._h, layer, block, B, h, w))
+
+    def block_grad_workspace_bytes(self, layer, block, B, h, w, max_chunk_pixels: int = 0) -> int:
+        return 0 if self.deconv else int(
+            lib().sfa_model_block_grad_workspace_size(self._h, layer, block, B, h, w, int(max_chunk_pixels)))
+
+    def block_grad_chunk_pixels(self, layer, block, which: int, B, h, w, max_chunk_pixels: int = 0) -> int:
+        """K_c of dW1' (which = 0), dW2' (1) or dWd' (2) in :meth:`block_grad`: the pixel count of its largest
+        split-K chunk, the length of the float32 accumulation inside it (0 for what the entry refuses)."""
+        return 0 if self.deconv else int(
+            lib().sfa_model_block_grad_chunk_pixels(self._h, layer, block, int(which), B, h, w, int(max_chunk_pixels)))
+
+    def block_forward(self, layer: int, block: int, x: torch.Tensor, out=None, workspace: torch.Tensor = None):
+        """BasicBlock layer{layer}.{block} (sfa_model_block_forward) on a caller's ``x``, float32 NHWC (B, h, w, Cin)
+        on the GPU, BatchNorm folded with the running statistics the engine was packed from.  Returns (mid, y),
+        NHWC (B, ceil(h / s), ceil(w / s), Cout): the ReLU output of conv1 and the block's output; ``out`` (two
+        contiguous tensors) receives them instead.  fp16x3 through the model's own convolution launches.  With ``out`` and ``workspace`` given the call only enqueues its
+        launches (graph-capturable)."""
+        x, B, h, w, _, _, _, _, osh = self._block_dims("block_forward", layer, block, x)
+        mid, y = _kfpn_buffers(None if out is None else dict(enumerate(out)), range(2), [osh, osh], x, "block_forward out")
+        need = self.block_forward_workspace_bytes(layer, block, B, h, w)
+        if need == 0:
+            self._block_refused("block_forward", B, h, w)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            check(lib().sfa_model_block_forward(self._h, layer, block, x.data_ptr(), B, h, w, mid.data_ptr(), y.data_ptr(),
+                                                workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(x.device)),
+                  "sfa_model_block_forward")
+        return mid, y
+
+    def block_grad(self, layer: int, block: int, x, mid, y, gy, want_x: bool = True, want_params=(True,) * 5, out=None,
+                   max_chunk_pixels: int = 0, workspace: torch.Tensor = None):
+        """The gradients of layer{layer}.{block} (sfa_model_block_grad) from ``gy`` = d total / d y and the maps
+        :meth:`block_forward` took and returned (float32 NHWC).  Returns (dx, [dW1', db1', dW2', db2', dWd']): the
+        gradients at x and at the BN-folded parameters in torch's shapes, None where not wanted (dWd' is None on a
+        block without a downsample whatever ``want_params[4]`` says); every element of a wanted output is written.
+        ``out`` = (tensor or None, 5 tensors or Nones) receives them instead of fresh tensors.  With ``out`` and
+        ``workspace`` given the call only enqueues its launches."""
+        x, B, h, w, cin, cout, _, ds, osh = self._block_dims("block_grad", layer, block, x)
+        maps = []
+        for t, n in ((mid, "mid"), (y, "y"), (gy, "gy")):
+            t = _require_gpu_tensor(t, f"block_grad {n}")
+            if tuple(t.shape) != osh:
+                raise ValueError(f"block_grad {n}: {tuple(t.shape)} is not the NHWC {osh}")
+            maps.append(t)
+        want = [bool(want_x)] + [bool(v) for v in want_params]
+        want[5] = want[5] and ds
+        shapes = [(B, h, w, cin), (cout, cin, 3, 3), (cout,), (cout, cout, 3, 3), (cout,), (cout, cin, 1, 1)]
+        given = ([out[0]] + list(out[1])) if out is not None else [None] * 6
+        res = []
+        for k, (wnt, s) in enumerate(zip(want, shapes)):
+            if not wnt:
+                res.append(None)
+            elif given[k] is None:
+                res.append(torch.empty(s, dtype=torch.float32, device=x.device))
+            else:
+                res.append(_kfpn_buffers({0: given[k]}, [0], [s], x, f"block_grad out[{k}]")[0])
+        need = self.block_grad_workspace_bytes(layer, block, B, h, w, max_chunk_pixels)
+        if need == 0:
+            self._block_refused("block_grad", B, h, w)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        dparams = (ctypes.c_void_p * 5)(*[ptr(t) for t in res[1:]]) if any(t is not None for t in res[1:]) else None
+        with torch.cuda.device(x.device):
+            check(lib().sfa_model_block_grad(self._h, layer, block, x.data_ptr(), *(t.data_ptr() for t in maps), B, h, w,
+                                             ptr(res[0]), dparams, int(max_chunk_pixels), workspace.data_ptr(),
+                                             workspace.numel(), _lib.stream_ptr(x.device)), "sfa_model_block_grad")
+        return res[0], res[1:]
+
     def forward(self, x: torch.Tensor, in_layout: int = _lib.IN_NCHW3) -> dict:
         x = _require_gpu_tensor(x, "PoseResNet.forward")
         if in_layout != _lib.IN_NHWC4:
@@ -1595,6 +1691,34 @@ class LossEvaluator:
 # ------------------------------------------------- apply_kfpn as an operator: forward + gradient
 def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def bn_unfold_grad(weight, gamma, mean, var, eps, dWf, dbf, want=(True, True, True)):
+    """The gradients of a convolution weight and of the BatchNorm after it from the gradients ``dWf``, ``dbf`` of their
+    folded form W' = s W, b' = beta - mean s, s = gamma / sqrt(var + eps) (sfa_bn_unfold_grad; float64 from the
+    float32 operands, rounded once).  ``weight`` (Cout, ...) and ``dWf`` of its shape, ``gamma``, ``mean``, ``var``,
+    ``dbf`` (Cout): contiguous float32 GPU tensors.  Returns (dW, dgamma, dbeta), None where ``want`` is False.  One
+    launch on the current stream."""
+    ts = [_require_gpu_tensor(t, f"bn_unfold_grad {n}").detach() for t, n in
+          ((weight, "weight"), (gamma, "gamma"), (mean, "mean"), (var, "var"), (dWf, "dWf"), (dbf, "dbf"))]
+    weight, gamma, mean, var, dWf, dbf = ts
+    cout = int(weight.shape[0])
+    K = weight.numel() // max(cout, 1)
+    if tuple(dWf.shape) != tuple(weight.shape) or any(tuple(t.shape) != (cout,) for t in (gamma, mean, var, dbf)):
+        raise ValueError("bn_unfold_grad: dWf must have weight's shape and gamma, mean, var, dbf its (Cout,)")
+    if not all(t.is_contiguous() for t in ts):
+        raise ValueError("bn_unfold_grad: the operands must be contiguous")
+    if not any(want):
+        return None, None, None
+    dW = torch.empty_like(weight) if want[0] else None
+    dg = torch.empty_like(gamma) if want[1] else None
+    dbt = torch.empty_like(gamma) if want[2] else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(weight.device):
+        check(lib().sfa_bn_unfold_grad(weight.data_ptr(), gamma.data_ptr(), mean.data_ptr(), var.data_ptr(), float(eps),
+                                       dWf.data_ptr(), dbf.data_ptr(), cout, K, ptr(dW), ptr(dg), ptr(dbt),
+                                       _lib.stream_ptr(weight.device)), "sfa_bn_unfold_grad")
+    return dW, dg, dbt
 
 
 def _kfpn_operands(levels_by_head: dict, level0_half: bool, what: str):
