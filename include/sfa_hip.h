@@ -932,6 +932,51 @@ int sfa_bn_unfold_grad(const float* W, const float* gamma, const float* mean, co
                        const float* dWf, const float* dbf, int Cout, int K, float* dW, float* dgamma, float* dbeta,
                        void* stream);
 
+/* ------------------------------------------- the stem as an operator (both backbone families) --
+ * models/fpn_resnet.py:179-182 on a caller's image, bn1 as the handle holds it: running statistics, folded into conv1
+ * (W' = s W, b' = beta - mean s, s = gamma / sqrt(var + 1e-5)).  x is DEVICE float32 (B, 3, H, W) NCHW (SFA_IN_NCHW3;
+ * the other two input layouts are not part of this operator); the maps are DEVICE float32 NHWC; all 16-byte aligned.
+ *   a = ReLU(conv7x7_2(x; W') + b')   (B, oh, ow, 64), oh = ceil(H / 2), ow = ceil(W / 2)
+ *   p = maxpool3x3_2(a)               (B, ph, pw, 64), ph = ceil(oh / 2), pw = ceil(ow / 2)
+ *
+ * sfa_model_stem_forward: the model's own unfused launches (the layout pass with its per-frame max |x|, the fp16x3
+ * convolution whatever the handle's math mode is, the max-pool); a_out and pooled_out are both written.  Accepted
+ * sizes: 1 <= H, W <= 32760 (the convolution launch packs input rows and columns in 16 bits), 1 <= B <= 65535 (the
+ * frame is a grid axis of the layout and max-pool launches), odd sizes included, and every map below 2^31 bytes
+ * (x as (B, H, W, 4) and a).  workspace: sfa_model_stem_forward_workspace_size(...) bytes.
+ *
+ * sfa_model_stem_grad: from gp = d total / d p (B, ph, pw, 64) and the map a the forward wrote
+ *   dAp = pool adjoint of gp: a pixel of a receives a window's gp exactly when it is that window's first maximum in
+ *         row-major scan order (torch's rule: strict >, padding is -inf and never wins); window maxima are recomputed
+ *         from a, the pooled map is not an input
+ *   dA  = a > 0 ? dAp : 0     db' = sum dA     dW' = wgrad_2(dA, x) (64, 3, 7, 7)     dx = dgrad_2(dA; W') (B, 3, H, W)
+ * dA is a gather over the pixels of a (at most 4 windows per pixel), written once to the workspace; dW' runs on
+ * v_mfma_f32_32x32x2_f32, split-K over chunks of conv output pixels (max_chunk_pixels caps a chunk, 0: the plan's own
+ * size) whose float32 partial tiles a fold adds in chunk order in float64, rounded once; db' is a float64 sum in pixel
+ * order, rounded once; dx is a vector gather over the taps of matching parity in (ky, kx, channel) order, float64
+ * accumulation of exact products, rounded once, and runs only when grad_x is wanted.
+ *   grad_x       NULL (not wanted) or (B, 3, H, W); every byte written
+ *   dparams      NULL, or a HOST array of 2 DEVICE pointers dW' (64, 3, 7, 7) in torch's layout and db' (64), each may
+ *                be NULL; every byte of a wanted output is written
+ *   x            may be NULL when dW' is not wanted; a and gp are required
+ *   workspace    DEVICE, 16-byte aligned, sfa_model_stem_grad_workspace_size(...) bytes (0 for refused arguments)
+ * sfa_model_stem_grad_chunk_pixels is K_c, the pixels of dW's largest chunk: the K of its longest float32
+ * accumulation (0 when refused).  No atomics, no memset, nothing allocates or synchronises; two runs are
+ * bit-identical; graph-capturable.  NaN in a or gp is outside the contract (a NaN never counts as a maximum here).
+ *
+ * All of these, before any launch: SFA_E_INVALID for a NULL required pointer, no output wanted, non-positive B, H or
+ * W, a negative max_chunk_pixels, a misaligned buffer, a workspace that is too small, or a map of 2^31 bytes or more;
+ * SFA_E_UNSUPPORTED for H or W above 32760 or B above 65535.  A SFA_BACKBONE_DECONV handle is accepted: the stem is
+ * shared code and shared packing. */
+size_t sfa_model_stem_forward_workspace_size(const sfa_model* model, int B, int H, int W);
+int sfa_model_stem_forward(const sfa_model* model, const float* x, int B, int H, int W, float* a_out, float* pooled_out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+size_t sfa_model_stem_grad_workspace_size(const sfa_model* model, int B, int H, int W, int max_chunk_pixels);
+int sfa_model_stem_grad_chunk_pixels(const sfa_model* model, int B, int H, int W, int max_chunk_pixels);
+int sfa_model_stem_grad(const sfa_model* model, const float* x, const float* a, const float* gp, int B, int H, int W,
+                        float* grad_x, float* const* dparams, int max_chunk_pixels, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

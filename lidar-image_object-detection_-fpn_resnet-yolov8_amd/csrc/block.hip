@@ -18,6 +18,20 @@
 
 using namespace sfa;
 
+int sfa::launch_block_wgrad_fold(const BlockWgrad& g, const float* part, float* dW, hipStream_t st) {
+  return launch({dim3((unsigned)ceil_div(g.rows * g.taps * g.cin, 256)), dim3(256), st}, block_wgrad_fold_kernel, part,
+                g.chunks, g.rows, g.cin, g.taps, dW);
+}
+
+int sfa::launch_block_bias_grad(const BlockBias& b, const float* g, const float* gm, double* part, float* db,
+                                hipStream_t st) {
+  const unsigned cy = (unsigned)ceil_div(b.cout, 256);
+  if (int rc = launch({dim3((unsigned)b.blocks, cy), dim3(256), st}, block_bias_kernel, g, gm, part, b.npix, b.pixels,
+                      b.cout))
+    return rc;
+  return launch({dim3(cy), dim3(256), st}, block_bias_fold_kernel, part, b.blocks, b.cout, db);
+}
+
 namespace {
 
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
@@ -36,16 +50,11 @@ int wgrad(const BlockWgrad& g, const BlockShape& s, const float* gr, const float
   const BkWgrad t = {gr, gm, x, h, w, s.oh, s.ow, stride, g.cin, g.rows, tap0, g.taps, g.npix, g.Kc};
   const dim3 grid((unsigned)g.chunks, (unsigned)(g.taps * g.cin / kBkTile), (unsigned)(g.rows / kBkTile));
   if (int rc = launch({grid, dim3(256), st}, block_wgrad_kernel, t, part)) return rc;
-  return launch({dim3((unsigned)ceil_div(g.rows * g.taps * g.cin, 256)), dim3(256), st}, block_wgrad_fold_kernel, part,
-                g.chunks, g.rows, g.cin, g.taps, dW);
+  return launch_block_wgrad_fold(g, part, dW, st);
 }
 
 int bias_grad(const BlockBias& b, const float* g, const float* gm, double* part, float* db, hipStream_t st) {
-  const unsigned cy = (unsigned)ceil_div(b.cout, 256);
-  if (int rc = launch({dim3((unsigned)b.blocks, cy), dim3(256), st}, block_bias_kernel, g, gm, part, b.npix, b.pixels,
-                      b.cout))
-    return rc;
-  return launch({dim3(cy), dim3(256), st}, block_bias_fold_kernel, part, b.blocks, b.cout, db);
+  return launch_block_bias_grad(b, g, gm, part, db, st);
 }
 
 int dgrad(const BkDgrad& t, float* out, hipStream_t st) {

@@ -195,6 +195,17 @@ struct BlockLevel {
 };
 int model_block_level(const sfa_model* m, int layer, int block, BlockLevel* out);
 
+// The stem (conv1 + bn1, 7x7 / stride 2 / pad 3, input channels padded 3 -> 4) inside a model handle's packed weights,
+// for sfa_model_stem_forward / sfa_model_stem_grad (stem_grad.hip): the BN-folded float32 rows [o][(kh * 7 + kw) 4 + c]
+// of K words (zero padded past 196), the folded shift, and the bf16x6 / fp16x3 forms launch_conv reads.  Both backbone
+// families share it.
+struct StemLevel {
+  const float *w, *b, *winv;
+  const uint16_t *wx, *wh;
+  int K;
+};
+int model_stem_level(const sfa_model* m, StemLevel* out);
+
 // max |x| of each of B frames of n4 float4s into the frames' records (heads_amax_kernel, heads_grad.hip): what an
 // fp16x3 convolution on a caller's map reads as amax_in, measured without atomics or a zeroed record.
 int launch_frame_amax(const float* x, unsigned* amax, int B, int n4, hipStream_t st);

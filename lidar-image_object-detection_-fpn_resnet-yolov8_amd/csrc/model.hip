@@ -1029,6 +1029,19 @@ int sfa::model_block_level(const sfa_model* m, int layer, int block, BlockLevel*
   return SFA_OK;
 }
 
+// conv1 + bn1 inside the handle (conv.h StemLevel).
+int sfa::model_stem_level(const sfa_model* m, StemLevel* out) {
+  const PConv& pc = m->plan.stem;
+  SFA_CHECK_ARG(pc.N == 64 && pc.K == 196 && pc.Kpad >= pc.K, "stem: conv1 is not packed as 64 rows of 7 x 7 x 4");
+  out->w = m->w + pc.w;
+  out->b = m->w + pc.b;
+  out->winv = m->w + pc.winv;
+  out->wx = reinterpret_cast<const uint16_t*>(m->w + pc.wx);
+  out->wh = reinterpret_cast<const uint16_t*>(m->w + pc.wh);
+  out->K = pc.Kpad;
+  return SFA_OK;
+}
+
 #define SFA_RC(expr)            \
   do {                          \
     int rc_ = (expr);           \

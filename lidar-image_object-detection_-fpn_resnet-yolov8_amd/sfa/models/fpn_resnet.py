@@ -234,6 +234,42 @@ class _BlockFromInput(torch.autograd.Function):
         return (None, None, None, None, None if dx is None else dx.permute(0, 3, 1, 2)) + tuple(out)
 
 
+class _StemFromImage(torch.autograd.Function):
+    """The stem as an operator over the image and conv1.weight, bn1.weight, bn1.bias: forward is sfa_model_stem_forward,
+    BatchNorm folded with the running statistics; backward one sfa_model_stem_grad on the saved x and a (the pool's
+    window maxima are recomputed from a), then sfa_bn_unfold_grad on conv1 / bn1.  The image gradient is computed only
+    when the image requires grad."""
+
+    @staticmethod
+    def forward(ctx, eng, conv, bn, x, *params):
+        with torch.cuda.device(x.device):
+            a, pooled = eng.stem_forward(x)
+        ctx.eng, ctx.conv, ctx.bn = eng, conv, bn
+        ctx.save_for_backward(x, a)
+        return pooled.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gp):
+        eng, conv, bn = ctx.eng, ctx.conv, ctx.bn
+        x, a = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        n = need[4:7]
+        if not need[3] and not any(n):
+            return (None,) * len(need)
+        with torch.cuda.device(x.device):
+            B, oh, ow, _ = a.shape
+            g = _nhwc_grad(gp, (B, -(-oh // 2), -(-ow // 2), 64), x.device)
+            # dW' feeds dW and dgamma, db' dgamma and dbeta
+            want = (n[0] or n[1], n[1] or n[2])
+            dx, dp = eng.stem_grad(x, a, g, want_x=need[3], want_params=want)
+            out = [None, None, None]
+            if any(n):
+                out = list(bn_unfold_grad(conv.weight, bn.weight, bn.running_mean, bn.running_var, bn.eps,
+                                          dp[0] if want[0] else torch.empty_like(conv.weight),
+                                          dp[1] if want[1] else torch.empty_like(bn.weight), want=n))
+        return (None, None, None, dx) + tuple(out)
+
+
 class _TrainableNeckForward(torch.autograd.Function):
     """PoseResNet.forward with the 6 neck and the 60 head parameters as differentiable inputs (neck_trainable()):
     _TrainableHeadsForward one stage deeper (_trainable_backward with the neck's part).  The input image and the
@@ -291,6 +327,7 @@ class PoseResNet(nn.Module):
         self._state_tensors = None  # (structure generation, [state tensors]) cache of _signature
         self._heads_trainable = False
         self._neck_trainable = False
+        self._backbone_trainable = False
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
@@ -494,8 +531,51 @@ class PoseResNet(nn.Module):
     def detect_from_pooled(self, x):
         """:meth:`detect_from_layers` of :meth:`layers_from_pooled`: everything behind the stem on a caller's pooled map
         (B, 64, h, w), h and w multiples of 8.  The five maps carry a grad_fn reaching ``x`` and 123 of the model's 126
-        parameters (all but the stem's conv1.weight, bn1.weight, bn1.bias)."""
+        parameters; the stem's conv1.weight, bn1.weight, bn1.bias are reached through :meth:`detect_from_image`."""
         return self.detect_from_layers(*self.layers_from_pooled(x))
+
+    def stem_parameters(self):
+        """conv1.weight, bn1.weight, bn1.bias: the order :meth:`stem_from_image` differentiates them in."""
+        self._no_neck("stem_parameters")
+        return [self.conv1.weight, self.bn1.weight, self.bn1.bias]
+
+    def stem_from_image(self, x):
+        """The stem (models/fpn_resnet.py:179-182: conv1, bn1, ReLU, max-pool) on a caller's image ``x``, a (B, 3, H, W)
+        float32 GPU tensor: returns the pooled map (B, 64, ceil(H / 4), ceil(W / 4)) as channels-last bytes.  BatchNorm
+        uses its running statistics whatever ``.training`` says, folded into conv1, exactly as :meth:`forward` does; the
+        gradients are those of the stem in ``eval()``.  Differentiable with respect to ``x`` and the three
+        :meth:`stem_parameters` (sfa_model_stem_forward; sfa_model_stem_grad and sfa_bn_unfold_grad in backward);
+        parameters that do not require grad get None, and the image gradient is computed only when ``x`` requires
+        grad.  x and the ReLU map are saved for backward.  The plain resnet family (models/resnet.py) refuses this
+        method although the C entries accept its handles."""
+        self._no_neck("stem_from_image")
+        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+            raise _lib.SfaNativeError("PoseResNet.stem_from_image runs on the GPU (HIP) only")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"stem_from_image: expected (B, 3, H, W), got {tuple(x.shape)}")
+        eng = self._engine(x.device)
+        x = x.float().contiguous()
+        return _StemFromImage.apply(eng, self.conv1, self.bn1, x, *self.stem_parameters())
+
+    def detect_from_image(self, x):
+        """:meth:`detect_from_pooled` of :meth:`stem_from_image`: the whole detector through the differentiable
+        operators on an image (B, 3, H, W), H and W multiples of 32.  The five maps carry a grad_fn reaching ``x`` (when
+        it requires grad) and all 126 parameters."""
+        if isinstance(x, torch.Tensor) and x.dim() == 4 and (x.shape[2] % 32 or x.shape[3] % 32):
+            raise ValueError(f"detect_from_image: H and W must be multiples of 32, got {tuple(x.shape)}")
+        return self.detect_from_pooled(self.stem_from_image(x))
+
+    def backbone_trainable(self, flag=True):
+        """Training of the whole detector: the deepest of the three trainable modes, it wins over
+        :meth:`neck_trainable` and :meth:`heads_trainable`.  On, with grad mode enabled, ``forward(x)`` returns
+        :meth:`detect_from_image` of ``x``: five maps whose backward leaves ``.grad`` at all 126 parameters that require
+        grad and at ``x`` when it does.  These maps are the operators' (fp16x3 stem and blocks, float32 MFMA neck,
+        saved activations), so they equal the fused forward only within the per-stage gate and not bit for bit.  The
+        flipped input layout is refused in this mode, and BatchNorm stays folded with its running statistics.  Off, or
+        under ``no_grad``, forward is exactly what it is without this mode.  Returns self."""
+        self._no_neck("backbone_trainable")
+        self._backbone_trainable = bool(flag)
+        return self
 
     def forward_layout(self, x, in_layout):
         """forward() with the input read as ``in_layout``: _lib.IN_NCHW3 (the reference's), or
@@ -507,6 +587,13 @@ class PoseResNet(nn.Module):
             raise ValueError(f"expected (B, 3, H, W), got {tuple(x.shape)}")
         if in_layout not in (_lib.IN_NCHW3, _lib.IN_NCHW3_FLIP_HW):
             raise ValueError(f"unsupported input layout {in_layout}")
+        if self._backbone_trainable and torch.is_grad_enabled():
+            if in_layout != _lib.IN_NCHW3:
+                raise ValueError("backbone_trainable: the flipped input layout is not differentiated; flip the image")
+            res = self.detect_from_image(x)
+            self.kfpn_features, self.fpn_outputs = [], {}
+            self.kfpn_weights, self.backbone_features = {}, {}
+            return res
         eng = self._engine(x.device)
         x = x.contiguous().float()
         if (self._neck_trainable or self._heads_trainable) and torch.is_grad_enabled():

@@ -587,6 +587,94 @@ class KfpnEngine:
                                              workspace.numel(), _lib.stream_ptr(x.device)), "sfa_model_block_grad")
         return res[0], res[1:]
 
+    # ------------------------------------------------ the stem as an operator (a caller's image in)
+    @staticmethod
+    def stem_shapes(B, H, W):
+        """NHWC shapes of a and pooled for a (B, 3, H, W) image."""
+        oh, ow = -(-H // 2), -(-W // 2)
+        return (B, oh, ow, 64), (B, -(-oh // 2), -(-ow // 2), 64)
+
+    def _stem_dims(self, what, x):
+        x = _require_gpu_tensor(x, f"{what} x")
+        if x.dim() != 4 or int(x.shape[1]) != 3:
+            raise ValueError(f"{what} x: {tuple(x.shape)} is not the NCHW (B, 3, H, W)")
+        B, _, H, W = (int(v) for v in x.shape)
+        return x, B, H, W
+
+    def _stem_refused(self, what, B, H, W):
+        msg = lib().sfa_last_error_string()
+        raise ValueError(f"{what}: B={B}, H={H}, W={W} refused: {msg.decode() if msg else ''}")
+
+    def stem_forward_workspace_bytes(self, B, H, W) -> int:
+        return int(lib().sfa_model_stem_forward_workspace_size(self._h, B, H, W))
+
+    def stem_grad_workspace_bytes(self, B, H, W, max_chunk_pixels: int = 0) -> int:
+        return int(lib().sfa_model_stem_grad_workspace_size(self._h, B, H, W, int(max_chunk_pixels)))
+
+    def stem_grad_chunk_pixels(self, B, H, W, max_chunk_pixels: int = 0) -> int:
+        """K_c of dW' in :meth:`stem_grad`: the pixel count of its largest split-K chunk, the length of the float32
+        accumulation inside it (0 for what the entry refuses)."""
+        return int(lib().sfa_model_stem_grad_chunk_pixels(self._h, B, H, W, int(max_chunk_pixels)))
+
+    def stem_forward(self, x: torch.Tensor, out=None, workspace: torch.Tensor = None):
+        """The stem (conv1 7x7 / 2, bn1 folded with the running statistics the engine was packed from, ReLU, max-pool;
+        sfa_model_stem_forward) on a caller's ``x``, float32 NCHW (B, 3, H, W) on the GPU.  Returns (a, pooled), NHWC
+        (B, ceil(H / 2), ceil(W / 2), 64) and (B, ceil(H / 4), ceil(W / 4), 64): the ReLU output and its 3x3 / 2
+        max-pool; ``out`` (two contiguous tensors) receives them instead.  fp16x3 through the model's own unfused
+        launches.  With ``out`` and ``workspace`` given the call only enqueues its launches (graph-capturable)."""
+        x, B, H, W = self._stem_dims("stem_forward", x)
+        a, pooled = _kfpn_buffers(None if out is None else dict(enumerate(out)), range(2), self.stem_shapes(B, H, W), x,
+                                  "stem_forward out")
+        need = self.stem_forward_workspace_bytes(B, H, W)
+        if need == 0:
+            self._stem_refused("stem_forward", B, H, W)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            check(lib().sfa_model_stem_forward(self._h, x.data_ptr(), B, H, W, a.data_ptr(), pooled.data_ptr(),
+                                               workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(x.device)),
+                  "sfa_model_stem_forward")
+        return a, pooled
+
+    def stem_grad(self, x, a, gp, want_x: bool = True, want_params=(True, True), out=None, max_chunk_pixels: int = 0,
+                  workspace: torch.Tensor = None):
+        """The stem's gradients (sfa_model_stem_grad) from ``gp`` = d total / d pooled (NHWC) and the ``x`` and ``a``
+        :meth:`stem_forward` took and returned.  Returns (dx, [dW', db']): the gradient at the image (B, 3, H, W) and at
+        the BN-folded parameters (64, 3, 7, 7), (64,), None where not wanted (dx is not computed then); every element
+        of a wanted output is written.  ``out`` = (tensor or None, 2 tensors or Nones) receives them instead of fresh
+        tensors.  With ``out`` and ``workspace`` given the call only enqueues its launches."""
+        x, B, H, W = self._stem_dims("stem_grad", x)
+        ash, psh = self.stem_shapes(B, H, W)
+        maps = []
+        for t, n, s in ((a, "a", ash), (gp, "gp", psh)):
+            t = _require_gpu_tensor(t, f"stem_grad {n}")
+            if tuple(t.shape) != s:
+                raise ValueError(f"stem_grad {n}: {tuple(t.shape)} is not the NHWC {s}")
+            maps.append(t)
+        want = [bool(want_x)] + [bool(v) for v in want_params]
+        shapes = [(B, 3, H, W), (64, 3, 7, 7), (64,)]
+        given = ([out[0]] + list(out[1])) if out is not None else [None] * 3
+        res = []
+        for k, (wnt, s) in enumerate(zip(want, shapes)):
+            if not wnt:
+                res.append(None)
+            elif given[k] is None:
+                res.append(torch.empty(s, dtype=torch.float32, device=x.device))
+            else:
+                res.append(_kfpn_buffers({0: given[k]}, [0], [s], x, f"stem_grad out[{k}]")[0])
+        need = self.stem_grad_workspace_bytes(B, H, W, max_chunk_pixels)
+        if need == 0:
+            self._stem_refused("stem_grad", B, H, W)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        dparams = (ctypes.c_void_p * 2)(*[ptr(t) for t in res[1:]]) if any(t is not None for t in res[1:]) else None
+        with torch.cuda.device(x.device):
+            check(lib().sfa_model_stem_grad(self._h, x.data_ptr(), *(t.data_ptr() for t in maps), B, H, W, ptr(res[0]),
+                                            dparams, int(max_chunk_pixels), workspace.data_ptr(), workspace.numel(),
+                                            _lib.stream_ptr(x.device)), "sfa_model_stem_grad")
+        return res[0], res[1:]
+
     def forward(self, x: torch.Tensor, in_layout: int = _lib.IN_NCHW3) -> dict:
         x = _require_gpu_tensor(x, "PoseResNet.forward")
         if in_layout != _lib.IN_NHWC4:
