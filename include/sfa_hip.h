@@ -234,8 +234,14 @@ void sfa_model_destroy(sfa_model* model);
  * cannot make that call turns the images off with SFA_OPT_W_IMAGES = 0.  (The Python model creates a new
  * handle from freshly packed weights whenever a parameter changes, heads_trainable() steps included.) */
 int sfa_model_refresh_weight_images(sfa_model* model, void* stream);
-/* Bytes of device memory the handle's derived weight images take (shared with its twins); 0: it has none. */
+/* Bytes of device memory the handle's derived weight images of the detection heads take (shared with its
+ * twins); 0: it has none. */
 size_t sfa_model_weight_image_bytes(const sfa_model* model);
+/* The residual layers' 3x3 / stride-1 convs (all of layer1, block 1 of layers 2 - 4) have derived weight images
+ * too, in a second device buffer under the same rules (built at create, shared with twins, rebuilt by
+ * sfa_model_refresh_weight_images, read only when SFA_OPT_W_IMAGES and SFA_OPT_BODY_W_IMAGES are both 1).
+ * Its bytes (the size of those convs' fp16 terms again, ~25 MB); 0: the handle has none. */
+size_t sfa_model_body_weight_image_bytes(const sfa_model* model);
 
 /* Side streams on (1, the default; env SFA_SIDE_STREAMS=0 at create time turns them off) or
  * off (0: every launch of the forward on the caller's stream).  Off destroys them (after their
@@ -305,9 +311,12 @@ int sfa_model_get_math(const sfa_model* model);
  *   SFA_OPT_W_IMAGES    (SFA_W_IMAGES)    1 (default): the fp16x3 heads read W from the derived weight
  *                                         images (above), when the handle has them; 0: from the packed
  *                                         terms; the same bits
+ *   SFA_OPT_BODY_W_IMAGES (SFA_BODY_W_IMAGES) 1 (default): the residual layers' fp16x3 strip convs read W
+ *                                         from their derived weight images, when the handle has them and
+ *                                         SFA_OPT_W_IMAGES is 1; 0: from the packed terms; the same bits
  */
 enum sfa_model_option { SFA_OPT_STEM_PATCH = 0, SFA_OPT_FPN_COMMUTE = 1, SFA_OPT_FPN_GEMM = 2,
-                        SFA_OPT_SPLITK_TICKETS = 3, SFA_OPT_W_IMAGES = 16 };
+                        SFA_OPT_SPLITK_TICKETS = 3, SFA_OPT_W_IMAGES = 16, SFA_OPT_BODY_W_IMAGES = 17 };
 int sfa_model_set_option(sfa_model* model, int key, int value);
 int sfa_model_get_option(const sfa_model* model, int key, int* value);
 

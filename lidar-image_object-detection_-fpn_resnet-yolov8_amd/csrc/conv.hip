@@ -84,6 +84,8 @@ constexpr int H3_PIPE = h3opt::PIPE;
 static_assert(R3_BODY == 526592 && R3_FPN == 35072 && R3_HEAD_STAG == 3766532 && R3_HEAD_STAG_IMG == 7960836,
               "conv_r3 instance names");
 static_assert(H3S_64 == 1166 && H3S_128 == 1166 && H3S_128W == 1038, "conv_h3s instance names");
+static_assert((H3S_64 | h3sopt::W_IMAGE) == 3214 && (H3S_128W | h3sopt::W_IMAGE) == 3086,
+              "conv_h3s image instance names");
 static_assert(H3_PLAIN == 0 && H3_PIPE == 2, "conv_h3 instance names");
 
 // FPN 1x1 convs (commuted: the low-resolution W_a . x and the skip conv with the upsampled
@@ -109,6 +111,16 @@ static int launch_fpn(const ConvArgs& a, hipStream_t st) {
     if (C == 512 && a.N % 64 == 0) return launch_fpn_gemm_cfg<512, 64, false, 1>(a, st);
   }
   return SFA_E_UNSUPPORTED;
+}
+
+// A strip launch: the instance with W from the conv's pre-tiled LDS image (h3sopt::W_IMAGE) when
+// the model set ConvArgs::wimg (fp16x3; the one-product mode keeps row-major W), else the row-major one.
+// conv_plan.h strip_tile_bn restates which tile width each rule below gives a conv: keep them together.
+template <int BM, int BN, int WM, int OCC, int ABL, int TERMS>
+static int launch_strip(const ConvArgs& a, hipStream_t st) {
+  if constexpr (TERMS == 2)
+    if (a.wimg) return launch_conv_h3s_cfg<BM, BN, WM, EPI_STD, OCC, ABL | h3sopt::W_IMAGE, 2>(a, st);
+  return launch_conv_h3s_cfg<BM, BN, WM, EPI_STD, OCC, ABL, TERMS>(a, st);
 }
 
 // The fp16 dispatch rules, once for both modes: TERMS = 2 is fp16x3 (two fp16 terms per operand, three
@@ -151,7 +163,7 @@ static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
     }
   }
   if (a.N == 64) {
-    if (strip) rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64, TERMS>(a, st);
+    if (strip) rc = launch_strip<128, 64, 32, 3, H3S_64, TERMS>(a, st);
     if (!ok(rc) && a.Kpad >= 256)
       rc = launch_conv_h3_cfg<256, 64, 32, EPI_STD, 1, 32, 2, false, H3_PLAIN, 1, 64, TERMS>(a, st);
     if constexpr (TERMS == 2) {
@@ -167,14 +179,14 @@ static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
       // layer3 (362 128-row tiles for 512 block slots): 64 x 128 tiles at 3 blocks / CU fill the
       // chip; same per-element K order, so the same bits (tools/convbench4: 97.7 vs 102.0 us,
       // profiles/r04a_convbench4_stem_regw_tiles.txt)
-      rc = launch_conv_h3s_cfg<64, 128, 16, EPI_STD, 3, H3S_128, TERMS>(b, st);
+      rc = launch_strip<64, 128, 16, 3, H3S_128, TERMS>(b, st);
     else if (strip && b.ksplit == 2 && a.N == 512 && tile_rows(a) < 50000)
       // layer4 (184 128 x 128 tiles x 2 slices for 512 block slots): the 64-wide layer1 form, 128 x 64
       // tiles at 3 blocks / CU (736 blocks for 768 slots); same slices and per-element K order, so the
       // same bits (tools/convbench4: 102.4-105.0 vs 107.4-110.7 us, profiles/r04o_convbench4_layer4_splits.txt)
-      rc = launch_conv_h3s_cfg<128, 64, 32, EPI_STD, 3, H3S_64, TERMS>(b, st);
+      rc = launch_strip<128, 64, 32, 3, H3S_64, TERMS>(b, st);
     else if (strip && (3 * (a.seg[0].C >> 5)) % b.ksplit == 0)
-      rc = launch_conv_h3s_cfg<128, 128, 32, EPI_STD, 3, H3S_128W, TERMS>(b, st);
+      rc = launch_strip<128, 128, 32, 3, H3S_128W, TERMS>(b, st);
     else if (!strip && tile_rows(a) >= 50000)  // big-M stride-2 / two-segment: A from registers
       // (3 blocks / CU, late round 5: 150-153 VGPRs, 722 tiles in one round; per launch within 1 %, bench
       // +0.9 % with two steps in flight, bit-identical: profiles/r05bp_*)

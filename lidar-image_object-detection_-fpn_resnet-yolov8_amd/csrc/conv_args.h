@@ -146,6 +146,9 @@ struct ConvArgs {
   // pieces from the row-major terms. Kernel instances without an image form never read it.
   const unsigned char* wimg;
   unsigned wimg_bytes;
+  // the tile width the image was built for (an image's size does not depend on it); read by the strip
+  // kernel's launch check, the heads' 256 x 320 instance has one width
+  int wimg_bn;
 };
 
 // Transposed convolution k=4 / s=2 / p=1 + folded BN + ReLU, fp16x3 (deconv_h3_kernel.h): the four

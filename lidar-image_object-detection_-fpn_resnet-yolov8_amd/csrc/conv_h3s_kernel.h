@@ -46,8 +46,14 @@ constexpr int REG_W = 256;
 // the next (kh, chunk) strip with buffer loads at kw 1 and splits them from its VGPRs at kw 0, so the f32
 // strip never passes through LDS (no strip buffer, no LDS-DMA pieces, no f32 LDS reads in the split).
 constexpr int STRIP_REGS = 1024;
+// W pieces from the conv's pre-tiled LDS image (a.wimg, conv_wimage.h: WImageGeom::strip, the K-tiles in this
+// kernel's (kh, chunk, kw) order) instead of gathered from the row-major terms: piece e of K-tile kt of column
+// tile nt is the 1,024 contiguous bytes at ((nt * ktiles + kt) * ND_B + e) * 1024, the lane part of the offset
+// 16 * lane, the rest wave-uniform. The same LDS bytes, so the same fragments and products. A split-K slice
+// finds its K-tiles 3 s0 .. contiguous in the one image. fp16x3 by LDS-DMA only (not REG_W, not TERMS == 1).
+constexpr int W_IMAGE = 2048;
 constexpr int ALWAYS = TRANSPOSED | MIX_SPLIT;  // set in every product instance
-constexpr int ALLOWED = ALWAYS | PRESPLIT | RES_PREFETCH | REG_W | STRIP_REGS;
+constexpr int ALLOWED = ALWAYS | PRESPLIT | RES_PREFETCH | REG_W | STRIP_REGS | W_IMAGE;
 }  // namespace h3sopt
 
 // TERMS: 2 = fp16x3; 1 = SFA_MATH_FP16 (one product per MAC, conv_r3_kernel.h): the pre-split rows hold the
@@ -69,6 +75,8 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
   constexpr bool RESPF = PS && (ABL & h3sopt::RES_PREFETCH) != 0;
   constexpr bool RW = (ABL & h3sopt::REG_W) != 0;
   constexpr bool SREG = (ABL & h3sopt::STRIP_REGS) != 0;
+  constexpr bool WIMG = (ABL & h3sopt::W_IMAGE) != 0;
+  static_assert(!WIMG || (TERMS == 2 && !RW), "W images: fp16x3, W by LDS-DMA");
   constexpr int PROWS = WM + 2;              // a wave's pre-split rows (its WM rows + the kw halo)
   constexpr int PR_BYTES = (PROWS + 1) * 64;  // per term: 32 fp16 per row, + one zero row
   constexpr int NSB = PS ? (SREG ? 0 : 1) : 2;  // f32 strip buffers
@@ -123,16 +131,25 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
   const __amdgpu_buffer_rsrc_t rsx =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.x), (short)0, (int)g.bytes, 0x00020000);
   const unsigned term_bytes = (unsigned)a.N * (unsigned)a.Kpad * 2u;
-  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.wh), (short)0,
-                                                                       (int)(2 * term_bytes), 0x00020000);
-  int boff[NB];  // int + unsigned cast at the use (see conv_h3_kernel)
+  // WIMG: the conv's LDS image, checked against this instance's geometry at launch (conv_h3s_image_check)
+  const __amdgpu_buffer_rsrc_t rsw =
+      WIMG ? __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.wimg), (short)0, (int)a.wimg_bytes,
+                                               0x00020000)
+           : __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.wh), (short)0, (int)(2 * term_bytes),
+                                               0x00020000);
+  // WIMG: one VGPR for every piece, the lane's 16 bytes of the wave's first piece of column tile nt's image
+  // (the uniform K-tile and piece parts are added at the use, as in conv_r3_kernel.h)
+  [[maybe_unused]] const int wlane = 16 * lane + (nt * (a.Kpad >> 5) * ND_B + wave) * 1024;
+  [[maybe_unused]] int boff[NB];  // int + unsigned cast at the use (see conv_h3_kernel)
+  if constexpr (!WIMG) {
 #pragma unroll
-  for (int jj = 0; jj < NB; ++jj) {
-    const int e = wave + NW * jj < ND_B ? wave + NW * jj : ND_B - 1;
-    const int term = e / (ND_B / TERMS);
-    const int R = (e - term * (ND_B / TERMS)) * 16 + (lane >> 2);
-    const int lc = (lane & 3) ^ swzB(R);
-    boff[jj] = (int)(term * term_bytes) + (int)(((n0 + R) * a.Kpad + 8 * lc) << 1);
+    for (int jj = 0; jj < NB; ++jj) {
+      const int e = wave + NW * jj < ND_B ? wave + NW * jj : ND_B - 1;
+      const int term = e / (ND_B / TERMS);
+      const int R = (e - term * (ND_B / TERMS)) * 16 + (lane >> 2);
+      const int lc = (lane & 3) ^ swzB(R);
+      boff[jj] = (int)(term * term_bytes) + (int)(((n0 + R) * a.Kpad + 8 * lc) << 1);
+    }
   }
   auto swzP = [](int R) { return ((R >> 2) & 1) << 1; };  // conflict-free at every kw row offset
 
@@ -179,13 +196,17 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
       xs[p] = __builtin_bit_cast(x6_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsx, off, 0, 0));
     }
   };
+  // k0: the K-tile's first weight column (wk0 below), or (WIMG) its index in the image
   auto load_w = [&](int k0, unsigned char* S) {
 #pragma unroll
     for (int jj = 0; jj < NB; ++jj) {
-      if (NB_REM == 0 || jj < NB - 1 || wave < NB_REM)
+      if (NB_REM == 0 || jj < NB - 1 || wave < NB_REM) {
+        unsigned off;
+        if constexpr (WIMG) off = (unsigned)(wlane + k0 * W_BYTES + NW * jj * 1024);
+        else off = (unsigned)(boff[jj] + 2 * k0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsw, (__attribute__((address_space(3))) void*)(S + (wave + NW * jj) * 1024), 16,
-            (unsigned)(boff[jj] + 2 * k0), 0, 0, 0);
+            rsw, (__attribute__((address_space(3))) void*)(S + (wave + NW * jj) * 1024), 16, off, 0, 0, 0);
+      }
     }
   };
   // the fp16x3 scales of the block's first two frames (uniform loads); x of this lane's A row in each
@@ -239,7 +260,8 @@ __global__ void __launch_bounds__((BM / WM) * 64, OCC) conv_h3s_kernel(const Con
     else if (NS_REM == 0 || wave < NS_REM) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NS) : "memory");
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NS - 1) : "memory");
   };
-  auto wk0 = [&](int s, int kw) {  // K offset of the W tile of super-step s, tap kw
+  auto wk0 = [&](int s, int kw) {  // K offset of the W tile of super-step s, tap kw (WIMG: its K-tile index)
+    if constexpr (WIMG) return 3 * s + kw;
     const int kh = s >> lognchunk, c0 = (s & (nchunk - 1)) << 5;
     return (kh * 3 + kw) * g.C + c0;
   };
@@ -508,6 +530,8 @@ template <int BM, int BN, int WM, int EPI, int OCC, int ABL = 0, int TERMS = 2>
 inline int launch_conv_h3s_cfg(const ConvArgs& a, hipStream_t st) {
   unsigned grid;
   if (int rc = conv_h3s_check(a, BM, BN, EPI, &grid)) return rc;
+  if constexpr ((ABL & h3sopt::W_IMAGE) != 0)  // the image must be this instance's (tile width, K order)
+    if (int rc = conv_h3s_image_check(a, BN)) return rc;
   const int ks = ksplit_of(a);
   ConvArgs b = a;  // the strip rows' multiply-high divisions
   b.fd_w = make_fast_div((unsigned)a.seg[0].W);

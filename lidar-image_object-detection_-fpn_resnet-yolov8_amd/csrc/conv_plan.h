@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "conv_args.h"
+#include "conv_wimage.h"
 
 namespace sfa {
 
@@ -131,6 +132,20 @@ inline bool strip_ok(const ConvArgs& a) {
          (g.C & 31) == 0 && a.Kpad == 9 * g.C && a.OH == g.H && a.OW == g.W;
 }
 
+// The tile width of the strip instance conv.hip's launch_conv_h gives this fp16x3 conv (its strip rules,
+// restated: 64-wide convs and the split-K 2 layer4 form on 128 x 64 tiles, the rest 128 wide), or 0 when
+// the conv takes another family. The model asks it before it hands a launch the conv's W image, which is
+// built for one tile width; the launch check (conv_h3s_image_check) refuses an image of another width.
+inline int strip_tile_bn(const ConvArgs& a) {
+  if (!strip_ok(a) || conv_sliced(a) || !a.wh || !a.winv || a.OH * a.OW < 128) return 0;
+  if (a.N == 64) return 64;
+  if (a.N % 128 != 0) return 0;
+  const int ks = pick_ksplit(a);
+  if (ks == 1 && a.N == 256 && tile_rows(a) < 50000) return 128;
+  if (ks == 2 && a.N == 512 && tile_rows(a) < 50000) return 64;
+  return (3 * (a.seg[0].C >> 5)) % ks == 0 ? 128 : 0;
+}
+
 // ---- the per-family checks: SFA_OK with the launch's grid, or the refusal
 
 inline int conv_f32_check(const ConvArgs& a, int BM, int BN, int BK, unsigned* grid) {
@@ -189,6 +204,21 @@ inline int conv_h3s_check(const ConvArgs& a, int BM, int BN, int epi, unsigned* 
   if (int rc = check_splitk("conv_h3s", a, epi, 3 * (g.C >> 5), "C", g.C)) return rc;
   if (int rc = check_weight_bytes("conv_h3s", 2, a.N, a.Kpad)) return rc;
   return check_grid("conv_h3s", a.M, a.N, BM, BN, ksplit_of(a), grid);
+}
+
+// The image of a conv_h3s instance with h3sopt::W_IMAGE: the whole conv in the strip K order at the
+// instance's tile width (after conv_h3s_check: a one-segment 3x3 conv, no K-slice).
+inline WImageGeom conv_h3s_image_geom(const ConvArgs& a, int BN) {
+  return WImageGeom{a.N, a.Kpad, a.Kpad, 0, BN, 2, 0, a.seg[0].C, 1};
+}
+inline int conv_h3s_image_check(const ConvArgs& a, int BN) {
+  const WImageGeom g = conv_h3s_image_geom(a, BN);
+  const char* err = wimage_check(g);
+  if (!err && (!a.wimg || a.wimg_bytes != wimage_bytes(g) || a.wimg_bn != BN))
+    err = "conv_h3s: W image does not fit this kernel instance";
+  if (!err) return SFA_OK;
+  set_error("%s", err);
+  return SFA_E_INVALID;
 }
 
 // conv_r3: res_up_epi / scalar_taps / chunk_major are the instance's r3opt bits of those names

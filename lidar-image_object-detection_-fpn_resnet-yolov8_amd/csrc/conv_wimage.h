@@ -37,6 +37,11 @@ struct WImageGeom {
   // channels: K-tile kt covers tap kt % 9 of the 32-channel chunk kt / 9; the tiles after them
   // (a fused 1x1 downsample segment) and every tile of a tap-major kernel (cmaj_tiles 0): kt * 32
   int cmaj_tiles, C;
+  // strip K order (conv_h3s_kernel; 0: the orders above): a whole 3x3 window of C channels, K = 9 C,
+  // swept as (kh, 32-channel chunk, kw): K-tile kt is tap kw = kt % 3 of super-step s = kt / 3,
+  // kh = s / (C / 32), chunk = s % (C / 32). A split-K slice of the launch sweeps a contiguous run of
+  // super-steps, so its K-tiles are contiguous in the one image of the conv.
+  int strip;
 };
 
 constexpr int WIMG_BK = 32;       // K columns per K-tile
@@ -54,6 +59,11 @@ SFA_WIMG_FN size_t wimage_bytes(const WImageGeom& g) {
 
 // first weight column (inside the slice) of K-tile kt, in the kernel's order (conv_r3_kernel.h kcol)
 SFA_WIMG_FN int wimage_kcol(const WImageGeom& g, int kt) {
+  if (g.strip) {  // conv_h3s_kernel.h wk0
+    const int nchunk = g.C / WIMG_BK, s = kt / 3, kw = kt - 3 * s;
+    const int kh = s / nchunk, chunk = s - kh * nchunk;
+    return (kh * 3 + kw) * g.C + chunk * WIMG_BK;
+  }
   if (kt < g.cmaj_tiles) {
     const int chunk = kt / 9;
     return (kt - 9 * chunk) * g.C + chunk * WIMG_BK;
@@ -93,6 +103,8 @@ inline const char* wimage_check(const WImageGeom& g) {
   if (g.cmaj_tiles < 0 || g.cmaj_tiles > wimage_ktiles(g)) return "wimage: chunk-major tiles outside K";
   if (g.cmaj_tiles > 0 && (g.C < WIMG_BK || g.C % WIMG_BK != 0 || g.cmaj_tiles != 9 * (g.C / WIMG_BK)))
     return "wimage: chunk-major order needs a 3x3 window of C % 32 == 0 channels";
+  if (g.strip && (g.cmaj_tiles != 0 || g.C < WIMG_BK || g.C % WIMG_BK != 0 || g.K != 9 * g.C))
+    return "wimage: strip order needs a whole 3x3 window of C % 32 == 0 channels";
   // the kernels address both buffers with 32-bit byte offsets
   if (wimage_bytes(g) >= (1ull << 31) || 2ull * g.terms * g.N * g.wstride >= (1ull << 31))
     return "wimage: image or terms above 2 GiB";
@@ -100,15 +112,21 @@ inline const char* wimage_check(const WImageGeom& g) {
 }
 
 // The images of one model in one device buffer: 256-B aligned, disjoint, in the order given.
-constexpr int WIMG_MAX = 8;
-struct WImagePlan {
+// MAX: the plan's cap. The heads' plan (WImagePlan) and the body convs' (WBodyImagePlan, a second buffer).
+template <int MAX>
+struct WImagePlanT {
   int count;
-  size_t off[WIMG_MAX], bytes[WIMG_MAX];
+  size_t off[MAX], bytes[MAX];
   size_t total;
 };
+constexpr int WIMG_MAX = 8;
+using WImagePlan = WImagePlanT<WIMG_MAX>;
+constexpr int WIMG_BODY_MAX = 16;  // the residual layers have 16 convs
+using WBodyImagePlan = WImagePlanT<WIMG_BODY_MAX>;
 
-inline const char* wimage_plan(const WImageGeom* g, int count, WImagePlan* p) {
-  if (count < 0 || count > WIMG_MAX) return "wimage: too many images";
+template <int MAX>
+inline const char* wimage_plan(const WImageGeom* g, int count, WImagePlanT<MAX>* p) {
+  if (count < 0 || count > MAX) return "wimage: too many images";
   p->count = count;
   size_t cur = 0;
   for (int i = 0; i < count; ++i) {

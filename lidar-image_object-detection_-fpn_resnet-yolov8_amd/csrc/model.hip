@@ -18,6 +18,7 @@
 
 #include "aux_kernels.h"
 #include "conv.h"
+#include "conv_plan.h"
 
 namespace sfa {
 
@@ -343,6 +344,21 @@ struct WImages {
   }
 };
 
+// ... and of the residual layers' 3x3 / stride-1 convs on conv_h3s_kernel (h3sopt::W_IMAGE): a second device
+// buffer with a plan of its own, about the size of those convs' fp16 terms again (~25 MB). One image per conv,
+// in the strip K order at the tile width its strip instance has at the maps conv.hip gives that instance
+// (body_image_bn); a launch that takes another tile width or family reads the packed terms (Fwd::layers).
+struct WBodyImages {
+  unsigned char* dev = nullptr;
+  int index[4][4];  // image of conv k of layer li (Fwd::layers' order), or -1
+  size_t wh[sfa::WIMG_BODY_MAX];  // the conv's packed fp16 terms (floats into the packed buffer)
+  sfa::WImageGeom geom[sfa::WIMG_BODY_MAX];
+  sfa::WBodyImagePlan plan;
+  ~WBodyImages() {
+    if (dev) (void)hipFree(dev);
+  }
+};
+
 struct sfa_model {
   sfa_arch arch;
   int backbone = SFA_BACKBONE_KFPN;  // sfa_backbone: what follows layer4
@@ -371,6 +387,10 @@ struct sfa_model {
   // packed weights not in device memory, another head count): the row-major kernels run.
   int w_images = 1;
   std::shared_ptr<WImages> wimg;
+  // the residual layers' strip convs read W from their images (1, env SFA_BODY_W_IMAGES) or from the packed
+  // terms (0); the same bits. Both this and w_images must be on. `bimg` is null as `wimg` is.
+  int body_w_images = 1;
+  std::shared_ptr<WBodyImages> bimg;
   // Side stream for the level-0 heads (they only need up_level2, so they overlap the rest
   // of the FPN and the level-1/2 heads); created with the model on the current device,
   // used only when the forward's stream is on that device.
@@ -415,7 +435,11 @@ static sfa::WImageGeom head_wimage_geom(const PHeads& hp, int Cin) {
   return sfa::WImageGeom{hp.N, hp.K, hp.K, 0, 320, 2, hp.K / 32, Cin};
 }
 
-// (Re)builds every image from the packed weights, on `st`.
+// The tile width of the strip instance a body conv of N output channels runs on (conv.hip: 64-wide convs and
+// the split-K 2 layer4 convs on 128 x 64 tiles, layer2 / 3 on 128-wide tiles).
+static int body_image_bn(int N) { return N == 64 || N == 512 ? 64 : 128; }
+
+// (Re)builds the heads' images from the packed weights, on `st`.
 static int fill_wimages(const sfa_model* m, hipStream_t st) {
   const WImages& wi = *m->wimg;
   for (int f = 0; f < wi.plan.count; ++f)
@@ -425,11 +449,20 @@ static int fill_wimages(const sfa_model* m, hipStream_t st) {
   return SFA_OK;
 }
 
+// ... and the body convs'.
+static int fill_body_wimages(const sfa_model* m, hipStream_t st) {
+  const WBodyImages& bi = *m->bimg;
+  for (int i = 0; i < bi.plan.count; ++i)
+    if (int rc = sfa::launch_wimage_build(bi.geom[i], reinterpret_cast<const uint16_t*>(m->w + bi.wh[i]),
+                                          bi.dev + bi.plan.off[i], st))
+      return rc;
+  return SFA_OK;
+}
+
 // Allocates and builds the images at create. Only from packed weights that are device memory of the
 // current device and cover the plan (a handle over anything else, or created without a device, keeps the
 // row-major kernels); built on the null stream and waited for, so a forward on any stream finds them.
-static void make_wimages(sfa_model* m) {
-  if (m->plan.heads[0].N != 320) return;  // the image instance is the five-head 256 x 320 tile
+static bool weights_on_device(const sfa_model* m) {
   hipPointerAttribute_t at;
   memset(&at, 0, sizeof at);
   void* base = nullptr;
@@ -441,10 +474,12 @@ static void make_wimages(sfa_model* m) {
       hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &range, const_cast<float*>(m->w)) == hipSuccess &&
       (reinterpret_cast<uintptr_t>(m->w) & 15) == 0 &&
       (size_t)(reinterpret_cast<const char*>(m->w) - static_cast<const char*>(base)) + m->plan.total * 4 <= range;
-  if (!device_weights) {
-    (void)hipGetLastError();
-    return;
-  }
+  if (!device_weights) (void)hipGetLastError();
+  return device_weights;
+}
+
+static void make_wimages(sfa_model* m) {
+  if (m->plan.heads[0].N != 320) return;  // the image instance is the five-head 256 x 320 tile
   auto wi = std::make_shared<WImages>();
   const int nlev = m->backbone == SFA_BACKBONE_DECONV ? 1 : 3;
   for (int f = 0; f < nlev; ++f) wi->geom[f] = head_wimage_geom(m->plan.heads[f], kFpnC[f]);
@@ -457,6 +492,36 @@ static void make_wimages(sfa_model* m) {
   if (fill_wimages(m, nullptr) != SFA_OK || hipStreamSynchronize(nullptr) != hipSuccess) {
     (void)hipGetLastError();
     m->wimg.reset();
+  }
+}
+
+// The body convs' images: the one-segment 3x3 / stride-1 convs of the residual layers (all four of layer1,
+// block 1's two of layers 2 - 4), the ones conv_h3s_kernel runs.
+static void make_body_wimages(sfa_model* m) {
+  auto bi = std::make_shared<WBodyImages>();
+  int n = 0;
+  for (int li = 0; li < 4; ++li)
+    for (int k = 0; k < 4; ++k) {
+      bi->index[li][k] = -1;
+      if (li > 0 && k < 2) continue;  // stride 2 / the fused downsample segment
+      const PConv& pc = m->plan.blk[li][k >> 1][k & 1];
+      const int C = 64 << li;
+      if (pc.Kpad != 9 * C || pc.N % body_image_bn(pc.N) != 0) continue;
+      bi->index[li][k] = n;
+      bi->wh[n] = pc.wh;
+      bi->geom[n] = sfa::WImageGeom{pc.N, pc.Kpad, pc.Kpad, 0, body_image_bn(pc.N), 2, 0, C, 1};
+      ++n;
+    }
+  if (sfa::wimage_plan(bi->geom, n, &bi->plan) != nullptr || bi->plan.total == 0 ||
+      hipMalloc(&bi->dev, bi->plan.total) != hipSuccess) {
+    (void)hipGetLastError();
+    bi->dev = nullptr;
+    return;
+  }
+  m->bimg = bi;
+  if (fill_body_wimages(m, nullptr) != SFA_OK || hipStreamSynchronize(nullptr) != hipSuccess) {
+    (void)hipGetLastError();
+    m->bimg.reset();
   }
 }
 
@@ -673,10 +738,14 @@ static int model_create(const sfa_arch* arch, int backbone, const float* packed_
   if (const char* e = getenv("SFA_FPN_GEMM")) m->fpn_gemm = atoi(e) & 63;
   if (const char* e = getenv("SFA_SPLITK_TICKETS")) m->splitk_tickets = atoi(e) != 0;
   if (const char* e = getenv("SFA_W_IMAGES")) m->w_images = atoi(e) != 0;
-  if (twin_of)
+  if (const char* e = getenv("SFA_BODY_W_IMAGES")) m->body_w_images = atoi(e) != 0;
+  if (twin_of) {
     m->wimg = twin_of->wimg;  // the same weights: the same images
-  else
+    m->bimg = twin_of->bimg;
+  } else if (weights_on_device(m)) {
     make_wimages(m);
+    make_body_wimages(m);
+  }
   bool side_streams = true;  // env SFA_SIDE_STREAMS=0: every launch on the caller's stream (A/B)
   if (const char* e = getenv("SFA_SIDE_STREAMS")) side_streams = strcmp(e, "0") != 0;
   // the deconv family has no parallel branch: no side streams, every launch on the caller's stream
@@ -704,12 +773,18 @@ extern "C" int sfa_model_create_twin(const sfa_model* model, sfa_model** out) {
 
 extern "C" int sfa_model_refresh_weight_images(sfa_model* model, void* stream) {
   SFA_CHECK_ARG(model, "refresh_weight_images: null model");
-  if (!model->wimg) return SFA_OK;  // nothing derived from the weights
-  return fill_wimages(model, reinterpret_cast<hipStream_t>(stream));
+  int rc = SFA_OK;  // (no images: nothing derived from the weights)
+  if (model->wimg) rc = fill_wimages(model, reinterpret_cast<hipStream_t>(stream));
+  if (rc == SFA_OK && model->bimg) rc = fill_body_wimages(model, reinterpret_cast<hipStream_t>(stream));
+  return rc;
 }
 
 extern "C" size_t sfa_model_weight_image_bytes(const sfa_model* model) {
   return model && model->wimg ? model->wimg->plan.total : 0;
+}
+
+extern "C" size_t sfa_model_body_weight_image_bytes(const sfa_model* model) {
+  return model && model->bimg ? model->bimg->plan.total : 0;
 }
 
 extern "C" void sfa_model_destroy(sfa_model* model) {
@@ -760,6 +835,10 @@ extern "C" int sfa_model_set_option(sfa_model* model, int key, int value) {
       SFA_CHECK_ARG(value == 0 || value == 1, "set_option: W_IMAGES %d not 0 / 1", value);
       model->w_images = value;
       break;
+    case SFA_OPT_BODY_W_IMAGES:
+      SFA_CHECK_ARG(value == 0 || value == 1, "set_option: BODY_W_IMAGES %d not 0 / 1", value);
+      model->body_w_images = value;
+      break;
     default: set_error("set_option: unknown key %d", key); return SFA_E_INVALID;
   }
   return SFA_OK;
@@ -773,6 +852,7 @@ extern "C" int sfa_model_get_option(const sfa_model* model, int key, int* value)
     case SFA_OPT_FPN_GEMM: *value = model->fpn_gemm; break;
     case SFA_OPT_SPLITK_TICKETS: *value = model->splitk_tickets; break;
     case SFA_OPT_W_IMAGES: *value = model->w_images; break;
+    case SFA_OPT_BODY_W_IMAGES: *value = model->body_w_images; break;
     default: set_error("get_option: unknown key %d", key); return SFA_E_INVALID;
   }
   return SFA_OK;
@@ -1181,6 +1261,17 @@ struct Pass {
         io(a, cv.in.slot, cv.downsample ? x.slot : -1, blk_slot(li, k >> 1, k & 1));
         a.tile_cnt = TK(li, k);
         a.tile_cnt_words = (int)bf.tick_words;
+        // the conv's pre-tiled W image, when this launch takes the strip instance of the image's tile width
+        // (fp16x3: conv.hip reads it, the other modes do not)
+        if (m->w_images && m->body_w_images && m->bimg && m->bimg->index[li][k] >= 0) {
+          const WBodyImages& bi = *m->bimg;
+          const int i = bi.index[li][k];
+          if (strip_tile_bn(a) == bi.geom[i].BN) {
+            a.wimg = bi.dev + bi.plan.off[i];
+            a.wimg_bytes = (unsigned)bi.plan.bytes[i];
+            a.wimg_bn = bi.geom[i].BN;
+          }
+        }
         SFA_RC(launch_conv(a, EPI_STD, m->math, st));
       }
       x = {lv, oh, ow, planes, blk_slot(li, 1, 1)};

@@ -29,7 +29,8 @@ BEV_RAW, BEV_PREFILTERED, BEV_FLIP_HW, BEV_FORCE_ATOMIC, BEV_FORCE_BINNED, BEV_S
 OPT_STEM_PATCH, OPT_FPN_COMMUTE, OPT_FPN_GEMM, OPT_SPLITK_TICKETS = 0, 1, 2, 3
 OPT_COUNT = 4  # keys 0 .. OPT_COUNT - 1
 OPT_W_IMAGES = 16  # derived weight images on / off (outside the dense range)
-OPTION_KEYS = tuple(range(OPT_COUNT)) + (OPT_W_IMAGES,)
+OPT_BODY_W_IMAGES = 17  # the residual layers' weight images alone on / off
+OPTION_KEYS = tuple(range(OPT_COUNT)) + (OPT_W_IMAGES, OPT_BODY_W_IMAGES)
 IN_NCHW3, IN_NHWC4, IN_NCHW3_FLIP_HW = 0, 1, 2
 
 
@@ -118,6 +119,7 @@ PROBE_HEADS, PROBE_SERIAL = 1, 2
 _PROTOS["sfa_model_create_twin"] = (_c_int, [_vp, ctypes.POINTER(_vp)])
 _PROTOS["sfa_model_refresh_weight_images"] = (_c_int, [_vp, _vp])
 _PROTOS["sfa_model_weight_image_bytes"] = (_c_size, [_vp])
+_PROTOS["sfa_model_body_weight_image_bytes"] = (_c_size, [_vp])
 _PROTOS["sfa_model_set_probe"] = (_c_int, [_vp, _c_int])
 _PROTOS["sfa_model_set_side_streams"] = (_c_int, [_vp, _c_int])
 _PROTOS["sfa_model_probe_times"] = (_c_int, [_vp, ctypes.POINTER(ctypes.c_float), _c_int])

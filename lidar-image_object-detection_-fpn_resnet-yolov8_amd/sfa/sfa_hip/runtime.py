@@ -126,6 +126,11 @@ class KfpnEngine:
         if it has none."""
         return int(lib().sfa_model_weight_image_bytes(self._h))
 
+    def body_weight_image_bytes(self) -> int:
+        """Device bytes of the derived weight images of the residual layers' strip convs (a second buffer,
+        shared with the twins), 0 if the handle has none."""
+        return int(lib().sfa_model_body_weight_image_bytes(self._h))
+
     def refresh_weight_images(self, stream: int = None):
         """Rebuild the derived weight images from ``self.weights`` on ``stream`` (default: the current one):
         after any in-place change of the packed device weights, before the next forward."""
