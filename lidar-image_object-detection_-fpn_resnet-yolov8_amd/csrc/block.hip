@@ -4,8 +4,8 @@
 //   forward   launch_frame_amax on x, launch_conv (fp16x3, conv1 + shift + ReLU) -> mid, launch_frame_amax on mid,
 //             launch_conv (conv2 + shift + skip + ReLU; the downsample as its second K segment) -> y
 //   gradient  block_dgrad_kernel   dA = mid > 0 ? dgrad_1(dZ; W2') : 0, dZ = y > 0 ? gy : 0 masked as it is loaded
-//             block_wgrad_kernel + fold   dW2' (dZ, mid), dW1' (dA, x), dWd' (dZ, x through the centre tap)
-//             block_bias_kernel + fold    db2' (dZ), db1' (dA)
+//             block_wgrad_kernel + the shared fold   dW2' (dZ, mid), dW1' (dA, x), dWd' (dZ, x through the centre tap)
+//             the shared bias pair (grad_common.hip)   db2' (dZ), db1' (dA)
 //             block_dgrad_kernel   dx = dgrad_s(dA; W1') + the skip: dZ in the epilogue (identity) or the 1x1
 //                                  stride-s downsample as a second K segment on the centre tap
 //             Only what a wanted output needs is launched.
@@ -15,26 +15,11 @@
 #include "block_kernel.h"
 #include "conv.h"
 #include "dispatch.h"
+#include "grad_host.h"
 
 using namespace sfa;
 
-int sfa::launch_block_wgrad_fold(const BlockWgrad& g, const float* part, float* dW, hipStream_t st) {
-  return launch({dim3((unsigned)ceil_div(g.rows * g.taps * g.cin, 256)), dim3(256), st}, block_wgrad_fold_kernel, part,
-                g.chunks, g.rows, g.cin, g.taps, dW);
-}
-
-int sfa::launch_block_bias_grad(const BlockBias& b, const float* g, const float* gm, double* part, float* db,
-                                hipStream_t st) {
-  const unsigned cy = (unsigned)ceil_div(b.cout, 256);
-  if (int rc = launch({dim3((unsigned)b.blocks, cy), dim3(256), st}, block_bias_kernel, g, gm, part, b.npix, b.pixels,
-                      b.cout))
-    return rc;
-  return launch({dim3(cy), dim3(256), st}, block_bias_fold_kernel, part, b.blocks, b.cout, db);
-}
-
 namespace {
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 int block_level(const char* who, const sfa_model* model, int layer, int block, BlockLevel* bl) {
   SFA_CHECK_ARG(model, "%s: null model", who);
@@ -48,17 +33,13 @@ int block_level(const char* who, const sfa_model* model, int layer, int block, B
 int wgrad(const BlockWgrad& g, const BlockShape& s, const float* gr, const float* gm, const float* x, int h, int w,
           int stride, int tap0, float* part, float* dW, hipStream_t st) {
   const BkWgrad t = {gr, gm, x, h, w, s.oh, s.ow, stride, g.cin, g.rows, tap0, g.taps, g.npix, g.Kc};
-  const dim3 grid((unsigned)g.chunks, (unsigned)(g.taps * g.cin / kBkTile), (unsigned)(g.rows / kBkTile));
+  const dim3 grid((unsigned)g.chunks, (unsigned)(g.taps * g.cin / kGradTile), (unsigned)(g.rows / kGradTile));
   if (int rc = launch({grid, dim3(256), st}, block_wgrad_kernel, t, part)) return rc;
-  return launch_block_wgrad_fold(g, part, dW, st);
-}
-
-int bias_grad(const BlockBias& b, const float* g, const float* gm, double* part, float* db, hipStream_t st) {
-  return launch_block_bias_grad(b, g, gm, part, db, st);
+  return launch_wgrad_fold(part, g.chunks, g.rows, g.cin, g.taps, dW, g.cin, 0, st);
 }
 
 int dgrad(const BkDgrad& t, float* out, hipStream_t st) {
-  return launch({dim3((unsigned)block_tiles(t.npix), (unsigned)(t.cin / kBkTile)), dim3(256), st}, block_dgrad_kernel, t,
+  return launch({dim3((unsigned)grad_tiles(t.npix), (unsigned)(t.cin / kGradTile)), dim3(256), st}, block_dgrad_kernel, t,
                 out);
 }
 
@@ -69,10 +50,8 @@ extern "C" size_t sfa_model_block_forward_workspace_size(const sfa_model* model,
   BlockLevel bl;
   BlockForwardPlan plan;
   if (block_level("block_forward_workspace_size", model, layer, block, &bl) != SFA_OK) return 0;
-  if (!block_forward_plan(layer, block, B, h, w, &plan)) {
-    set_error("block_forward_workspace_size: B %d x %d x %d is outside the plan's range", B, h, w);
-    return 0;
-  }
+  if (!block_forward_plan(layer, block, B, h, w, &plan))
+    return refused("block_forward_workspace_size: B %d x %d x %d is outside the plan's range", B, h, w);
   return plan.total;
 }
 
@@ -86,7 +65,7 @@ extern "C" int sfa_model_block_forward(const sfa_model* model, int layer, int bl
   SFA_CHECK_ARG(block_forward_plan(layer, block, B, h, w, &plan), "block_forward: B %d x %d x %d has a map of 2^31 bytes",
                 B, h, w);
   SFA_CHECK_ARG(x && mid_out && y_out && workspace, "block_forward: null argument");
-  SFA_CHECK_ARG(aligned16(x) && aligned16(mid_out) && aligned16(y_out) && aligned16(workspace),
+  SFA_CHECK_ARG(all_aligned16({x, mid_out, y_out, workspace}),
                 "block_forward: the maps and the workspace must be 16-byte aligned");
   SFA_CHECK_ARG(workspace_bytes >= plan.total, "block_forward: workspace of %zu bytes, %zu needed", workspace_bytes,
                 plan.total);
@@ -141,11 +120,9 @@ extern "C" size_t sfa_model_block_grad_workspace_size(const sfa_model* model, in
   BlockLevel bl;
   BlockGradPlan plan;
   if (block_level("block_grad_workspace_size", model, layer, block, &bl) != SFA_OK) return 0;
-  if (!block_grad_plan(layer, block, B, h, w, max_chunk_pixels, &plan)) {
-    set_error("block_grad_workspace_size: B %d x %d x %d, max_chunk_pixels %d is outside the plan's range", B, h, w,
-              max_chunk_pixels);
-    return 0;
-  }
+  if (!block_grad_plan(layer, block, B, h, w, max_chunk_pixels, &plan))
+    return refused("block_grad_workspace_size: B %d x %d x %d, max_chunk_pixels %d is outside the plan's range", B, h, w,
+                   max_chunk_pixels);
   return plan.total;
 }
 
@@ -155,11 +132,9 @@ extern "C" int sfa_model_block_grad_chunk_pixels(const sfa_model* model, int lay
   BlockGradPlan plan;
   if (block_level("block_grad_chunk_pixels", model, layer, block, &bl) != SFA_OK) return 0;
   if (which < 0 || which > 2 || !block_grad_plan(layer, block, B, h, w, max_chunk_pixels, &plan) ||
-      plan.wg[which].taps == 0) {
-    set_error("block_grad_chunk_pixels: gradient %d of layer%d.%d at B %d x %d x %d, max_chunk_pixels %d does not exist",
-              which, layer, block, B, h, w, max_chunk_pixels);
-    return 0;
-  }
+      plan.wg[which].taps == 0)
+    return refused("block_grad_chunk_pixels: gradient %d of layer%d.%d at B %d x %d x %d, max_chunk_pixels %d does not exist",
+                   which, layer, block, B, h, w, max_chunk_pixels);
   return plan.wg[which].Kc;
 }
 
@@ -181,8 +156,8 @@ extern "C" int sfa_model_block_grad(const sfa_model* model, int layer, int block
   SFA_CHECK_ARG(bl.downsample || !dWd, "block_grad: layer%d.%d has no downsample to take dWd'", layer, block);
   SFA_CHECK_ARG(grad_x || dW1 || db1 || dW2 || db2 || dWd, "block_grad: no output wanted");
   SFA_CHECK_ARG(x || (!dW1 && !dWd), "block_grad: dW1' and dWd' read x");
-  const void* all[] = {x, mid, y, gy, grad_x, dW1, db1, dW2, db2, dWd, workspace};
-  for (const void* p : all) SFA_CHECK_ARG(aligned16(p), "block_grad: every buffer must be 16-byte aligned");
+  SFA_CHECK_ARG(all_aligned16({x, mid, y, gy, grad_x, dW1, db1, dW2, db2, dWd, workspace}),
+                "block_grad: every buffer must be 16-byte aligned");
   SFA_CHECK_ARG(workspace_bytes >= plan.total, "block_grad: workspace of %zu bytes, %zu needed", workspace_bytes,
                 plan.total);
   const BlockShape& s = plan.s;
@@ -194,7 +169,7 @@ extern "C" int sfa_model_block_grad(const sfa_model* model, int layer, int block
 
   // conv2 and the downsample: dZ = y > 0 ? gy : 0 is never stored
   if (db2)
-    if (int rc = bias_grad(plan.bs, gy, y, bpart, db2, st)) return rc;
+    if (int rc = launch_bias_grad(plan.bs, gy, y, bpart, db2, st)) return rc;
   if (dW2)
     if (int rc = wgrad(plan.wg[1], s, gy, y, mid, s.oh, s.ow, 1, 0, part, dW2, st)) return rc;
   if (dWd)
@@ -208,7 +183,7 @@ extern "C" int sfa_model_block_grad(const sfa_model* model, int layer, int block
   t2.h = s.oh, t2.w = s.ow, t2.oh = s.oh, t2.ow = s.ow, t2.s = 1, t2.cin = s.cout, t2.cout = s.cout, t2.npix = s.npix_out;
   if (int rc = dgrad(t2, dA, st)) return rc;
   if (db1)
-    if (int rc = bias_grad(plan.bs, dA, nullptr, bpart, db1, st)) return rc;
+    if (int rc = launch_bias_grad(plan.bs, dA, nullptr, bpart, db1, st)) return rc;
   if (dW1)
     if (int rc = wgrad(plan.wg[0], s, dA, nullptr, x, h, w, s.stride, 0, part, dW1, st)) return rc;
   if (!grad_x) return SFA_OK;

@@ -1,7 +1,8 @@
 // Plan of sfa_model_block_forward / sfa_model_block_grad (block.hip), plain C++ so that a host program can walk it
 // (tools/block_plan_check.cpp): the shape of one BasicBlock, the pixel tiles of the data gradients, the split-K
-// chunks of the weight gradients, the per-block partials of the bias gradients and the workspace regions.  The
-// entries and the workspace-size functions all go through block_forward_plan() / block_grad_plan().
+// chunks of the weight gradients, the per-block partials of the bias gradients and the workspace regions, built on
+// grad_plan.h's tiles, split-K and bias records.  The entries and the workspace-size functions all go through
+// block_forward_plan() / block_grad_plan().
 //
 // Block layer{L}.{b} (models/fpn_resnet.py:42-71), L = 1..4, b = 0, 1: cout = 64 2^(L-1); cin = cout / 2 and
 // stride 2 with a 1x1 stride-2 downsample for b == 0 && L > 1, else cin = cout, stride 1 and the identity skip.
@@ -12,25 +13,9 @@
 #include <cstdint>
 
 #include "conv_args.h"
-
-#if defined(__HIPCC__)
-#define SFA_BK_HD __host__ __device__
-#else
-#define SFA_BK_HD
-#endif
+#include "grad_plan.h"
 
 namespace sfa {
-
-constexpr int kBkTile = 64;            // pixels (or output channels) and channels of one workgroup (2 x 2 waves of 32 x 32)
-constexpr int kBkStep = 16;            // K of one LDS step (8 MFMA k-steps)
-constexpr int kBkChunkPixels = 2048;   // the plan's own split-K chunk (max_chunk_pixels == 0), in output pixels
-constexpr int kBkBiasMinPixels = 64;   // block_bias_kernel: fewest pixels of one block ...
-constexpr int kBkBiasMaxBlocks = 256;  // ... and most blocks (what its fold walks per channel)
-constexpr size_t kBkAlign = 256;       // workspace regions
-
-struct BlockRange {
-  int first, count;
-};
 
 struct BlockShape {
   int layer, block, B, h, w;
@@ -38,14 +23,9 @@ struct BlockShape {
   int npix_in, npix_out;  // B h w, B oh ow
 };
 
-// One weight-gradient GEMM: rows x (taps cin) of dW over npix output pixels in chunks of Kc (the last may be short).
-struct BlockWgrad {
-  int rows, cin, taps, npix, Kc, chunks;
-};
-
-// One bias gradient: blocks of `pixels` consecutive pixels (the last may be short), cout float64 words each.
-struct BlockBias {
-  int npix, cout, pixels, blocks;
+// One weight-gradient GEMM: rows x (taps cin) of dW over the split-K's output pixels.
+struct BlockWgrad : GradSplitK {
+  int rows, cin, taps;
 };
 
 struct BlockForwardPlan {
@@ -58,13 +38,11 @@ struct BlockForwardPlan {
 struct BlockGradPlan {
   BlockShape s;
   BlockWgrad wg[3];  // dW1' (over x, stride s), dW2' (over mid), dWd' (over x, the centre tap; taps = 0 without one)
-  BlockBias bs;      // db1', db2': the same geometry
+  GradBias bs;       // db1', db2': the same geometry
   // bytes: dA (npix_out x cout), the float32 split-K partials (the largest of the GEMMs: they run one after the
   // other) and the float64 bias partials
   size_t off_da, off_part, off_bpart, total;
 };
-
-inline size_t bk_align_up(size_t v) { return (v + kBkAlign - 1) / kBkAlign * kBkAlign; }
 
 // false: layer or block out of range, non-positive sizes, or a map of 2^31 bytes or more.
 inline bool block_shape(int layer, int block, int B, int h, int w, BlockShape* s) {
@@ -85,73 +63,39 @@ inline bool block_shape(int layer, int block, int B, int h, int w, BlockShape* s
 
 inline bool block_forward_plan(int layer, int block, int B, int h, int w, BlockForwardPlan* p) {
   if (!block_shape(layer, block, B, h, w, &p->s)) return false;
-  size_t cur = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = cur;
-    cur = bk_align_up(cur + bytes);
-    return o;
-  };
-  p->off_amax_x = take((size_t)B * SFA_AMAX_WORDS * 4);
-  p->off_amax_mid = take((size_t)B * SFA_AMAX_WORDS * 4);
+  GradRegions ws;
+  p->off_amax_x = ws.take((size_t)B * SFA_AMAX_WORDS * 4);
+  p->off_amax_mid = ws.take((size_t)B * SFA_AMAX_WORDS * 4);
   p->part_floats = p->s.cout >= 512 ? (size_t)2 * p->s.npix_out * p->s.cout : 0;
-  p->off_part = take(p->part_floats * 4);
-  p->total = cur;
+  p->off_part = ws.take(p->part_floats * 4);
+  p->total = ws.cur;
   return true;
 }
 
 inline bool block_grad_plan(int layer, int block, int B, int h, int w, int max_chunk_pixels, BlockGradPlan* p) {
   if (max_chunk_pixels < 0 || !block_shape(layer, block, B, h, w, &p->s)) return false;
   const BlockShape& s = p->s;
-  const int cap = max_chunk_pixels > 0 ? max_chunk_pixels : kBkChunkPixels;
   const int wcin[3] = {s.cin, s.cout, s.cin}, wtaps[3] = {9, 9, s.downsample ? 1 : 0};
   size_t part = 0;
   for (int i = 0; i < 3; ++i) {
     BlockWgrad& g = p->wg[i];
-    g.rows = s.cout, g.cin = wcin[i], g.taps = wtaps[i], g.npix = s.npix_out;
-    g.Kc = g.npix < cap ? g.npix : cap;
-    g.chunks = (g.npix + g.Kc - 1) / g.Kc;
+    static_cast<GradSplitK&>(g) = grad_split_k(s.npix_out, max_chunk_pixels);
+    g.rows = s.cout, g.cin = wcin[i], g.taps = wtaps[i];
     const size_t bytes = (size_t)g.chunks * g.rows * g.taps * g.cin * 4;
     if (bytes > part) part = bytes;
   }
-  BlockBias& b = p->bs;
-  b.npix = s.npix_out, b.cout = s.cout;
-  int px = (b.npix + kBkBiasMaxBlocks - 1) / kBkBiasMaxBlocks;
-  if (px < kBkBiasMinPixels) px = kBkBiasMinPixels;
-  b.pixels = px;
-  b.blocks = (b.npix + px - 1) / px;
-  size_t cur = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = cur;
-    cur = bk_align_up(cur + bytes);
-    return o;
-  };
-  p->off_da = take((size_t)s.npix_out * s.cout * 4);
-  p->off_part = take(part);
-  p->off_bpart = take((size_t)b.blocks * b.cout * 8);
-  p->total = cur;
+  p->bs = grad_bias(s.npix_out, s.cout);
+  GradRegions ws;
+  p->off_da = ws.take((size_t)s.npix_out * s.cout * 4);
+  p->off_part = ws.take(part);
+  p->off_bpart = ws.take(grad_bias_bytes(p->bs));
+  p->total = ws.cur;
   return true;
-}
-
-// Tiles of kBkTile over n items (pixels of a map): tile t of block_tiles(n).  The kernels call these very functions.
-SFA_BK_HD inline int block_tiles(int n) { return (n + kBkTile - 1) / kBkTile; }
-SFA_BK_HD inline BlockRange block_tile_at(int t, int n) {
-  BlockRange r;
-  r.first = t * kBkTile;
-  r.count = n - r.first < kBkTile ? n - r.first : kBkTile;
-  return r;
-}
-
-// Chunk c of a split of n pixels into runs of `per` (split-K chunks with per = Kc, bias blocks with per = pixels).
-SFA_BK_HD inline BlockRange block_chunk_at(int c, int n, int per) {
-  BlockRange r;
-  r.first = c * per;
-  r.count = n - r.first < per ? n - r.first : per;
-  return r;
 }
 
 // The output pixel (along one axis) that input index i reaches through tap k of a 3-tap / pad-1 / stride-s window:
 // i = o s - 1 + k.  -1: none (between the strides, or outside 0 .. on - 1).
-SFA_BK_HD inline int block_tap_source(int i, int k, int s, int on) {
+SFA_GRAD_HD inline int block_tap_source(int i, int k, int s, int on) {
   const int t = i + 1 - k;
   if (t < 0 || t % s != 0) return -1;
   const int o = t / s;

@@ -18,6 +18,7 @@
 
 #include "conv.h"
 #include "dispatch.h"
+#include "grad_host.h"
 #include "heads_grad_kernel.h"
 
 using namespace sfa;
@@ -27,8 +28,6 @@ int sfa::launch_frame_amax(const float* x, unsigned* amax, int B, int n4, hipStr
 }
 
 namespace {
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 // The checks the two entries share: the level's parameters and the plan.
 int heads_grad_setup(const char* who, const sfa_model* model, int level, int B, int h, int w, int max_chunk_pixels,
@@ -121,7 +120,7 @@ extern "C" int sfa_model_heads_grad(const sfa_model* model, int level, const flo
     t.gb2[j] = grad_b2[j];
     t.ch[j] = hl.ch[j];
   }
-  SFA_CHECK_ARG(aligned16(x) && aligned16(workspace) && aligned16(hidden_out) && aligned16(dhidden_out),
+  SFA_CHECK_ARG(all_aligned16({x, workspace, hidden_out, dhidden_out}),
                 "heads_grad: x, workspace, hidden_out and dhidden_out must be 16-byte aligned");
   if (workspace_bytes < plan.total) {
     set_error("heads_grad: workspace of %zu bytes, %zu needed", workspace_bytes, plan.total);
@@ -171,7 +170,7 @@ extern "C" int sfa_model_heads_input_grad(const sfa_model* model, int level, con
   SFA_CHECK_ARG(heads_dgrad_plan(B, h, w, hl.Cin, hl.num_heads, &dg), "heads_input_grad: B %d x %d x %d has too many tiles",
                 B, h, w);
   SFA_CHECK_ARG(dhidden && grad_x, "heads_input_grad: null argument");
-  SFA_CHECK_ARG(aligned16(dhidden) && aligned16(grad_x) && aligned16(hl.w3),
+  SFA_CHECK_ARG(all_aligned16({dhidden, grad_x, hl.w3}),
                 "heads_input_grad: dhidden, grad_x and the model's weights must be 16-byte aligned");
   return launch({dim3((unsigned)dg.blocks), dim3(256), reinterpret_cast<hipStream_t>(stream)}, heads_dgrad_kernel, dhidden,
                 hl.w3, grad_x, h, w, hl.Cin, plan.M, dg.tiles_per_row, dg.chan_tiles);
@@ -202,7 +201,7 @@ extern "C" int sfa_model_heads_forward(const sfa_model* model, int level, const 
     t.y[j] = y_levels[j];
     t.ch[j] = hl.ch[j];
   }
-  SFA_CHECK_ARG(aligned16(x) && aligned16(workspace) && aligned16(hidden_out),
+  SFA_CHECK_ARG(all_aligned16({x, workspace, hidden_out}),
                 "heads_forward: x, workspace and hidden_out must be 16-byte aligned");
   if (workspace_bytes < fp.total) {
     set_error("heads_forward: workspace of %zu bytes, %zu needed", workspace_bytes, fp.total);

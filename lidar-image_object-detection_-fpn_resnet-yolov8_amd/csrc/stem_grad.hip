@@ -4,8 +4,8 @@
 //   forward   the model's own unfused launches: launch_nchw3_to_nhwc4 with its per-frame max |x| (record zeroed by
 //             launch_zero_words), launch_conv (fp16x3, conv1 + shift + ReLU) -> a, launch_maxpool3s2 -> pooled
 //   gradient  stem_pool_adjoint_kernel   dA = a > 0 ? pool adjoint of gp : 0, written once to the workspace
-//             block.hip's bias launches  db' (dA)
-//             stem_wgrad_kernel + block.hip's fold   dW' (dA, x)
+//             the shared bias pair (grad_common.hip)  db' (dA)
+//             stem_wgrad_kernel + the shared fold   dW' (dA, x)
 //             stem_dgrad_kernel          dx = dgrad_2(dA; W'), only when grad_x is wanted
 // Every check is made before the first launch; nothing allocates or synchronises.
 #include <cstring>
@@ -13,13 +13,12 @@
 #include "aux_kernels.h"
 #include "conv.h"
 #include "dispatch.h"
+#include "grad_host.h"
 #include "stem_grad_kernel.h"
 
 using namespace sfa;
 
 namespace {
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 int stem_level(const char* who, const sfa_model* model, StemLevel* sl) {
   SFA_CHECK_ARG(model, "%s: null model", who);
@@ -34,10 +33,8 @@ extern "C" size_t sfa_model_stem_forward_workspace_size(const sfa_model* model, 
   StemLevel sl;
   StemForwardPlan plan;
   if (stem_level("stem_forward_workspace_size", model, &sl) != SFA_OK) return 0;
-  if (!stem_forward_plan(B, H, W, &plan)) {
-    set_error("stem_forward_workspace_size: B %d x %d x %d is outside the plan's range", B, H, W);
-    return 0;
-  }
+  if (!stem_forward_plan(B, H, W, &plan))
+    return refused("stem_forward_workspace_size: B %d x %d x %d is outside the plan's range", B, H, W);
   return plan.total;
 }
 
@@ -54,7 +51,7 @@ extern "C" int sfa_model_stem_forward(const sfa_model* model, const float* x, in
   }
   SFA_CHECK_ARG(stem_forward_plan(B, H, W, &plan), "stem_forward: B %d x %d x %d has a map of 2^31 bytes", B, H, W);
   SFA_CHECK_ARG(x && a_out && pooled_out && workspace, "stem_forward: null argument");
-  SFA_CHECK_ARG(aligned16(x) && aligned16(a_out) && aligned16(pooled_out) && aligned16(workspace),
+  SFA_CHECK_ARG(all_aligned16({x, a_out, pooled_out, workspace}),
                 "stem_forward: the image, the maps and the workspace must be 16-byte aligned");
   SFA_CHECK_ARG(workspace_bytes >= plan.total, "stem_forward: workspace of %zu bytes, %zu needed", workspace_bytes,
                 plan.total);
@@ -90,11 +87,9 @@ extern "C" size_t sfa_model_stem_grad_workspace_size(const sfa_model* model, int
   StemLevel sl;
   StemGradPlan plan;
   if (stem_level("stem_grad_workspace_size", model, &sl) != SFA_OK) return 0;
-  if (!stem_grad_plan(B, H, W, max_chunk_pixels, &plan)) {
-    set_error("stem_grad_workspace_size: B %d x %d x %d, max_chunk_pixels %d is outside the plan's range", B, H, W,
-              max_chunk_pixels);
-    return 0;
-  }
+  if (!stem_grad_plan(B, H, W, max_chunk_pixels, &plan))
+    return refused("stem_grad_workspace_size: B %d x %d x %d, max_chunk_pixels %d is outside the plan's range", B, H, W,
+                   max_chunk_pixels);
   return plan.total;
 }
 
@@ -102,11 +97,9 @@ extern "C" int sfa_model_stem_grad_chunk_pixels(const sfa_model* model, int B, i
   StemLevel sl;
   StemGradPlan plan;
   if (stem_level("stem_grad_chunk_pixels", model, &sl) != SFA_OK) return 0;
-  if (!stem_grad_plan(B, H, W, max_chunk_pixels, &plan)) {
-    set_error("stem_grad_chunk_pixels: B %d x %d x %d, max_chunk_pixels %d is outside the plan's range", B, H, W,
-              max_chunk_pixels);
-    return 0;
-  }
+  if (!stem_grad_plan(B, H, W, max_chunk_pixels, &plan))
+    return refused("stem_grad_chunk_pixels: B %d x %d x %d, max_chunk_pixels %d is outside the plan's range", B, H, W,
+                   max_chunk_pixels);
   return plan.wg.Kc;
 }
 
@@ -130,8 +123,7 @@ extern "C" int sfa_model_stem_grad(const sfa_model* model, const float* x, const
   SFA_CHECK_ARG(a && gp && workspace, "stem_grad: null a, gp or workspace");
   SFA_CHECK_ARG(grad_x || dW || db, "stem_grad: no output wanted");
   SFA_CHECK_ARG(x || !dW, "stem_grad: dW' reads x");
-  const void* all[] = {x, a, gp, grad_x, dW, db, workspace};
-  for (const void* p : all) SFA_CHECK_ARG(aligned16(p), "stem_grad: every buffer must be 16-byte aligned");
+  SFA_CHECK_ARG(all_aligned16({x, a, gp, grad_x, dW, db, workspace}), "stem_grad: every buffer must be 16-byte aligned");
   SFA_CHECK_ARG(workspace_bytes >= plan.total, "stem_grad: workspace of %zu bytes, %zu needed", workspace_bytes,
                 plan.total);
   const StemShape& s = plan.s;
@@ -145,12 +137,12 @@ extern "C" int sfa_model_stem_grad(const sfa_model* model, const float* x, const
                       s.ow, s.ph, s.pw, s.npix_a))
     return rc;
   if (db)
-    if (int rc = launch_block_bias_grad(plan.bs, dA, nullptr, bpart, db, st)) return rc;
+    if (int rc = launch_bias_grad(plan.bs, dA, nullptr, bpart, db, st)) return rc;
   if (dW) {
     if (int rc = launch({dim3((unsigned)plan.wg.chunks, (unsigned)kSgColTiles), dim3(256), st}, stem_wgrad_kernel, dA, x,
                         part, H, W, s.oh, s.ow, s.npix_a, plan.wg.Kc))
       return rc;
-    if (int rc = launch_block_wgrad_fold(plan.wg, part, dW, st)) return rc;
+    if (int rc = launch_wgrad_fold(part, plan.wg.chunks, kSgC, kSgK, 1, dW, kSgK, 0, st)) return rc;
   }
   if (!grad_x) return SFA_OK;
   const int passes = ceil_div(s.npix_x, kSgDgradPixels);

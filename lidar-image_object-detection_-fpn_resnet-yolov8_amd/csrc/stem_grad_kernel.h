@@ -4,20 +4,20 @@
 //                        at the (at most 4) windows that hold it and takes a window's gp exactly when it is that
 //                        window's first maximum in row-major scan order (strict > before it, >= after it: torch's
 //                        rule; padding never wins because it is never read).  Every element stored once by one lane.
-//   stem_wgrad_kernel    dW' on v_mfma_f32_32x32x2_f32 with block_tile.h's 64 x 64 tile: rows = the 64 output
+//   stem_wgrad_kernel    dW' on v_mfma_f32_32x32x2_f32 with grad_tile.h's 64 x 64 tile: rows = the 64 output
 //                        channels, columns = 64 of the 147 (c, ky, kx) entries padded to 192, K = the conv output
 //                        pixels of one split-K chunk.  dA rows as they lie; the x operand gathered from the NCHW
 //                        image, every row and column tested against H and W.  float32 partial tile per chunk
-//                        [chunk][64][147]; block_wgrad_fold_kernel adds the chunks (block.hip).
+//                        [chunk][64][147]; grad_wgrad_fold_kernel adds the chunks (grad_common.hip).
 //   stem_dgrad_kernel    dx as a vector gather: one image pixel per thread, the taps whose parity matches
 //                        (ky = iy + 3 mod 2, likewise kx; stem_tap_source) in (ky, kx) order, the 64 channels in
 //                        channel order, three float64 accumulators (one per input plane) from exact float32
 //                        products, rounded once.  W' [tap][o] as float4 (c0, c1, c2, 0) in LDS: the handle's
 //                        packed row order.
-// db' is block_bias_kernel on dA (block.hip).  No atomics; every sum has a fixed order, so runs are bit-identical.
+// db' is grad_bias_kernel on dA (grad_common.hip).  No atomics; every sum has a fixed order, so runs are bit-identical.
 #pragma once
 
-#include "block_tile.h"
+#include "grad_tile.h"
 #include "stem_grad_plan.h"
 
 namespace sfa {
@@ -31,8 +31,8 @@ __global__ void __launch_bounds__(256) stem_pool_adjoint_kernel(const float* __r
   if (p >= npix) return;
   const int x = p % ow, t = p / ow;
   const int y = t % oh, b = t / oh;
-  const bk_f32x4 me = *reinterpret_cast<const bk_f32x4*>(a + (size_t)p * kSgC + q);
-  bk_f32x4 out = bk_zero4();
+  const grad_f32x4 me = *reinterpret_cast<const grad_f32x4*>(a + (size_t)p * kSgC + q);
+  grad_f32x4 out = grad_zero4();
   if (me.x > 0.f || me.y > 0.f || me.z > 0.f || me.w > 0.f) {
     const int wy0 = stem_pool_first_window(y), ny = stem_pool_windows(y, ph);
     const int wx0 = stem_pool_first_window(x), nx = stem_pool_windows(x, pw);
@@ -48,8 +48,8 @@ __global__ void __launch_bounds__(256) stem_pool_adjoint_kernel(const float* __r
           for (int dx = 0; dx < 3; ++dx) {
             const int ix = 2 * wx - 1 + dx;
             if ((unsigned)ix >= (unsigned)ow || (iy == y && ix == x)) continue;
-            const bk_f32x4 v =
-                *reinterpret_cast<const bk_f32x4*>(a + ((size_t)(b * oh + iy) * ow + ix) * kSgC + q);
+            const grad_f32x4 v =
+                *reinterpret_cast<const grad_f32x4*>(a + ((size_t)(b * oh + iy) * ow + ix) * kSgC + q);
             // scanned before this pixel: it must be strictly smaller; after it: not larger
             const bool before = iy < y || (iy == y && ix < x);
             w0 &= (int)(before ? v.x < me.x : v.x <= me.x);
@@ -58,13 +58,13 @@ __global__ void __launch_bounds__(256) stem_pool_adjoint_kernel(const float* __r
             w3 &= (int)(before ? v.w < me.w : v.w <= me.w);
           }
         }
-        const bk_f32x4 g = *reinterpret_cast<const bk_f32x4*>(gp + ((size_t)(b * ph + wy) * pw + wx) * kSgC + q);
+        const grad_f32x4 g = *reinterpret_cast<const grad_f32x4*>(gp + ((size_t)(b * ph + wy) * pw + wx) * kSgC + q);
         out.x = out.x + (w0 ? g.x : 0.f), out.y = out.y + (w1 ? g.y : 0.f);
         out.z = out.z + (w2 ? g.z : 0.f), out.w = out.w + (w3 ? g.w : 0.f);
       }
-    out = bk_masked(out, me);
+    out = grad_masked(out, me);
   }
-  *reinterpret_cast<bk_f32x4*>(dA + (size_t)p * kSgC + q) = out;
+  *reinterpret_cast<grad_f32x4*>(dA + (size_t)p * kSgC + q) = out;
 }
 
 // part[chunk][o][j] = sum over the chunk's conv output pixels p of dA[p][o] x[b][c][2 oy - 3 + ky][2 ox - 3 + kx],
@@ -72,11 +72,11 @@ __global__ void __launch_bounds__(256) stem_pool_adjoint_kernel(const float* __r
 __global__ void __launch_bounds__(256) stem_wgrad_kernel(const float* __restrict__ dA, const float* __restrict__ x,
                                                          float* __restrict__ part, int H, int W, int oh, int ow, int npix,
                                                          int Kc) {
-  __shared__ __attribute__((aligned(16))) float sA[kBkLdsWords];
-  __shared__ __attribute__((aligned(16))) float sB[kBkLdsWords];
-  BK_LANE_IDS;
-  const BlockRange ck = block_chunk_at((int)blockIdx.x, npix, Kc);
-  const int j0 = (int)blockIdx.y * kBkTile;
+  __shared__ __attribute__((aligned(16))) float sA[kGradLdsWords];
+  __shared__ __attribute__((aligned(16))) float sB[kGradLdsWords];
+  GRAD_LANE_IDS;
+  const GradRange ck = grad_chunk_at((int)blockIdx.x, npix, Kc);
+  const int j0 = (int)blockIdx.y * kGradTile;
   const int kk = tid >> 4, q4 = (tid & 15) * 4;  // this thread's k row (pixel of the step) and column quad
   // this thread's four columns: plane offset and tap of each (a column past 146 reads nothing)
   int cpl[4], cky[4], ckx[4];
@@ -87,12 +87,12 @@ __global__ void __launch_bounds__(256) stem_wgrad_kernel(const float* __restrict
     if (j < kSgK) stem_column(j, &c, &ky, &kx);
     cpl[e] = j < kSgK ? c : -1, cky[e] = ky, ckx[e] = kx;
   }
-  auto load_g = [&](int k) -> bk_f32x4 {
-    if (k + kk >= ck.count) return bk_zero4();  // a short last step pairs with zero rows
-    return *reinterpret_cast<const bk_f32x4*>(dA + (size_t)(ck.first + k + kk) * kSgC + q4);
+  auto load_g = [&](int k) -> grad_f32x4 {
+    if (k + kk >= ck.count) return grad_zero4();  // a short last step pairs with zero rows
+    return *reinterpret_cast<const grad_f32x4*>(dA + (size_t)(ck.first + k + kk) * kSgC + q4);
   };
-  auto load_x = [&](int k) -> bk_f32x4 {
-    bk_f32x4 v = bk_zero4();
+  auto load_x = [&](int k) -> grad_f32x4 {
+    grad_f32x4 v = grad_zero4();
     if (k + kk >= ck.count) return v;
     const int p = ck.first + k + kk;
     const int ox = p % ow, q = p / ow;
@@ -105,26 +105,26 @@ __global__ void __launch_bounds__(256) stem_wgrad_kernel(const float* __restrict
     }
     return v;
   };
-  bk_f32x16 acc;
+  grad_f32x16 acc;
 #pragma unroll
   for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-  bk_f32x4 ra = load_g(0), rb = load_x(0);
-  for (int k = 0; k < ck.count; k += kBkStep) {
+  grad_f32x4 ra = load_g(0), rb = load_x(0);
+  for (int k = 0; k < ck.count; k += kGradStep) {
     __syncthreads();
-    bk_store_mc(sA, ra, tid);
-    bk_store_mc(sB, rb, tid);
+    grad_store_mc(sA, ra, tid);
+    grad_store_mc(sB, rb, tid);
     __syncthreads();
-    if (k + kBkStep < ck.count) {
-      ra = load_g(k + kBkStep);
-      rb = load_x(k + kBkStep);
+    if (k + kGradStep < ck.count) {
+      ra = load_g(k + kGradStep);
+      rb = load_x(k + kGradStep);
     }
-    bk_mma(sA, sB, wm, wn, r, hh, acc);
+    grad_mma(sA, sB, wm, wn, r, hh, acc);
   }
   float* P = part + (size_t)blockIdx.x * kSgC * kSgK;
   const int col = j0 + wn * 32 + r;
   if (col < kSgK) {
 #pragma unroll
-    for (int v = 0; v < 16; ++v) P[(size_t)(wm * 32 + bk_acc_row(v, hh)) * kSgK + col] = acc[v];
+    for (int v = 0; v < 16; ++v) P[(size_t)(wm * 32 + grad_acc_row(v, hh)) * kSgK + col] = acc[v];
   }
 }
 
@@ -136,7 +136,7 @@ __global__ void __launch_bounds__(256) stem_dgrad_kernel(const float* __restrict
   __shared__ __attribute__((aligned(16))) float sW[49 * kSgC * 4];  // [tap][o] float4
   for (int i = (int)threadIdx.x; i < 49 * kSgC; i += 256) {
     const int tap = i / kSgC, o = i - tap * kSgC;
-    *reinterpret_cast<bk_f32x4*>(sW + (size_t)i * 4) = *reinterpret_cast<const bk_f32x4*>(Wp + (size_t)o * ldw + tap * 4);
+    *reinterpret_cast<grad_f32x4*>(sW + (size_t)i * 4) = *reinterpret_cast<const grad_f32x4*>(Wp + (size_t)o * ldw + tap * 4);
   }
   __syncthreads();
   const int passes = (npix + kSgDgradPixels - 1) / kSgDgradPixels;
@@ -156,10 +156,10 @@ __global__ void __launch_bounds__(256) stem_dgrad_kernel(const float* __restrict
         const float* w = sW + (size_t)(ky * 7 + kx) * kSgC * 4;
 #pragma unroll 4
         for (int o4 = 0; o4 < kSgC; o4 += 4) {
-          const bk_f32x4 gv = *reinterpret_cast<const bk_f32x4*>(g + o4);
+          const grad_f32x4 gv = *reinterpret_cast<const grad_f32x4*>(g + o4);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const bk_f32x4 wv = *reinterpret_cast<const bk_f32x4*>(w + (size_t)(o4 + e) * 4);
+            const grad_f32x4 wv = *reinterpret_cast<const grad_f32x4*>(w + (size_t)(o4 + e) * 4);
             const double gd = (double)gv[e];
             s0 = fma(gd, (double)wv.x, s0);
             s1 = fma(gd, (double)wv.y, s1);
@@ -174,5 +174,7 @@ __global__ void __launch_bounds__(256) stem_dgrad_kernel(const float* __restrict
     dx[at + 2 * plane] = (float)s2;
   }
 }
+
+#undef GRAD_LANE_IDS
 
 }  // namespace sfa

@@ -17,8 +17,7 @@ namespace sfa {
 
 constexpr int kSgC = 64;              // the stem's output channels
 constexpr int kSgK = 147;             // 3 x 7 x 7: the columns of dW' in torch's (c, ky, kx) order
-constexpr int kSgColTiles = 3;        // 147 columns padded to 3 tiles of kBkTile
-constexpr int kSgChunkPixels = 2048;  // the plan's own split-K chunk (max_chunk_pixels == 0), in conv output pixels
+constexpr int kSgColTiles = 3;        // 147 columns padded to 3 tiles of kGradTile
 constexpr int kSgMaxSide = 32760;     // the forward's conv launch packs input rows and columns in 16 bits
 constexpr int kSgMaxBatch = 65535;    // the forward's layout and max-pool launches put the frame on a grid axis
 constexpr int kSgDgradPixels = 256;   // image pixels of one stem_dgrad_kernel pass (one per thread)
@@ -38,7 +37,7 @@ struct StemForwardPlan {
 struct StemGradPlan {
   StemShape s;
   BlockWgrad wg;  // dW': rows 64, cin 147, taps 1 (the fold's (M, cin, ntaps) = torch's (64, 3 x 7 x 7))
-  BlockBias bs;   // db'
+  GradBias bs;    // db'
   // bytes: dA (npix_a x 64), the float32 split-K partials [chunk][64][147], the float64 bias partials
   size_t off_da, off_part, off_bpart, total;
 };
@@ -59,43 +58,26 @@ inline bool stem_shape(int B, int H, int W, StemShape* s) {
 
 inline bool stem_forward_plan(int B, int H, int W, StemForwardPlan* p) {
   if (!stem_shape(B, H, W, &p->s)) return false;
-  size_t cur = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = cur;
-    cur = bk_align_up(cur + bytes);
-    return o;
-  };
-  p->off_xin = take((size_t)p->s.npix_x * 16);
+  GradRegions ws;
+  p->off_xin = ws.take((size_t)p->s.npix_x * 16);
   p->amax_bytes = (size_t)B * SFA_AMAX_WORDS * 4;
-  p->off_amax = take(p->amax_bytes);
-  p->total = cur;
+  p->off_amax = ws.take(p->amax_bytes);
+  p->total = ws.cur;
   return true;
 }
 
 inline bool stem_grad_plan(int B, int H, int W, int max_chunk_pixels, StemGradPlan* p) {
   if (max_chunk_pixels < 0 || !stem_shape(B, H, W, &p->s)) return false;
   const StemShape& s = p->s;
-  const int cap = max_chunk_pixels > 0 ? max_chunk_pixels : kSgChunkPixels;
   BlockWgrad& g = p->wg;
-  g.rows = kSgC, g.cin = kSgK, g.taps = 1, g.npix = s.npix_a;
-  g.Kc = g.npix < cap ? g.npix : cap;
-  g.chunks = (g.npix + g.Kc - 1) / g.Kc;
-  BlockBias& b = p->bs;
-  b.npix = s.npix_a, b.cout = kSgC;
-  int px = (b.npix + kBkBiasMaxBlocks - 1) / kBkBiasMaxBlocks;
-  if (px < kBkBiasMinPixels) px = kBkBiasMinPixels;
-  b.pixels = px;
-  b.blocks = (b.npix + px - 1) / px;
-  size_t cur = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = cur;
-    cur = bk_align_up(cur + bytes);
-    return o;
-  };
-  p->off_da = take((size_t)s.npix_a * kSgC * 4);
-  p->off_part = take((size_t)g.chunks * kSgC * kSgK * 4);
-  p->off_bpart = take((size_t)b.blocks * kSgC * 8);
-  p->total = cur;
+  static_cast<GradSplitK&>(g) = grad_split_k(s.npix_a, max_chunk_pixels);
+  g.rows = kSgC, g.cin = kSgK, g.taps = 1;
+  p->bs = grad_bias(s.npix_a, kSgC);
+  GradRegions ws;
+  p->off_da = ws.take((size_t)s.npix_a * kSgC * 4);
+  p->off_part = ws.take((size_t)g.chunks * kSgC * kSgK * 4);
+  p->off_bpart = ws.take(grad_bias_bytes(p->bs));
+  p->total = ws.cur;
   return true;
 }
 
@@ -103,12 +85,12 @@ inline bool stem_grad_plan(int B, int H, int W, int max_chunk_pixels, StemGradPl
 
 // The pool windows that hold conv-map index i (0 <= i < n; pn = ceil(n / 2) windows of 3 / stride 2 / pad 1, window
 // v covering 2 v - 1 .. 2 v + 1): always v = i / 2, and at an odd i also i / 2 + 1 when that window exists.
-SFA_BK_HD inline int stem_pool_first_window(int i) { return i >> 1; }
-SFA_BK_HD inline int stem_pool_windows(int i, int pn) { return ((i & 1) && (i >> 1) + 1 < pn) ? 2 : 1; }
+SFA_GRAD_HD inline int stem_pool_first_window(int i) { return i >> 1; }
+SFA_GRAD_HD inline int stem_pool_windows(int i, int pn) { return ((i & 1) && (i >> 1) + 1 < pn) ? 2 : 1; }
 
 // The conv output index that image index i reaches through tap k of the 7-tap / pad 3 / stride 2 window:
 // i = 2 o - 3 + k.  -1: none (wrong parity, or outside 0 .. on - 1).
-SFA_BK_HD inline int stem_tap_source(int i, int k, int on) {
+SFA_GRAD_HD inline int stem_tap_source(int i, int k, int on) {
   const int t = i + 3 - k;
   if (t < 0 || (t & 1)) return -1;
   const int o = t >> 1;
@@ -116,10 +98,10 @@ SFA_BK_HD inline int stem_tap_source(int i, int k, int on) {
 }
 
 // The first tap of matching parity at image index i: the taps that can reach it are k0, k0 + 2, .. <= 6.
-SFA_BK_HD inline int stem_first_tap(int i) { return (i + 3) & 1; }
+SFA_GRAD_HD inline int stem_first_tap(int i) { return (i + 3) & 1; }
 
 // Column j of dW' (0 .. kSgK - 1, torch's order): input plane c and taps (ky, kx).
-SFA_BK_HD inline void stem_column(int j, int* c, int* ky, int* kx) {
+SFA_GRAD_HD inline void stem_column(int j, int* c, int* ky, int* kx) {
   *c = j / 49;
   const int r = j - *c * 49;
   *ky = r / 7;

@@ -326,17 +326,12 @@ class KfpnEngine:
                    for n, sh in zip(names, shapes)]
         hid = [torch.empty((B, h, w, 64 * len(names)), dtype=torch.float32, device=x.device) for _ in range(2)] \
             if want_hidden else None
-        need = self.heads_grad_workspace_bytes(level, B, h, w, max_chunk_pixels)
-        if need == 0:
-            msg = lib().sfa_last_error_string()
-            raise ValueError(f"heads_param_grad: B={B}, h={h}, w={w}, max_chunk_pixels={max_chunk_pixels} refused: "
-                             f"{msg.decode() if msg else ''}")
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        workspace = _workspace("heads_param_grad", f"B={B}, h={h}, w={w}, max_chunk_pixels={max_chunk_pixels}",
+                               self.heads_grad_workspace_bytes(level, B, h, w, max_chunk_pixels), workspace, x.device)
         with torch.cuda.device(x.device):
             check(lib().sfa_model_heads_grad(self._h, level, x.data_ptr(), B, h, w, _ptr_array(gs),
                                              *(_ptr_array([r[k] for r in res]) for k in range(4)),
-                                             hid[0].data_ptr() if hid else None, hid[1].data_ptr() if hid else None,
+                                             *(_opt_ptr(t) for t in hid or (None, None)),
                                              int(max_chunk_pixels), workspace.data_ptr(), workspace.numel(),
                                              _lib.stream_ptr(x.device)), "sfa_model_heads_grad")
         grads = {n: tuple(r) for n, r in zip(names, res)}
@@ -365,15 +360,11 @@ class KfpnEngine:
         names = [n for n, _ in self.heads]
         ys = _kfpn_buffers(out, names, [(B, c, h, w) for _, c in self.heads], x, "heads_forward out")
         hid = torch.empty((B, h, w, 64 * len(names)), dtype=torch.float32, device=x.device) if want_hidden else None
-        need = self.heads_forward_workspace_bytes(level, B, h, w)
-        if need == 0:
-            msg = lib().sfa_last_error_string()
-            raise ValueError(f"heads_forward: B={B}, h={h}, w={w} refused: {msg.decode() if msg else ''}")
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        workspace = _workspace("heads_forward", f"B={B}, h={h}, w={w}",
+                               self.heads_forward_workspace_bytes(level, B, h, w), workspace, x.device)
         with torch.cuda.device(x.device):
             check(lib().sfa_model_heads_forward(self._h, level, x.data_ptr(), B, h, w, _ptr_array(ys),
-                                                hid.data_ptr() if want_hidden else None, workspace.data_ptr(),
+                                                _opt_ptr(hid), workspace.data_ptr(),
                                                 workspace.numel(), _lib.stream_ptr(x.device)), "sfa_model_heads_forward")
         res = dict(zip(names, ys))
         return (res, hid) if want_hidden else res
@@ -393,11 +384,10 @@ class KfpnEngine:
         return gx
 
     # ------------------------------------------------ the FPN neck as an operator (four backbone maps in)
-    def _neck_refused(self, what, B, h4, w4):
+    def _neck_workspace(self, what, B, h4, w4, need, workspace, device):
         if self.deconv:
             raise ValueError(f"{what}: a resnet_18 model has no FPN neck")
-        msg = lib().sfa_last_error_string()
-        raise ValueError(f"{what}: B={B}, h4={h4}, w4={w4} refused: {msg.decode() if msg else ''}")
+        return _workspace(what, f"B={B}, h4={h4}, w4={w4}", need, workspace, device)
 
     @staticmethod
     def _neck_shapes(B, h4, w4):
@@ -443,11 +433,8 @@ class KfpnEngine:
         sh = self._neck_shapes(B, h4, w4)
         ls = self._neck_maps("neck_forward", (l1, l2, l3, l4), ("l1", "l2", "l3", "l4"), sh[:4])
         us = _kfpn_buffers(None if out is None else dict(enumerate(out)), range(3), sh[4:], l4, "neck_forward out")
-        need = self.neck_forward_workspace_bytes(B, h4, w4)
-        if need == 0:
-            self._neck_refused("neck_forward", B, h4, w4)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=l4.device)
+        workspace = self._neck_workspace("neck_forward", B, h4, w4, self.neck_forward_workspace_bytes(B, h4, w4), workspace,
+                                         l4.device)
         with torch.cuda.device(l4.device):
             check(lib().sfa_model_neck_forward(self._h, *(t.data_ptr() for t in ls), B, h4, w4,
                                                *(t.data_ptr() for t in us), workspace.data_ptr(), workspace.numel(),
@@ -473,25 +460,12 @@ class KfpnEngine:
         us = self._neck_maps("neck_grad", ups or (None,) * 2, ("u2", "u3"), sh[4:6], optional=True)
         want = list(want_layers) + list(want_params)
         shapes = sh[:4] + list(_lib.NECK_PARAM_SHAPES)
-        given = (list(out[0]) + list(out[1])) if out is not None else [None] * 10
-        res = []
-        for k, (wnt, s) in enumerate(zip(want, shapes)):
-            if not wnt:
-                res.append(None)
-            elif given[k] is None:
-                res.append(torch.empty(s, dtype=torch.float32, device=g4.device))
-            else:
-                res.append(_kfpn_buffers({0: given[k]}, [0], [s], g4, f"neck_grad out[{k}]")[0])
-        need = self.neck_grad_workspace_bytes(B, h4, w4, max_chunk_pixels)
-        if need == 0:
-            self._neck_refused("neck_grad", B, h4, w4)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=g4.device)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        dparams = (ctypes.c_void_p * 6)(*[ptr(t) for t in res[4:]]) if any(t is not None for t in res[4:]) else None
+        res = _grad_outputs("neck_grad", want, shapes, out and (list(out[0]) + list(out[1])), g4)
+        workspace = self._neck_workspace("neck_grad", B, h4, w4, self.neck_grad_workspace_bytes(B, h4, w4, max_chunk_pixels),
+                                         workspace, g4.device)
         with torch.cuda.device(g4.device):
-            check(lib().sfa_model_neck_grad(self._h, *(ptr(t) for t in ls), *(ptr(t) for t in us),
-                                            *(ptr(t) for t in gs), B, h4, w4, *(ptr(t) for t in res[:4]), dparams,
+            check(lib().sfa_model_neck_grad(self._h, *(_opt_ptr(t) for t in ls + us + gs), B, h4, w4,
+                                            *(_opt_ptr(t) for t in res[:4]), _dparams(res[4:]),
                                             int(max_chunk_pixels), workspace.data_ptr(), workspace.numel(),
                                             _lib.stream_ptr(g4.device)), "sfa_model_neck_grad")
         return res[:4], res[4:]
@@ -516,10 +490,6 @@ class KfpnEngine:
         B, h, w, _ = (int(v) for v in x.shape)
         return x, B, h, w, cin, cout, s, ds, (B, -(-h // s), -(-w // s), cout)
 
-    def _block_refused(self, what, B, h, w):
-        msg = lib().sfa_last_error_string()
-        raise ValueError(f"{what}: B={B}, h={h}, w={w} refused: {msg.decode() if msg else ''}")
-
     def block_forward_workspace_bytes(self, layer, block, B, h, w) -> int:
         return 0 if self.deconv else int(lib().sfa_model_block_forward_workspace_size(self._h, layer, block, B, h, w))
 
@@ -541,11 +511,8 @@ class KfpnEngine:
         launches (graph-capturable)."""
         x, B, h, w, _, _, _, _, osh = self._block_dims("block_forward", layer, block, x)
         mid, y = _kfpn_buffers(None if out is None else dict(enumerate(out)), range(2), [osh, osh], x, "block_forward out")
-        need = self.block_forward_workspace_bytes(layer, block, B, h, w)
-        if need == 0:
-            self._block_refused("block_forward", B, h, w)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        workspace = _workspace("block_forward", f"B={B}, h={h}, w={w}",
+                               self.block_forward_workspace_bytes(layer, block, B, h, w), workspace, x.device)
         with torch.cuda.device(x.device):
             check(lib().sfa_model_block_forward(self._h, layer, block, x.data_ptr(), B, h, w, mid.data_ptr(), y.data_ptr(),
                                                 workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(x.device)),
@@ -570,26 +537,14 @@ class KfpnEngine:
         want = [bool(want_x)] + [bool(v) for v in want_params]
         want[5] = want[5] and ds
         shapes = [(B, h, w, cin), (cout, cin, 3, 3), (cout,), (cout, cout, 3, 3), (cout,), (cout, cin, 1, 1)]
-        given = ([out[0]] + list(out[1])) if out is not None else [None] * 6
-        res = []
-        for k, (wnt, s) in enumerate(zip(want, shapes)):
-            if not wnt:
-                res.append(None)
-            elif given[k] is None:
-                res.append(torch.empty(s, dtype=torch.float32, device=x.device))
-            else:
-                res.append(_kfpn_buffers({0: given[k]}, [0], [s], x, f"block_grad out[{k}]")[0])
-        need = self.block_grad_workspace_bytes(layer, block, B, h, w, max_chunk_pixels)
-        if need == 0:
-            self._block_refused("block_grad", B, h, w)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        dparams = (ctypes.c_void_p * 5)(*[ptr(t) for t in res[1:]]) if any(t is not None for t in res[1:]) else None
+        res = _grad_outputs("block_grad", want, shapes, out and ([out[0]] + list(out[1])), x)
+        workspace = _workspace("block_grad", f"B={B}, h={h}, w={w}",
+                               self.block_grad_workspace_bytes(layer, block, B, h, w, max_chunk_pixels), workspace, x.device)
         with torch.cuda.device(x.device):
             check(lib().sfa_model_block_grad(self._h, layer, block, x.data_ptr(), *(t.data_ptr() for t in maps), B, h, w,
-                                             ptr(res[0]), dparams, int(max_chunk_pixels), workspace.data_ptr(),
-                                             workspace.numel(), _lib.stream_ptr(x.device)), "sfa_model_block_grad")
+                                             _opt_ptr(res[0]), _dparams(res[1:]), int(max_chunk_pixels),
+                                             workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(x.device)),
+                  "sfa_model_block_grad")
         return res[0], res[1:]
 
     # ------------------------------------------------ the stem as an operator (a caller's image in)
@@ -605,10 +560,6 @@ class KfpnEngine:
             raise ValueError(f"{what} x: {tuple(x.shape)} is not the NCHW (B, 3, H, W)")
         B, _, H, W = (int(v) for v in x.shape)
         return x, B, H, W
-
-    def _stem_refused(self, what, B, H, W):
-        msg = lib().sfa_last_error_string()
-        raise ValueError(f"{what}: B={B}, H={H}, W={W} refused: {msg.decode() if msg else ''}")
 
     def stem_forward_workspace_bytes(self, B, H, W) -> int:
         return int(lib().sfa_model_stem_forward_workspace_size(self._h, B, H, W))
@@ -630,11 +581,8 @@ class KfpnEngine:
         x, B, H, W = self._stem_dims("stem_forward", x)
         a, pooled = _kfpn_buffers(None if out is None else dict(enumerate(out)), range(2), self.stem_shapes(B, H, W), x,
                                   "stem_forward out")
-        need = self.stem_forward_workspace_bytes(B, H, W)
-        if need == 0:
-            self._stem_refused("stem_forward", B, H, W)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        workspace = _workspace("stem_forward", f"B={B}, H={H}, W={W}", self.stem_forward_workspace_bytes(B, H, W), workspace,
+                               x.device)
         with torch.cuda.device(x.device):
             check(lib().sfa_model_stem_forward(self._h, x.data_ptr(), B, H, W, a.data_ptr(), pooled.data_ptr(),
                                                workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(x.device)),
@@ -658,26 +606,13 @@ class KfpnEngine:
             maps.append(t)
         want = [bool(want_x)] + [bool(v) for v in want_params]
         shapes = [(B, 3, H, W), (64, 3, 7, 7), (64,)]
-        given = ([out[0]] + list(out[1])) if out is not None else [None] * 3
-        res = []
-        for k, (wnt, s) in enumerate(zip(want, shapes)):
-            if not wnt:
-                res.append(None)
-            elif given[k] is None:
-                res.append(torch.empty(s, dtype=torch.float32, device=x.device))
-            else:
-                res.append(_kfpn_buffers({0: given[k]}, [0], [s], x, f"stem_grad out[{k}]")[0])
-        need = self.stem_grad_workspace_bytes(B, H, W, max_chunk_pixels)
-        if need == 0:
-            self._stem_refused("stem_grad", B, H, W)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        dparams = (ctypes.c_void_p * 2)(*[ptr(t) for t in res[1:]]) if any(t is not None for t in res[1:]) else None
+        res = _grad_outputs("stem_grad", want, shapes, out and ([out[0]] + list(out[1])), x)
+        workspace = _workspace("stem_grad", f"B={B}, H={H}, W={W}", self.stem_grad_workspace_bytes(B, H, W, max_chunk_pixels),
+                               workspace, x.device)
         with torch.cuda.device(x.device):
-            check(lib().sfa_model_stem_grad(self._h, x.data_ptr(), *(t.data_ptr() for t in maps), B, H, W, ptr(res[0]),
-                                            dparams, int(max_chunk_pixels), workspace.data_ptr(), workspace.numel(),
-                                            _lib.stream_ptr(x.device)), "sfa_model_stem_grad")
+            check(lib().sfa_model_stem_grad(self._h, x.data_ptr(), *(t.data_ptr() for t in maps), B, H, W,
+                                            _opt_ptr(res[0]), _dparams(res[1:]), int(max_chunk_pixels), workspace.data_ptr(),
+                                            workspace.numel(), _lib.stream_ptr(x.device)), "sfa_model_stem_grad")
         return res[0], res[1:]
 
     def forward(self, x: torch.Tensor, in_layout: int = _lib.IN_NCHW3) -> dict:
@@ -1786,6 +1721,26 @@ def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+def _opt_ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _dparams(tensors):
+    """The ``dparams`` argument of a gradient entry: its pointers, null where not wanted; None when none is."""
+    if all(t is None for t in tensors):
+        return None
+    return (ctypes.c_void_p * len(tensors))(*[_opt_ptr(t) for t in tensors])
+
+
+def _workspace(what, dims, need, workspace, device):
+    """The workspace of an operator call: the caller's, or a fresh one of ``need`` bytes.  ``need`` == 0 is the size
+    query's refusal of ``dims``: ValueError with the library's text."""
+    if need == 0:
+        msg = lib().sfa_last_error_string()
+        raise ValueError(f"{what}: {dims} refused: {msg.decode() if msg else ''}")
+    return workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=device)
+
+
 def bn_unfold_grad(weight, gamma, mean, var, eps, dWf, dbf, want=(True, True, True)):
     """The gradients of a convolution weight and of the BatchNorm after it from the gradients ``dWf``, ``dbf`` of their
     folded form W' = s W, b' = beta - mean s, s = gamma / sqrt(var + eps) (sfa_bn_unfold_grad; float64 from the
@@ -1806,10 +1761,9 @@ def bn_unfold_grad(weight, gamma, mean, var, eps, dWf, dbf, want=(True, True, Tr
     dW = torch.empty_like(weight) if want[0] else None
     dg = torch.empty_like(gamma) if want[1] else None
     dbt = torch.empty_like(gamma) if want[2] else None
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with torch.cuda.device(weight.device):
         check(lib().sfa_bn_unfold_grad(weight.data_ptr(), gamma.data_ptr(), mean.data_ptr(), var.data_ptr(), float(eps),
-                                       dWf.data_ptr(), dbf.data_ptr(), cout, K, ptr(dW), ptr(dg), ptr(dbt),
+                                       dWf.data_ptr(), dbf.data_ptr(), cout, K, _opt_ptr(dW), _opt_ptr(dg), _opt_ptr(dbt),
                                        _lib.stream_ptr(weight.device)), "sfa_bn_unfold_grad")
     return dW, dg, dbt
 
@@ -1852,6 +1806,20 @@ def _kfpn_buffers(given, names, shapes, like, what):
             raise ValueError(f"{what}[{name!r}]: a contiguous tensor of shape {tuple(s)} is needed")
         out.append(t)
     return out
+
+
+def _grad_outputs(what, want, shapes, given, like):
+    """The outputs of a gradient entry, in order: None where ``want`` is False, the caller's tensor where ``given``
+    (a list, or None) has one, else a fresh one."""
+    res = []
+    for k, (wnt, s) in enumerate(zip(want, shapes)):
+        if not wnt:
+            res.append(None)
+        elif not given or given[k] is None:
+            res.append(torch.empty(s, dtype=torch.float32, device=like.device))
+        else:
+            res.append(_kfpn_buffers({0: given[k]}, [0], [s], like, f"{what} out[{k}]")[0])
+    return res
 
 
 def kfpn_combine(levels_by_head: dict, level0_half: bool = False, return_weights: bool = False, out: dict = None,

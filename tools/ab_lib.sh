@@ -3,8 +3,9 @@
 #   cp <pkg>/sfa/sfa_hip/libsfa_hip.so tools/prev_lib/libsfa_hip_prev.so   # before the change, here
 #   <edit, build>                                                                  # then
 #   gpurun -- 'bash tools/ab_lib.sh TAG "KERNEL_REGEX" [stamps,hstamps,tests,bits,ab,prof]'
-# Parts (default all but stamps / hstamps): tests = the model + timed-config parity GPU tests; bits =
-# tools/ab_lib_bits.py over the full forward, previous vs new; ab = tools/ab_env.sh bench A/B (2 x 2
+# Parts (default all but stamps / hstamps / grads; "grads" is one more name for the list): tests = the model +
+# timed-config parity GPU tests; bits = tools/ab_lib_bits.py over the full forward, previous vs new; grads = the same over the forwards and gradients of the
+# neck, block and stem operators, written under $OUT (default bench_out/); ab = tools/ab_env.sh bench A/B (2 x 2
 # interleaved); prof = rocprofv3 kernel trace of the serial forward for both libraries, the lines of
 # KERNEL_REGEX and the per-stage times; stamps / hstamps = the s_memtime diagnostics of the strip /
 # heads kernels (tools/stampbench, tools/headstampbench: tools/build_stamps.sh regenerates the stamped copies from
@@ -39,6 +40,15 @@ if has bits; then
   python tools/ab_lib_bits.py compare gpurun_out/bits_prev_${TAG}.npz gpurun_out/bits_new_${TAG}.npz >> gpurun_out/${TAG}_bits.txt 2>&1
   tail -1 gpurun_out/${TAG}_bits.txt
   rm -f gpurun_out/bits_*_${TAG}.npz
+fi
+if has grads; then
+  OUT="${OUT:-bench_out}"
+  mkdir -p "$OUT"
+  SFA_HIP_LIB=$PREV timeout -k 10 200 python tools/ab_lib_bits.py grads $OUT/grads_prev_${TAG}.npz > $OUT/${TAG}_grads.txt 2>&1 || { echo "grads prev failed"; exit 1; }
+  timeout -k 10 200 python tools/ab_lib_bits.py grads $OUT/grads_new_${TAG}.npz >> $OUT/${TAG}_grads.txt 2>&1 || { echo "grads new failed"; exit 1; }
+  python tools/ab_lib_bits.py compare $OUT/grads_prev_${TAG}.npz $OUT/grads_new_${TAG}.npz >> $OUT/${TAG}_grads.txt 2>&1 || { echo "grads differ"; tail -30 $OUT/${TAG}_grads.txt; exit 1; }
+  tail -1 $OUT/${TAG}_grads.txt
+  rm -f $OUT/grads_*_${TAG}.npz
 fi
 if has ab; then
   bash tools/ab_env.sh SFA_HIP_LIB=$PREV,SFA_HIP_LIB=$NEW || exit 1

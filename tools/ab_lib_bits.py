@@ -1,6 +1,7 @@
 """Bit-comparison of two builds of libsfa_hip.so on the same forwards (round-4 prune check).
 
     SFA_HIP_LIB=<lib> [SFA_ABI_EXPECT=1] python tools/ab_lib_bits.py run out.npz
+    SFA_HIP_LIB=<lib> python tools/ab_lib_bits.py grads out.npz
     python tools/ab_lib_bits.py compare a.npz b.npz
 
 `run` packs the synthetic weights and saves every head map of the forward under each configuration of
@@ -8,8 +9,10 @@ CONFIGS below: every math mode, every kernel-choice option off, no side streams,
 three input layouts and the resnet_18 family, at sizes with more than one tile per map at every level;
 and fp16x3 / fp16 with default options at 608 x 608 with 10 frames, which covers every kernel path of the
 bench (r3 heads, strip convs, r3 body convs, FPN skip convs, split-K layer4, the patch stem). A
-configuration that the library lacks (an older build) is reported and left out. `compare` asserts that
-the two files hold the same maps, bit-identical."""
+configuration that the library lacks (an older build) is reported and left out. `grads` saves the forwards
+and every gradient of the neck, block and stem operators on seeded inputs at the cases of GRAD_CASES below,
+once with all outputs wanted and once with only the data gradient. `compare` asserts that the two files
+hold the same maps, bit-identical."""
 import os
 import sys
 
@@ -103,6 +106,64 @@ def run(out):
     print("saved", out, len(res))
 
 
+# The smallest cases at which the pieces the three operators share can go wrong.  neck (B, h4, w4, cap): a short last
+# chunk, a chunk that is no multiple of 16, one-pixel tiles, dW1 written in two column ranges.  block (layer, block, B,
+# h, w, cap): the identity skip; the stride-2 downsample at odd sizes with its one-tap fold; cout 512, whose bias grid
+# has a second axis of 2.  stem (B, H, W, cap).
+GRAD_CASES = {"neck": [(2, 2, 3, 7), (1, 1, 3, 3), (1, 1, 1, 0)],
+              "block": [(1, 0, 2, 5, 7, 17), (2, 0, 2, 5, 7, 7), (4, 1, 1, 3, 3, 0)],
+              "stem": [(2, 12, 20, 17), (1, 7, 9, 3)]}
+
+
+def grads(out):
+    import torch
+    from sfa_hip import _lib, runtime, synthetic
+    dev = torch.device("cuda", 0)
+    arch = _lib.make_arch(runtime.DEFAULT_HEADS)
+    sd = synthetic.synthetic_state_dict(_lib.state_layout(arch), 0)
+    eng = runtime.KfpnEngine(arch, runtime.pack_state_dict(sd, arch), dev)
+    gen = torch.Generator().manual_seed(7)
+    rnd = lambda shape: torch.randn(tuple(shape), generator=gen).to(dev)  # noqa: E731
+    res = {}
+
+    def keep(tag, names, tensors):
+        for n, t in zip(names, tensors):
+            if t is not None:
+                res[f"{tag}/{n}"] = t.cpu().numpy()
+
+    for B, h4, w4, cap in GRAD_CASES["neck"]:
+        tag = f"neck/{B}x{h4}x{w4}/cap{cap}"
+        sh = eng._neck_shapes(B, h4, w4)
+        ls = [rnd(s) for s in sh[:4]]
+        us = eng.neck_forward(*ls)
+        keep(tag, ("u2", "u3", "u4"), us)
+        gs = [rnd(s) for s in sh[4:]]
+        for part, wp in (("all", (True,) * 6), ("data", (False,) * 6)):
+            dl, dp = eng.neck_grad(*gs, layers=ls, ups=us[:2], want_params=wp, max_chunk_pixels=cap)
+            keep(f"{tag}/{part}", ("d_l1", "d_l2", "d_l3", "d_l4", "dW1", "db1", "dW2", "db2", "dW3", "db3"), dl + dp)
+    for layer, block, B, h, w, cap in GRAD_CASES["block"]:
+        tag = f"block/layer{layer}.{block}/{B}x{h}x{w}/cap{cap}"
+        x = rnd((B, h, w, eng.block_shape(layer, block)[0]))
+        mid, y = eng.block_forward(layer, block, x)
+        keep(tag, ("mid", "y"), (mid, y))
+        gy = rnd(y.shape)
+        for part, wp in (("all", (True,) * 5), ("data", (False,) * 5)):
+            dx, dp = eng.block_grad(layer, block, x, mid, y, gy, want_params=wp, max_chunk_pixels=cap)
+            keep(f"{tag}/{part}", ("dx", "dW1", "db1", "dW2", "db2", "dWd"), [dx] + dp)
+    for B, H, W, cap in GRAD_CASES["stem"]:
+        tag = f"stem/{B}x{H}x{W}/cap{cap}"
+        x = rnd((B, 3, H, W))
+        a, pooled = eng.stem_forward(x)
+        keep(tag, ("a", "pooled"), (a, pooled))
+        gp = rnd(pooled.shape)
+        for part, wp in (("all", (True, True)), ("data", (False, False))):
+            dx, dp = eng.stem_grad(x, a, gp, want_params=wp, max_chunk_pixels=cap)
+            keep(f"{tag}/{part}", ("dx", "dW", "db"), [dx] + dp)
+    torch.cuda.synchronize()
+    np.savez(out, **res)
+    print("saved", out, len(res))
+
+
 def compare(a, b):
     A, Bz = np.load(a), np.load(b)
     for k in sorted(set(A.files) ^ set(Bz.files)):
@@ -119,5 +180,7 @@ def compare(a, b):
 if __name__ == "__main__":
     if sys.argv[1] == "run":
         run(sys.argv[2])
+    elif sys.argv[1] == "grads":
+        grads(sys.argv[2])
     else:
         sys.exit(compare(sys.argv[2], sys.argv[3]))

@@ -6,47 +6,10 @@
 // are exactly the output pixels whose window holds it, and that the workspace regions of both entries are disjoint,
 // aligned and inside the reported size; then two plans worked by hand and the refused shapes.  Built with
 // -fsanitize=address,undefined by tests/test_block_plan.py.
-#include <cstdio>
-#include <vector>
-
 #include "../lidar-image_object-detection_-fpn_resnet-yolov8_amd/csrc/block_plan.h"
+#include "plan_check.h"
 
 using namespace sfa;
-
-static long bad = 0, plans = 0;
-#define EXPECT(cond, ...)            \
-  do {                               \
-    if (!(cond)) {                   \
-      if (bad++ < 20) {              \
-        std::printf("BAD: " __VA_ARGS__); \
-        std::printf("\n");           \
-      }                              \
-    }                                \
-  } while (0)
-
-// runs of `per` over n items: every item once, in order, none empty, only the last short
-static void check_runs(int n, int per, int count, bool tiles, const char* what) {
-  std::vector<int> seen((size_t)n, 0);
-  int next = 0;
-  for (int c = 0; c < count; ++c) {
-    const BlockRange r = tiles ? block_tile_at(c, n) : block_chunk_at(c, n, per);
-    EXPECT(r.first == next && r.count >= 1 && r.count <= per && r.first + r.count <= n, "%s: run %d is [%d, +%d) of %d", what,
-           c, r.first, r.count, n);
-    EXPECT(c == count - 1 || r.count == per, "%s: run %d of %d is short and not the last", what, c, count);
-    if (r.first < 0 || r.count < 0 || r.first + r.count > n) return;
-    for (int i = 0; i < r.count; ++i) seen[(size_t)r.first + i]++;
-    next = r.first + r.count;
-  }
-  for (int v : seen) EXPECT(v == 1, "%s: an item is covered %d times (n %d per %d)", what, v, n, per);
-}
-
-static void check_regions(const size_t* off, const size_t* len, int n, size_t total, const char* what) {
-  EXPECT(off[0] == 0, "%s: first region not at 0", what);
-  for (int i = 0; i < n; ++i) {
-    EXPECT(off[i] % kBkAlign == 0, "%s: region %d misaligned", what, i);
-    EXPECT(off[i] + len[i] <= (i + 1 < n ? off[i + 1] : total), "%s: region %d overlaps the next / the end", what, i);
-  }
-}
 
 // block_tap_source against the forward's own index arithmetic i = o s - 1 + k, along one axis
 static void check_taps(int n, int s, int on) {
@@ -74,23 +37,23 @@ static void check_plan(int layer, int block, int B, int h, int w, int mcp) {
   EXPECT(s.oh == (h + s.stride - 1) / s.stride && s.ow == (w + s.stride - 1) / s.stride, "output dims");
   EXPECT((s.oh - 1) * s.stride < h && (s.ow - 1) * s.stride < w, "the last output pixel's centre is outside the map");
   EXPECT(s.npix_in == B * h * w && s.npix_out == B * s.oh * s.ow && f.s.npix_out == s.npix_out, "pixel counts");
-  check_runs(s.npix_in, kBkTile, block_tiles(s.npix_in), true, "input pixel tiles");
-  check_runs(s.npix_out, kBkTile, block_tiles(s.npix_out), true, "output pixel tiles");
+  check_runs(s.npix_in, kGradTile, grad_tiles(s.npix_in), true, "input pixel tiles");
+  check_runs(s.npix_out, kGradTile, grad_tiles(s.npix_out), true, "output pixel tiles");
   check_taps(h, s.stride, s.oh);
   check_taps(w, s.stride, s.ow);
-  const int cap = mcp > 0 ? mcp : kBkChunkPixels;
+  const int cap = mcp > 0 ? mcp : kGradChunkPixels;
   size_t part = 0;
   for (int i = 0; i < 3; ++i) {
     const BlockWgrad& g = p.wg[i];
     EXPECT(g.rows == s.cout && g.cin == (i == 1 ? s.cout : s.cin) && g.taps == (i == 2 ? (ds ? 1 : 0) : 9), "wgrad %d dims", i);
     EXPECT(g.Kc >= 1 && g.Kc <= cap && g.Kc <= g.npix && g.npix == s.npix_out, "wgrad %d Kc %d", i, g.Kc);
     EXPECT(g.chunks == (g.npix + g.Kc - 1) / g.Kc, "wgrad %d chunks", i);
-    EXPECT(g.rows % kBkTile == 0 && g.cin % kBkTile == 0, "wgrad %d channel tiles", i);
+    EXPECT(g.rows % kGradTile == 0 && g.cin % kGradTile == 0, "wgrad %d channel tiles", i);
     check_runs(g.npix, g.Kc, g.chunks, false, "split-K chunks");
     const size_t bytes = (size_t)g.chunks * g.rows * g.taps * g.cin * 4;
     if (bytes > part) part = bytes;
   }
-  EXPECT(p.bs.npix == s.npix_out && p.bs.cout == s.cout && p.bs.pixels >= kBkBiasMinPixels && p.bs.blocks <= kBkBiasMaxBlocks,
+  EXPECT(p.bs.npix == s.npix_out && p.bs.cout == s.cout && p.bs.pixels >= kGradBiasMinPixels && p.bs.blocks <= kGradBiasMaxBlocks,
          "bias plan");
   check_runs(p.bs.npix, p.bs.pixels, p.bs.blocks, false, "bias blocks");
   const size_t goff[3] = {p.off_da, p.off_part, p.off_bpart};
@@ -126,7 +89,7 @@ int main() {
     EXPECT(p.bs.pixels == 64 && p.bs.blocks == 1, "hand plan 1 bias");
     EXPECT(p.off_da == 0 && p.off_part == 12288 && p.off_bpart == 12288 + 1179648 && p.total == 12288 + 1179648 + 1024,
            "hand plan 1 regions %zu %zu %zu", p.off_part, p.off_bpart, p.total);
-    EXPECT(block_tiles(70) == 2 && block_tile_at(1, 70).first == 64 && block_tile_at(1, 70).count == 6, "hand plan 1 tiles");
+    EXPECT(grad_tiles(70) == 2 && grad_tile_at(1, 70).first == 64 && grad_tile_at(1, 70).count == 6, "hand plan 1 tiles");
   }
   // by hand: layer4.1 at (16, 19, 19), the plan's own chunks.  5,776 pixels in chunks of 2,048, 2,048 and 1,680; the
   // partials are 3 x 512 x 4,608 x 4 = 28,311,552 bytes after dA (5,776 x 512 x 4 = 11,829,248 bytes); 91 bias blocks
@@ -137,9 +100,9 @@ int main() {
     BlockForwardPlan f;
     EXPECT(block_grad_plan(4, 1, 16, 19, 19, 0, &p) && block_forward_plan(4, 1, 16, 19, 19, &f), "hand plan 2 refused");
     EXPECT(p.s.cin == 512 && p.s.cout == 512 && p.s.stride == 1 && p.s.npix_out == 5776, "hand plan 2 shape");
-    EXPECT(p.wg[1].Kc == 2048 && p.wg[1].chunks == 3 && block_chunk_at(2, 5776, 2048).count == 1680, "hand plan 2 chunks");
+    EXPECT(p.wg[1].Kc == 2048 && p.wg[1].chunks == 3 && grad_chunk_at(2, 5776, 2048).count == 1680, "hand plan 2 chunks");
     EXPECT(p.wg[2].taps == 0, "hand plan 2 has no downsample");
-    EXPECT(p.bs.pixels == 64 && p.bs.blocks == 91 && block_chunk_at(90, 5776, 64).count == 16, "hand plan 2 bias");
+    EXPECT(p.bs.pixels == 64 && p.bs.blocks == 91 && grad_chunk_at(90, 5776, 64).count == 16, "hand plan 2 bias");
     EXPECT(p.off_part == 11829248 && p.off_bpart == 11829248 + 28311552 && p.total == 11829248 + 28311552 + 372736,
            "hand plan 2 regions");
     EXPECT(f.off_amax_mid == 16384 && f.off_part == 32768 && f.part_floats == (size_t)2 * 5776 * 512 &&

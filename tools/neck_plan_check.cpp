@@ -5,47 +5,10 @@
 // is the largest chunk and within the cap, and that the workspace regions of both entries are disjoint, aligned and
 // inside the reported size; then two known answers computed by hand and the refused shapes.  Built with
 // -fsanitize=address,undefined by tests/test_neck_host.py.
-#include <cstdio>
-#include <vector>
-
 #include "../lidar-image_object-detection_-fpn_resnet-yolov8_amd/csrc/neck_plan.h"
+#include "plan_check.h"
 
 using namespace sfa;
-
-static long bad = 0, plans = 0;
-#define EXPECT(cond, ...)            \
-  do {                               \
-    if (!(cond)) {                   \
-      if (bad++ < 20) {              \
-        std::printf("BAD: " __VA_ARGS__); \
-        std::printf("\n");           \
-      }                              \
-    }                                \
-  } while (0)
-
-// runs of `per` over n items: every item once, in order, none empty, only the last short
-static void check_runs(int n, int per, int count, bool tiles, const char* what) {
-  std::vector<int> seen((size_t)n, 0);
-  int next = 0;
-  for (int c = 0; c < count; ++c) {
-    const NeckRange r = tiles ? neck_tile_at(c, n) : neck_chunk_at(c, n, per);
-    EXPECT(r.first == next && r.count >= 1 && r.count <= per && r.first + r.count <= n, "%s: run %d is [%d, +%d) of %d", what,
-           c, r.first, r.count, n);
-    EXPECT(c == count - 1 || r.count == per, "%s: run %d of %d is short and not the last", what, c, count);
-    if (r.first < 0 || r.count < 0 || r.first + r.count > n) return;
-    for (int i = 0; i < r.count; ++i) seen[(size_t)r.first + i]++;
-    next = r.first + r.count;
-  }
-  for (int v : seen) EXPECT(v == 1, "%s: an item is covered %d times (n %d per %d)", what, v, n, per);
-}
-
-static void check_regions(const size_t* off, const size_t* len, int n, const char* what) {
-  EXPECT(off[0] == 0, "%s: first region not at 0", what);
-  for (int i = 0; i < n; ++i) {
-    EXPECT(off[i] % kNkAlign == 0, "%s: region %d misaligned", what, i);
-    EXPECT(off[i] + len[i] <= off[i + 1], "%s: region %d overlaps the next / the end", what, i);
-  }
-}
 
 static void check_plan(int B, int h4, int w4, int mcp) {
   NeckGradPlan p;
@@ -56,44 +19,44 @@ static void check_plan(int B, int h4, int w4, int mcp) {
   ++plans;
   for (int r = 0; r < 4; ++r) {
     EXPECT(p.npix[r] == (B * h4 * w4) << (2 * r) && f.npix[r] == p.npix[r], "npix[%d] %d", r, p.npix[r]);
-    check_runs(p.npix[r], kNkTile, neck_tiles(p.npix[r]), true, "pixel tiles");
+    check_runs(p.npix[r], kGradTile, grad_tiles(p.npix[r]), true, "pixel tiles");
   }
-  const int cap = mcp > 0 ? mcp : kNkChunkPixels;
+  const int cap = mcp > 0 ? mcp : kGradChunkPixels;
   const int rows[4] = {256, 256, 128, 64}, cols[4] = {512, 256, 384, 192};
   size_t part = 0, bpart = 0;
   for (int i = 0; i < 4; ++i) {
     const NeckWgrad& g = p.wg[i];
-    EXPECT(g.rows == rows[i] && g.cols == cols[i] && g.npix == p.npix[i] && g.rows % kNkTile == 0 && g.cols % kNkTile == 0,
+    EXPECT(g.rows == rows[i] && g.cols == cols[i] && g.npix == p.npix[i] && g.rows % kGradTile == 0 && g.cols % kGradTile == 0,
            "wgrad %d: %d x %d over %d", i, g.rows, g.cols, g.npix);
     EXPECT(g.Kc >= 1 && g.Kc <= cap && g.Kc <= g.npix && (g.Kc == cap || g.Kc == g.npix), "wgrad %d: K_c %d, cap %d", i, g.Kc,
            cap);
     check_runs(g.npix, g.Kc, g.chunks, false, "split-K chunks");
-    check_runs(g.rows, kNkTile, neck_tiles(g.rows), true, "row tiles");
-    check_runs(g.cols, kNkTile, neck_tiles(g.cols), true, "column tiles");
+    check_runs(g.rows, kGradTile, grad_tiles(g.rows), true, "row tiles");
+    check_runs(g.cols, kGradTile, grad_tiles(g.cols), true, "column tiles");
     const size_t bytes = (size_t)g.chunks * g.rows * g.cols * 4;
     if (bytes > part) part = bytes;
   }
   for (int s = 0; s < 3; ++s) {
-    const NeckBias& b = p.bs[s];
-    EXPECT(b.npix == p.npix[s + 1] && b.cout == kNkCout[s] && b.cout <= 256 && b.pixels >= kNkBiasMinPixels &&
-               b.blocks >= 1 && b.blocks <= kNkBiasMaxBlocks,
+    const GradBias& b = p.bs[s];
+    EXPECT(b.npix == p.npix[s + 1] && b.cout == kNkCout[s] && b.cout <= 256 && b.pixels >= kGradBiasMinPixels &&
+               b.blocks >= 1 && b.blocks <= kGradBiasMaxBlocks,
            "bias %d: %d blocks of %d pixels", s, b.blocks, b.pixels);
     check_runs(b.npix, b.pixels, b.blocks, false, "bias blocks");
     const size_t bytes = (size_t)b.blocks * b.cout * 8;
     if (bytes > bpart) bpart = bytes;
     // the forward's and the data gradients' channel tiles
-    check_runs(kNkCout[s], kNkTile, neck_tiles(kNkCout[s]), true, "Cout tiles");
-    check_runs(kNkUp[s], kNkTile, neck_tiles(kNkUp[s]), true, "up tiles");
-    check_runs(kNkSkip[s], kNkTile, neck_tiles(kNkSkip[s]), true, "skip tiles");
-    EXPECT(kNkUp[s] % kNkStep == 0 && kNkSkip[s] % kNkStep == 0 && kNkCout[s] % kNkStep == 0, "K steps");
+    check_runs(kNkCout[s], kGradTile, grad_tiles(kNkCout[s]), true, "Cout tiles");
+    check_runs(kNkUp[s], kGradTile, grad_tiles(kNkUp[s]), true, "up tiles");
+    check_runs(kNkSkip[s], kGradTile, grad_tiles(kNkSkip[s]), true, "skip tiles");
+    EXPECT(kNkUp[s] % kGradStep == 0 && kNkSkip[s] % kGradStep == 0 && kNkCout[s] % kGradStep == 0, "K steps");
   }
-  const size_t goff[8] = {p.off_du3, p.off_dz2, p.off_du2, p.off_dz1, p.off_dl, p.off_part, p.off_bpart, p.total};
+  const size_t goff[7] = {p.off_du3, p.off_dz2, p.off_du2, p.off_dz1, p.off_dl, p.off_part, p.off_bpart};
   const size_t glen[7] = {(size_t)p.npix[3] * 128 * 4, (size_t)p.npix[2] * 128 * 4, (size_t)p.npix[2] * 256 * 4,
                           (size_t)p.npix[1] * 256 * 4, (size_t)p.npix[0] * 256 * 4, part, bpart};
-  check_regions(goff, glen, 7, "grad workspace");
-  const size_t foff[4] = {f.off_up, f.off_z1, f.off_z2, f.total};
+  check_regions(goff, glen, 7, p.total, "grad workspace");
+  const size_t foff[3] = {f.off_up, f.off_z1, f.off_z2};
   const size_t flen[3] = {(size_t)f.npix[1] * 512 * 4, (size_t)f.npix[1] * 256 * 4, (size_t)f.npix[2] * 128 * 4};
-  check_regions(foff, flen, 3, "forward workspace");
+  check_regions(foff, flen, 3, f.total, "forward workspace");
 }
 
 int main() {
@@ -116,7 +79,7 @@ int main() {
   EXPECT(neck_grad_plan(2, 2, 3, 7, &p), "known answer 1 refused");
   EXPECT(p.wg[0].Kc == 7 && p.wg[0].chunks == 2 && p.wg[1].chunks == 7 && p.wg[2].chunks == 28 && p.wg[3].chunks == 110,
          "known answer 1 chunks");
-  const NeckRange c6 = neck_chunk_at(6, 48, 7), c109 = neck_chunk_at(109, 768, 7);
+  const GradRange c6 = grad_chunk_at(6, 48, 7), c109 = grad_chunk_at(109, 768, 7);
   EXPECT(c6.first == 42 && c6.count == 6 && c109.first == 763 && c109.count == 5, "known answer 1 last chunks");
   EXPECT(p.bs[0].blocks == 1 && p.bs[1].blocks == 3 && p.bs[2].blocks == 12 && p.bs[2].pixels == 64, "known answer 1 bias");
   EXPECT(p.off_du3 == 0 && p.off_dz2 == 393216 && p.off_du2 == 491520 && p.off_dz1 == 688128 && p.off_dl == 737280 &&
@@ -134,13 +97,13 @@ int main() {
   EXPECT(p.npix[0] == 5776 && p.npix[3] == 369664 && p.wg[0].chunks == 3 && p.wg[1].chunks == 12 && p.wg[2].chunks == 46 &&
              p.wg[3].chunks == 181 && p.wg[3].Kc == 2048,
          "known answer 2 chunks");
-  const NeckRange k11 = neck_chunk_at(11, 23104, 2048), k180 = neck_chunk_at(180, 369664, 2048);
+  const GradRange k11 = grad_chunk_at(11, 23104, 2048), k180 = grad_chunk_at(180, 369664, 2048);
   EXPECT(k11.first == 22528 && k11.count == 576 && k180.first == 368640 && k180.count == 1024, "known answer 2 last chunks");
   EXPECT(p.bs[0].pixels == 91 && p.bs[0].blocks == 254 && p.bs[1].pixels == 361 && p.bs[1].blocks == 256 &&
              p.bs[2].pixels == 1444 && p.bs[2].blocks == 256,
          "known answer 2 bias");
-  const NeckRange t90 = neck_tile_at(90, 5776);
-  EXPECT(neck_tiles(5776) == 91 && t90.first == 5760 && t90.count == 16, "known answer 2 tiles");
+  const GradRange t90 = grad_tile_at(90, 5776);
+  EXPECT(grad_tiles(5776) == 91 && t90.first == 5760 && t90.count == 16, "known answer 2 tiles");
   // refused
   EXPECT(!neck_grad_plan(0, 4, 4, 0, &p) && !neck_grad_plan(1, 0, 4, 0, &p) && !neck_grad_plan(1, 4, -1, 0, &p) &&
              !neck_grad_plan(1, 4, 4, -1, &p) && !neck_grad_plan(64, 64, 64, 0, &p) && !neck_grad_plan(1, 8192, 1, 0, &p) &&

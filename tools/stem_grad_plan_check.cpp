@@ -3,31 +3,10 @@
 // cover every pixel once at caps 0, 3 and 17, the window / tap source functions agree with a brute-force enumeration at
 // odd and even sizes, and the refusals hold.
 //   g++ -std=c++17 -fsanitize=address,undefined tools/stem_grad_plan_check.cpp -o stem_grad_plan_check
-#include <cstdio>
-#include <vector>
-
 #include "../lidar-image_object-detection_-fpn_resnet-yolov8_amd/csrc/stem_grad_plan.h"
+#include "plan_check.h"
 
 using namespace sfa;
-
-static int bad = 0;
-#define EXPECT(cond, ...)                \
-  do {                                   \
-    if (!(cond)) {                       \
-      ++bad;                             \
-      std::printf("FAIL %s: ", #cond);   \
-      std::printf(__VA_ARGS__);          \
-      std::printf("\n");                 \
-    }                                    \
-  } while (0)
-
-static void check_regions(const size_t* off, const size_t* bytes, int n, size_t total, const char* what) {
-  for (int i = 0; i < n; ++i) {
-    EXPECT(off[i] % kBkAlign == 0 && off[i] + bytes[i] <= total, "%s region %d", what, i);
-    for (int j = 0; j < i; ++j)
-      EXPECT(off[j] + bytes[j] <= off[i] || off[i] + bytes[i] <= off[j], "%s regions %d and %d overlap", what, j, i);
-  }
-}
 
 static void check_shape(int B, int H, int W) {
   StemForwardPlan f;
@@ -42,17 +21,10 @@ static void check_shape(int B, int H, int W) {
   for (int cap : {0, 3, 17}) {
     StemGradPlan g;
     EXPECT(stem_grad_plan(B, H, W, cap, &g), "grad plan");
-    EXPECT(g.wg.Kc >= 1 && (cap == 0 ? g.wg.Kc <= kSgChunkPixels : g.wg.Kc <= cap), "Kc %d at cap %d", g.wg.Kc, cap);
-    long long sum = 0;
-    for (int c = 0; c < g.wg.chunks; ++c) {
-      const BlockRange r = block_chunk_at(c, g.wg.npix, g.wg.Kc);
-      EXPECT(r.first == sum && r.count >= 1 && r.count <= g.wg.Kc, "chunk %d", c);
-      sum += r.count;
-    }
-    EXPECT(sum == s.npix_a, "chunks cover %lld of %d pixels", sum, s.npix_a);
-    sum = 0;
-    for (int c = 0; c < g.bs.blocks; ++c) sum += block_chunk_at(c, g.bs.npix, g.bs.pixels).count;
-    EXPECT(sum == s.npix_a && g.bs.blocks <= kBkBiasMaxBlocks, "bias blocks");
+    EXPECT(g.wg.Kc >= 1 && (cap == 0 ? g.wg.Kc <= kGradChunkPixels : g.wg.Kc <= cap), "Kc %d at cap %d", g.wg.Kc, cap);
+    EXPECT(g.wg.npix == s.npix_a && g.bs.npix == s.npix_a && g.bs.blocks <= kGradBiasMaxBlocks, "pixels of the runs");
+    check_runs(g.wg.npix, g.wg.Kc, g.wg.chunks, false, "split-K chunks");
+    check_runs(g.bs.npix, g.bs.pixels, g.bs.blocks, false, "bias blocks");
     const size_t off[] = {g.off_da, g.off_part, g.off_bpart};
     const size_t bytes[] = {(size_t)s.npix_a * kSgC * 4, (size_t)g.wg.chunks * kSgC * kSgK * 4, (size_t)g.bs.blocks * kSgC * 8};
     check_regions(off, bytes, 3, g.total, "grad");
@@ -88,7 +60,6 @@ static void check_axis(int n) {
 }
 
 int main() {
-  int plans = 0;
   const int shapes[][3] = {{1, 1, 1}, {1, 4, 4}, {1, 6, 10}, {2, 12, 20}, {1, 36, 52}, {2, 64, 96}, {1, 32, 160},
                            {3, 7, 9},  {1, 5, 3}, {16, 608, 608}, {1, 32760, 32}, {65535, 2, 2}};
   for (const auto& s : shapes) {
@@ -108,6 +79,6 @@ int main() {
   EXPECT(!stem_forward_plan(32, 1024, 1024, &f) && !stem_grad_plan(32, 1024, 1024, 0, &g), "2^31-byte map a");
   EXPECT(stem_forward_plan(31, 1024, 1024, &f) && stem_grad_plan(31, 1024, 1024, 0, &g), "map a below 2^31 bytes");
   EXPECT(stem_forward_plan(1, 4096, 4096, &f) && stem_grad_plan(1, 4096, 4096, 3, &g), "2^30-byte map a");
-  std::printf("%d plans, %d bad\n", plans, bad);
+  std::printf("%ld plans, %ld bad\n", plans, bad);
   return bad ? 1 : 0;
 }
