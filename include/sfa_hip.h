@@ -941,6 +941,68 @@ int sfa_bn_unfold_grad(const float* W, const float* gamma, const float* mean, co
                        const float* dWf, const float* dbf, int Cout, int K, float* dW, float* dgamma, float* dbeta,
                        void* stream);
 
+/* ------------------------- one BasicBlock in training mode: BatchNorm with batch statistics (layer1..4) --
+ * models/fpn_resnet.py:42-71 under model.train(): every BatchNorm normalises with the mean and the biased variance
+ * of the batch and is differentiated through them.  The entries take NO model handle (a handle holds folded fp16
+ * terms packed on the host, and training changes the weights every step): the caller passes the raw float32
+ * parameters in torch's layouts.  Geometry comes from (layer, block) as in sfa_model_block_*; all maps are DEVICE
+ * float32 NHWC, 16-byte aligned: x (B, h, w, Cin); z1, mid, z2, zd, y, gy (B, oh, ow, Cout).  n = B oh ow is what one
+ * channel of a BatchNorm sees.
+ *   z1 = conv3x3_s(x; W1)            mean1, var1 = the batch mean and biased variance of z1 per channel
+ *   mid = ReLU(s1 z1 + t1)           s = gamma / sqrt(var + eps),  t = beta - mean s
+ *   z2 = conv3x3_1(mid; W2)          mean2, var2
+ *   zd = conv1x1_s(x; Wd)            meand, vard        (block 0 of layer2..4 only)
+ *   y  = ReLU(s2 z2 + t2 + (x  or  sd zd + td))
+ *   params   HOST array of 9 DEVICE pointers W1 (Cout, Cin, 3, 3), gamma1, beta1, W2 (Cout, Cout, 3, 3), gamma2,
+ *            beta2, Wd (Cout, Cin, 1, 1), gammad, betad; the last three NULL on a block without a downsample
+ *   stats    DEVICE float32 [nbn][2][Cout], nbn = 2 (3 with a downsample): mean then biased variance of BatchNorm
+ *            1, 2 and the downsample's; the forward writes it, the gradient reads it
+ *
+ * sfa_block_train_forward writes z1, mid, z2, zd (NULL exactly on a block without a downsample), y and stats, every
+ * byte.  The convolutions are float32 on v_mfma_f32_32x32x2_f32, K in (tap, channel) order inside one workgroup, from
+ * k-major copies of the weights rebuilt in the workspace every call.  The statistics are float64 sums of z and z^2
+ * over blocks of pixels in pixel order, then over the blocks in block order (at most 256; max_chunk_pixels > 0 also
+ * caps a block): mean = S1 / n, var = max(S2 / n - mean^2, 0), each rounded once to float32.  s and t are computed
+ * once per channel in float64 FROM THE ROUNDED mean and var and rounded once; each BatchNorm is then one float32 FMA
+ * per element, the skip one float32 addition, then the ReLU.
+ *
+ * sfa_block_train_grad: from gy = d total / d y, the maps and the statistics the forward wrote, with
+ * dY = y > 0 ? gy : 0 and invstd = 1 / sqrt(var + eps), per BatchNorm
+ *   dbeta = sum dY     dgamma = invstd sum dY (z - mean)
+ *   dZ = gamma invstd (dY - sum dY / n - (z - mean) invstd^2 sum dY (z - mean) / n)
+ * (the two sums in float64 in the statistics' block order; dZ in float64 per element, rounded once, stored in the
+ * workspace), then
+ *   dW2 = wgrad_1(dZ2, mid)          dA  = mid > 0 ? dgrad_1(dZ2; W2) : 0       dZ1 = BatchNorm 1's backward of dA
+ *   dW1 = wgrad_s(dZ1, x)            dWd = wgrad1x1_s(dZd, x)
+ *   dx  = dgrad_s(dZ1; W1) + (dY  or  dgrad1x1_s(dZd; Wd))
+ * through sfa_model_block_grad's data- and weight-gradient kernels (split-K chunks of at most max_chunk_pixels
+ * output pixels, 0: the plan's own size).
+ *   grad_x       NULL (not wanted) or (B, h, w, Cin); every byte written
+ *   dparams      NULL, or a HOST array of 9 DEVICE pointers dW1, dgamma1, dbeta1, dW2, dgamma2, dbeta2, dWd,
+ *                dgammad, dbetad in torch's shapes, each may be NULL; the last three must be NULL on a block without
+ *                a downsample; every byte of a wanted output is written
+ *   params       as in the forward; the betas are not read and may be NULL
+ * sfa_block_train_chunk_pixels(which = 0: dW1, 1: dW2, 2: dWd) is K_c, the pixels of that gradient's largest chunk;
+ * which = 3 is the pixels of one statistics block (0 when refused, or which = 2 without a downsample).
+ * No atomics, no memset, nothing allocates or synchronises; two runs are bit-identical; graph-capturable.
+ *
+ * All of these, before any launch: SFA_E_INVALID for a NULL required pointer, no output wanted, layer outside 1..4,
+ * block outside 0..1, non-positive B, h or w, a negative max_chunk_pixels, a negative eps, a misaligned buffer, a
+ * workspace that is too small, a downsample pointer on a block without one (zd, dWd, dgammad, dbetad; the forward
+ * also refuses its parameters Wd, gammad, betad there, the gradient never reads them), a map of 2^31 bytes or more, or n < 2
+ * (torch: "Expected more than 1 value per channel when training"; the size functions return 0). */
+size_t sfa_block_train_forward_workspace_size(int layer, int block, int B, int h, int w, int max_chunk_pixels);
+size_t sfa_block_train_grad_workspace_size(int layer, int block, int B, int h, int w, int max_chunk_pixels);
+int sfa_block_train_chunk_pixels(int layer, int block, int which, int B, int h, int w, int max_chunk_pixels);
+int sfa_block_train_forward(int layer, int block, const float* x, const float* const* params, double eps, int B, int h,
+                            int w, float* z1, float* mid, float* z2, float* zd, float* y, float* stats,
+                            int max_chunk_pixels, void* workspace, size_t workspace_bytes, void* stream);
+int sfa_block_train_grad(int layer, int block, const float* x, const float* z1, const float* mid, const float* z2,
+                         const float* zd, const float* y, const float* gy, const float* stats,
+                         const float* const* params, double eps, int B, int h, int w, float* grad_x,
+                         float* const* dparams, int max_chunk_pixels, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* ------------------------------------------- the stem as an operator (both backbone families) --
  * models/fpn_resnet.py:179-182 on a caller's image, bn1 as the handle holds it: running statistics, folded into conv1
  * (W' = s W, b' = beta - mean s, s = gamma / sqrt(var + 1e-5)).  x is DEVICE float32 (B, 3, H, W) NCHW (SFA_IN_NCHW3;

@@ -12,6 +12,7 @@
 // Every check is made before the first launch; nothing allocates or synchronises.
 #include <cstring>
 
+#include "block_host.h"
 #include "block_kernel.h"
 #include "conv.h"
 #include "dispatch.h"
@@ -30,20 +31,20 @@ int block_level(const char* who, const sfa_model* model, int layer, int block, B
   return SFA_OK;
 }
 
-int wgrad(const BlockWgrad& g, const BlockShape& s, const float* gr, const float* gm, const float* x, int h, int w,
-          int stride, int tap0, float* part, float* dW, hipStream_t st) {
+}  // namespace
+
+int sfa::launch_block_wgrad(const BlockWgrad& g, const BlockShape& s, const float* gr, const float* gm, const float* x,
+                            int h, int w, int stride, int tap0, float* part, float* dW, hipStream_t st) {
   const BkWgrad t = {gr, gm, x, h, w, s.oh, s.ow, stride, g.cin, g.rows, tap0, g.taps, g.npix, g.Kc};
   const dim3 grid((unsigned)g.chunks, (unsigned)(g.taps * g.cin / kGradTile), (unsigned)(g.rows / kGradTile));
   if (int rc = launch({grid, dim3(256), st}, block_wgrad_kernel, t, part)) return rc;
   return launch_wgrad_fold(part, g.chunks, g.rows, g.cin, g.taps, dW, g.cin, 0, st);
 }
 
-int dgrad(const BkDgrad& t, float* out, hipStream_t st) {
+int sfa::launch_block_dgrad(const BkDgrad& t, float* out, hipStream_t st) {
   return launch({dim3((unsigned)grad_tiles(t.npix), (unsigned)(t.cin / kGradTile)), dim3(256), st}, block_dgrad_kernel, t,
                 out);
 }
-
-}  // namespace
 
 extern "C" size_t sfa_model_block_forward_workspace_size(const sfa_model* model, int layer, int block, int B, int h,
                                                          int w) {
@@ -171,9 +172,9 @@ extern "C" int sfa_model_block_grad(const sfa_model* model, int layer, int block
   if (db2)
     if (int rc = launch_bias_grad(plan.bs, gy, y, bpart, db2, st)) return rc;
   if (dW2)
-    if (int rc = wgrad(plan.wg[1], s, gy, y, mid, s.oh, s.ow, 1, 0, part, dW2, st)) return rc;
+    if (int rc = launch_block_wgrad(plan.wg[1], s, gy, y, mid, s.oh, s.ow, 1, 0, part, dW2, st)) return rc;
   if (dWd)
-    if (int rc = wgrad(plan.wg[2], s, gy, y, x, h, w, s.stride, 4, part, dWd, st)) return rc;
+    if (int rc = launch_block_wgrad(plan.wg[2], s, gy, y, x, h, w, s.stride, 4, part, dWd, st)) return rc;
   if (!grad_x && !dW1 && !db1) return SFA_OK;
 
   // dA = mid > 0 ? dgrad_1(dZ; W2') : 0
@@ -181,11 +182,11 @@ extern "C" int sfa_model_block_grad(const sfa_model* model, int layer, int block
   memset(&t2, 0, sizeof t2);
   t2.g0 = gy, t2.m0 = y, t2.W0 = bl.w[1], t2.ldw0 = bl.K[1], t2.om = mid;
   t2.h = s.oh, t2.w = s.ow, t2.oh = s.oh, t2.ow = s.ow, t2.s = 1, t2.cin = s.cout, t2.cout = s.cout, t2.npix = s.npix_out;
-  if (int rc = dgrad(t2, dA, st)) return rc;
+  if (int rc = launch_block_dgrad(t2, dA, st)) return rc;
   if (db1)
     if (int rc = launch_bias_grad(plan.bs, dA, nullptr, bpart, db1, st)) return rc;
   if (dW1)
-    if (int rc = wgrad(plan.wg[0], s, dA, nullptr, x, h, w, s.stride, 0, part, dW1, st)) return rc;
+    if (int rc = launch_block_wgrad(plan.wg[0], s, dA, nullptr, x, h, w, s.stride, 0, part, dW1, st)) return rc;
   if (!grad_x) return SFA_OK;
 
   // dx = dgrad_s(dA; W1') + the skip
@@ -197,7 +198,7 @@ extern "C" int sfa_model_block_grad(const sfa_model* model, int layer, int block
   else
     t1.eg = gy, t1.em = y;
   t1.h = h, t1.w = w, t1.oh = s.oh, t1.ow = s.ow, t1.s = s.stride, t1.cin = s.cin, t1.cout = s.cout, t1.npix = s.npix_in;
-  return dgrad(t1, grad_x, st);
+  return launch_block_dgrad(t1, grad_x, st);
 }
 
 extern "C" int sfa_bn_unfold_grad(const float* W, const float* gamma, const float* mean, const float* var, double eps,

@@ -20,20 +20,10 @@
 // No atomics; every sum has a fixed order, so runs are bit-identical.
 #pragma once
 
-#include "block_plan.h"
+#include "block_plan.h"  // BkDgrad, BkWgrad
 #include "grad_tile.h"
 
 namespace sfa {
-
-// The maps of one data gradient.  g0 (B, oh, ow, cout), masked by m0 when it is not null, meets W0 [o][tap cin + c]
-// (row stride ldw0) through the nine taps; g1 / m1 / W1 [o][c] (row stride ldw1), when g1 is not null, through the
-// centre tap alone.  eg / em: the masked map the epilogue adds (same shape as out), or null.  om: the map whose sign
-// masks the result, or null.
-struct BkDgrad {
-  const float *g0, *m0, *W0, *g1, *m1, *W1, *eg, *em, *om;
-  int ldw0, ldw1;
-  int h, w, oh, ow, s, cin, cout, npix;  // out is (B, h, w, cin), npix = B h w
-};
 
 // out[p][i] = sum over (tap, o) of g0[src(p, tap)][o] W0[o][tap cin + i] + sum over o of g1[src(p, centre)][o] W1[o][i]
 // grid (grad_tiles(npix), cin / 64), block (256)
@@ -100,13 +90,6 @@ __global__ void __launch_bounds__(256) block_dgrad_kernel(BkDgrad t, float* __re
     }
   }
 }
-
-// One weight gradient.  g (B, oh, ow, M) masked by gm when it is not null; x (B, h, w, cin) read through taps
-// tap0 .. tap0 + ntaps - 1 of the 3x3 / pad 1 / stride s window.
-struct BkWgrad {
-  const float *g, *gm, *x;
-  int h, w, oh, ow, s, cin, M, tap0, ntaps, npix, Kc;  // npix = B oh ow
-};
 
 // part[chunk][o][(tap - tap0) cin + c] = sum over the chunk's output pixels p of g[p][o] x[src(p, tap)][c]
 // grid (chunks, ntaps cin / 64, M / 64), block (256)

@@ -102,4 +102,23 @@ SFA_GRAD_HD inline int block_tap_source(int i, int k, int s, int on) {
   return o < on ? o : -1;
 }
 
+// The kernels' arguments (block_kernel.h), here so that a host file can fill them (block_host.h).
+
+// The maps of one data gradient.  g0 (B, oh, ow, cout), masked by m0 when it is not null, meets W0 [o][tap cin + c]
+// (row stride ldw0) through the nine taps; g1 / m1 / W1 [o][c] (row stride ldw1), when g1 is not null, through the
+// centre tap alone.  eg / em: the masked map the epilogue adds (same shape as out), or null.  om: the map whose sign
+// masks the result, or null.
+struct BkDgrad {
+  const float *g0, *m0, *W0, *g1, *m1, *W1, *eg, *em, *om;
+  int ldw0, ldw1;
+  int h, w, oh, ow, s, cin, cout, npix;  // out is (B, h, w, cin), npix = B h w
+};
+
+// One weight gradient.  g (B, oh, ow, M) masked by gm when it is not null; x (B, h, w, cin) read through taps
+// tap0 .. tap0 + ntaps - 1 of the 3x3 / pad 1 / stride s window.
+struct BkWgrad {
+  const float *g, *gm, *x;
+  int h, w, oh, ow, s, cin, M, tap0, ntaps, npix, Kc;  // npix = B oh ow
+};
+
 }  // namespace sfa

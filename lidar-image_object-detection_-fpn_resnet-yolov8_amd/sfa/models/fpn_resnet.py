@@ -22,7 +22,8 @@ import torch.nn.functional as F
 
 from sfa_hip import _lib
 from sfa_hip import dropin as _dropin
-from sfa_hip.runtime import KfpnEngine, bn_unfold_grad, kfpn_combine_grad, kfpn_heads, pack_state_dict
+from sfa_hip.runtime import (KfpnEngine, block_train_forward, block_train_grad, bn_unfold_grad, kfpn_combine_grad, kfpn_heads,
+                             pack_state_dict)
 
 BN_MOMENTUM = 0.1
 
@@ -232,6 +233,40 @@ class _BlockFromInput(torch.autograd.Function):
                                            dp[(0, 2, 4)[i]] if (n[0] or n[1]) else torch.empty_like(conv.weight),
                                            dp[(1, 3, 3)[i]] if (n[1] or n[2]) else torch.empty_like(bn.weight), want=n))
         return (None, None, None, None, None if dx is None else dx.permute(0, 3, 1, 2)) + tuple(out)
+
+
+class _BlockTrainFromInput(torch.autograd.Function):
+    """One BasicBlock in training mode as an operator over its input and its 6 (9 with a downsample) parameters:
+    forward is sfa_block_train_forward on the NHWC view of a channels-last tensor and the raw parameters, every
+    BatchNorm normalising with the statistics of the batch; backward one sfa_block_train_grad on the saved maps and
+    statistics, every BatchNorm differentiated through them.  No engine and no host repack.  Returns (y, stats);
+    ``stats`` (nbn, 2, Cout), the batch means and biased variances, is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, layer, block, eps, x, *params):
+        xn = x.permute(0, 2, 3, 1)
+        ps = [p.detach().contiguous() for p in params]
+        with torch.cuda.device(x.device):
+            m = block_train_forward(layer, block, xn, ps, eps)
+        ctx.layer, ctx.block, ctx.eps, ctx.ds = layer, block, eps, m["zd"] is not None
+        ctx.save_for_backward(xn, m["z1"], m["mid"], m["z2"], m["y"], m["stats"], *([m["zd"]] if ctx.ds else []), *ps)
+        ctx.mark_non_differentiable(m["stats"])
+        return m["y"].permute(0, 3, 1, 2), m["stats"]
+
+    @staticmethod
+    def backward(ctx, gy, _gstats):
+        saved = ctx.saved_tensors
+        xn, z1, mid, z2, y, stats = saved[:6]
+        zd = saved[6] if ctx.ds else None
+        ps = list(saved[7 if ctx.ds else 6:])
+        need = ctx.needs_input_grad
+        if not any(need[3:]):
+            return (None,) * len(need)
+        with torch.cuda.device(xn.device):
+            g = _nhwc_grad(gy, y.shape, xn.device)
+            dx, dp = block_train_grad(ctx.layer, ctx.block, xn, dict(z1=z1, mid=mid, z2=z2, zd=zd, y=y, stats=stats), g,
+                                      ps, ctx.eps, want_x=need[3], want_params=need[4:])
+        return (None, None, None, None if dx is None else dx.permute(0, 3, 1, 2)) + tuple(dp[:len(ps)])
 
 
 class _StemFromImage(torch.autograd.Function):
@@ -497,42 +532,72 @@ class PoseResNet(nn.Module):
         return [p for L in (1, 2, 3, 4) for b in (0, 1) for conv, bn in self._block_mods(L, b)
                 for p in (conv.weight, bn.weight, bn.bias)]
 
-    def block_from_input(self, layer, block, x):
+    def block_from_input(self, layer, block, x, batch_stats=False, update_running=True):
         """BasicBlock ``layer{layer}.{block}`` (models/fpn_resnet.py:42-71) on a caller's ``x``, a (B, Cin, h, w) float32
         GPU tensor taken as channels-last bytes: returns the block's output (B, Cout, ceil(h / s), ceil(w / s)).
         BatchNorm uses its running statistics whatever ``.training`` says, folded into the convolutions, exactly as
         :meth:`forward` does; the gradients are those of the block in ``eval()``.  Differentiable with respect to ``x``
         and the block's 6 parameters (9 with a downsample): sfa_model_block_forward; sfa_model_block_grad and
         sfa_bn_unfold_grad in backward.  Parameters that do not require grad get None.  x, mid and y are saved for
-        backward.  A parameter changed in place is seen by the next call (the engine repacks)."""
+        backward.  A parameter changed in place is seen by the next call (the engine repacks).
+
+        ``batch_stats=True`` is the block under ``model.train()`` instead: every BatchNorm normalises with the mean
+        and biased variance of the batch and is differentiated through them (sfa_block_train_forward /
+        sfa_block_train_grad on the raw parameters; the engine is not called, nothing is repacked on the host; B oh ow
+        must be at least 2).  After the forward each BatchNorm's ``running_mean``, ``running_var`` (unbiased,
+        n / (n - 1)) and ``num_batches_tracked`` move exactly as ``nn.BatchNorm2d`` moves them in ``train()``, under
+        ``no_grad``, unless ``update_running`` is False."""
         self._no_neck("block_from_input")
         if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
             raise _lib.SfaNativeError("PoseResNet.block_from_input runs on the GPU (HIP) only")
         cin = KfpnEngine.block_shape(layer, block)[0]
         if x.dim() != 4 or x.shape[1] != cin:
             raise ValueError(f"block_from_input: expected (B, {cin}, h, w) at layer{layer}.{block}, got {tuple(x.shape)}")
-        eng = self._engine(x.device)
-        x = x.float().contiguous(memory_format=torch.channels_last)
         mods = self._block_mods(layer, block)
         params = [p for conv, bn in mods for p in (conv.weight, bn.weight, bn.bias)]
+        if batch_stats:
+            return self._block_train(int(layer), int(block), mods, params, x, update_running)
+        eng = self._engine(x.device)
+        x = x.float().contiguous(memory_format=torch.channels_last)
         return _BlockFromInput.apply(eng, int(layer), int(block), mods, x, *params)
 
-    def layers_from_pooled(self, x):
+    def _block_train(self, layer, block, mods, params, x, update_running):
+        eps = float(mods[0][1].eps)
+        if any(float(bn.eps) != eps for _, bn in mods):
+            raise ValueError(f"block_from_input: the BatchNorms of layer{layer}.{block} differ in eps")
+        x = x.float().contiguous(memory_format=torch.channels_last)
+        y, stats = _BlockTrainFromInput.apply(layer, block, eps, x, *params)
+        if update_running:
+            n = y.numel() // y.shape[1]
+            with torch.no_grad():
+                for i, (_, bn) in enumerate(mods):
+                    if bn.running_mean is None:
+                        continue
+                    bn.num_batches_tracked += 1
+                    m = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else float(bn.momentum)
+                    bn.running_mean.mul_(1.0 - m).add_(stats[i, 0], alpha=m)
+                    bn.running_var.mul_(1.0 - m).add_(stats[i, 1], alpha=m * n / (n - 1))
+        return y
+
+    def layers_from_pooled(self, x, batch_stats=False, update_running=True):
         """``layer1..4`` (models/fpn_resnet.py:184-187) on a caller's pooled stem output ``x`` (B, 64, h, w): the eight
-        blocks chained through :meth:`block_from_input`.  Returns (out_layer1, out_layer2, out_layer3, out_layer4)
-        whose grad_fn reaches ``x`` and the 57 :meth:`block_parameters`."""
+        blocks chained through :meth:`block_from_input` (``batch_stats`` / ``update_running`` as there).  Returns
+        (out_layer1, out_layer2, out_layer3, out_layer4) whose grad_fn reaches ``x`` and the 57
+        :meth:`block_parameters`."""
+        kw = dict(batch_stats=True, update_running=update_running) if batch_stats else {}
         outs = []
         for layer in (1, 2, 3, 4):
             for block in (0, 1):
-                x = self.block_from_input(layer, block, x)
+                x = self.block_from_input(layer, block, x, **kw)
             outs.append(x)
         return tuple(outs)
 
-    def detect_from_pooled(self, x):
+    def detect_from_pooled(self, x, batch_stats=False, update_running=True):
         """:meth:`detect_from_layers` of :meth:`layers_from_pooled`: everything behind the stem on a caller's pooled map
         (B, 64, h, w), h and w multiples of 8.  The five maps carry a grad_fn reaching ``x`` and 123 of the model's 126
-        parameters; the stem's conv1.weight, bn1.weight, bn1.bias are reached through :meth:`detect_from_image`."""
-        return self.detect_from_layers(*self.layers_from_pooled(x))
+        parameters; the stem's conv1.weight, bn1.weight, bn1.bias are reached through :meth:`detect_from_image`.
+        ``batch_stats=True`` runs the eight blocks on batch statistics (the neck and the heads have no BatchNorm)."""
+        return self.detect_from_layers(*self.layers_from_pooled(x, batch_stats=batch_stats, update_running=update_running))
 
     def stem_parameters(self):
         """conv1.weight, bn1.weight, bn1.bias: the order :meth:`stem_from_image` differentiates them in."""

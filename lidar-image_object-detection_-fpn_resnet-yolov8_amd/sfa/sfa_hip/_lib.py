@@ -261,6 +261,14 @@ _PROTOS["sfa_model_block_grad_chunk_pixels"] = (_c_int, [_vp] + [_c_int] * 7)
 _PROTOS["sfa_model_block_grad"] = (_c_int, [_vp, _c_int, _c_int] + [_vp] * 4 + [_c_int] * 3 + [_vp, ctypes.POINTER(_vp),
                                             _c_int, _vp, _c_size, _vp])
 _PROTOS["sfa_bn_unfold_grad"] = (_c_int, [_vp] * 4 + [ctypes.c_double] + [_vp] * 2 + [_c_int] * 2 + [_vp] * 4)
+# one BasicBlock in training mode (batch statistics): no handle, raw float32 parameters in
+_PROTOS["sfa_block_train_forward_workspace_size"] = (_c_size, [_c_int] * 6)
+_PROTOS["sfa_block_train_grad_workspace_size"] = (_c_size, [_c_int] * 6)
+_PROTOS["sfa_block_train_chunk_pixels"] = (_c_int, [_c_int] * 7)
+_PROTOS["sfa_block_train_forward"] = (_c_int, [_c_int, _c_int, _vp, ctypes.POINTER(_vp), ctypes.c_double] + [_c_int] * 3
+                                      + [_vp] * 6 + [_c_int, _vp, _c_size, _vp])
+_PROTOS["sfa_block_train_grad"] = (_c_int, [_c_int, _c_int] + [_vp] * 8 + [ctypes.POINTER(_vp), ctypes.c_double]
+                                   + [_c_int] * 3 + [_vp, ctypes.POINTER(_vp), _c_int, _vp, _c_size, _vp])
 # the stem as an operator: forward and gradients on a caller's (B, 3, H, W) image
 _PROTOS["sfa_model_stem_forward_workspace_size"] = (_c_size, [_vp] + [_c_int] * 3)
 _PROTOS["sfa_model_stem_forward"] = (_c_int, [_vp, _vp] + [_c_int] * 3 + [_vp, _vp, _vp, _c_size, _vp])

@@ -1768,6 +1768,108 @@ def bn_unfold_grad(weight, gamma, mean, var, eps, dWf, dbf, want=(True, True, Tr
     return dW, dg, dbt
 
 
+# ------------------------------------------------- one BasicBlock in training mode (batch statistics): no engine
+def _block_train_dims(what, layer, block, x, params):
+    cin, cout, s, ds = KfpnEngine.block_shape(layer, block)
+    x = _require_gpu_tensor(x, f"{what} x")
+    if x.dim() != 4 or int(x.shape[3]) != cin:
+        raise ValueError(f"{what} x: {tuple(x.shape)} is not the NHWC (B, h, w, {cin}) of layer{layer}.{block}")
+    B, h, w, _ = (int(v) for v in x.shape)
+    shapes = [(cout, cin, 3, 3), (cout,), (cout,), (cout, cout, 3, 3), (cout,), (cout,)]
+    shapes += [(cout, cin, 1, 1), (cout,), (cout,)] if ds else []
+    params = list(params)
+    if len(params) != len(shapes):
+        raise ValueError(f"{what}: layer{layer}.{block} takes {len(shapes)} parameters, got {len(params)}")
+    ps = []
+    for i, (t, sh) in enumerate(zip(params, shapes)):
+        t = _require_gpu_tensor(t, f"{what} params[{i}]").detach()
+        if tuple(t.shape) != sh or not t.is_contiguous():
+            raise ValueError(f"{what} params[{i}]: a contiguous tensor of shape {sh} is needed, got {tuple(t.shape)}")
+        ps.append(t)
+    return x, B, h, w, cin, cout, ds, (B, -(-h // s), -(-w // s), cout), ps, shapes
+
+
+def _params9(ps):
+    return (ctypes.c_void_p * 9)(*([t.data_ptr() for t in ps] + [None] * (9 - len(ps))))
+
+
+def block_train_forward_workspace_bytes(layer, block, B, h, w, max_chunk_pixels: int = 0) -> int:
+    return int(lib().sfa_block_train_forward_workspace_size(layer, block, B, h, w, int(max_chunk_pixels)))
+
+
+def block_train_grad_workspace_bytes(layer, block, B, h, w, max_chunk_pixels: int = 0) -> int:
+    return int(lib().sfa_block_train_grad_workspace_size(layer, block, B, h, w, int(max_chunk_pixels)))
+
+
+def block_train_chunk_pixels(layer, block, which: int, B, h, w, max_chunk_pixels: int = 0) -> int:
+    """K_c of dW1 (which = 0), dW2 (1) or dWd (2) in :func:`block_train_grad`, or the pixels of one statistics block
+    (3); 0 for what the entries refuse."""
+    return int(lib().sfa_block_train_chunk_pixels(layer, block, int(which), B, h, w, int(max_chunk_pixels)))
+
+
+def block_train_forward(layer: int, block: int, x: torch.Tensor, params, eps: float = 1e-5, out: dict = None,
+                        max_chunk_pixels: int = 0, workspace: torch.Tensor = None) -> dict:
+    """BasicBlock layer{layer}.{block} in training mode (sfa_block_train_forward) on a caller's ``x``, float32 NHWC
+    (B, h, w, Cin) on the GPU: every BatchNorm normalises with the statistics of the batch.  ``params``: conv1.weight,
+    bn1.weight, bn1.bias, conv2.weight, bn2.weight, bn2.bias and, on a block with a downsample, downsample.0.weight,
+    downsample.1.weight, downsample.1.bias: raw contiguous float32 GPU tensors in torch's shapes (no engine, no host
+    repack).  Returns {z1, mid, z2, zd (None without a downsample), y, stats}: the NHWC maps (B, oh, ow, Cout) and
+    ``stats`` (nbn, 2, Cout), the batch mean and biased variance of BatchNorm 1, 2 and the downsample's.  ``out`` (the
+    same keys) receives them instead; with ``out`` and ``workspace`` given the call only enqueues its launches."""
+    what = "block_train_forward"
+    x, B, h, w, _, cout, ds, osh, ps, _ = _block_train_dims(what, layer, block, x, params)
+    names = ["z1", "mid", "z2"] + (["zd"] if ds else []) + ["y", "stats"]
+    shapes = [osh] * (len(names) - 1) + [(3 if ds else 2, 2, cout)]
+    bufs = dict(zip(names, _kfpn_buffers(out, names, shapes, x, f"{what} out")))
+    bufs.setdefault("zd", None)
+    workspace = _workspace(what, f"B={B}, h={h}, w={w}",
+                           block_train_forward_workspace_bytes(layer, block, B, h, w, max_chunk_pixels), workspace, x.device)
+    with torch.cuda.device(x.device):
+        check(lib().sfa_block_train_forward(layer, block, x.data_ptr(), _params9(ps), float(eps), B, h, w,
+                                            bufs["z1"].data_ptr(), bufs["mid"].data_ptr(), bufs["z2"].data_ptr(),
+                                            _opt_ptr(bufs["zd"]), bufs["y"].data_ptr(), bufs["stats"].data_ptr(),
+                                            int(max_chunk_pixels), workspace.data_ptr(), workspace.numel(),
+                                            _lib.stream_ptr(x.device)), "sfa_block_train_forward")
+    return bufs
+
+
+def block_train_grad(layer: int, block: int, x, maps: dict, gy, params, eps: float = 1e-5, want_x: bool = True,
+                     want_params=(True,) * 9, out=None, max_chunk_pixels: int = 0, workspace: torch.Tensor = None):
+    """The gradients of layer{layer}.{block} in training mode (sfa_block_train_grad), every BatchNorm differentiated
+    through its batch statistics, from ``gy`` = d total / d y, ``x`` and ``maps`` = what :func:`block_train_forward`
+    returned.  Returns (dx, [dW1, dgamma1, dbeta1, dW2, dgamma2, dbeta2, dWd, dgammad, dbetad]) in torch's shapes,
+    None where not wanted (the last three are None on a block without a downsample whatever ``want_params`` says);
+    every element of a wanted output is written.  ``out`` = (tensor or None, 9 tensors or Nones) receives them
+    instead of fresh tensors.  With ``out`` and ``workspace`` given the call only enqueues its launches."""
+    what = "block_train_grad"
+    x, B, h, w, cin, cout, ds, osh, ps, pshapes = _block_train_dims(what, layer, block, x, params)
+    ms = {}
+    for n in ["z1", "mid", "z2", "y"] + (["zd"] if ds else []):
+        ms[n] = _require_gpu_tensor(maps[n], f"{what} {n}")
+    ms["gy"] = _require_gpu_tensor(gy, f"{what} gy")
+    for n, t in ms.items():
+        if tuple(t.shape) != osh or not t.is_contiguous():
+            raise ValueError(f"{what} {n}: a contiguous NHWC {osh} is needed, got {tuple(t.shape)}")
+    stats = _require_gpu_tensor(maps["stats"], f"{what} stats")
+    if tuple(stats.shape) != (3 if ds else 2, 2, cout) or not stats.is_contiguous():
+        raise ValueError(f"{what} stats: a contiguous {(3 if ds else 2, 2, cout)} is needed, got {tuple(stats.shape)}")
+    want = [bool(want_x)] + [bool(v) for v in list(want_params)[:9]] + [False] * (9 - len(list(want_params)[:9]))
+    if not ds:
+        want[7:10] = [False] * 3
+    shapes = [(B, h, w, cin)] + pshapes + ([(1,)] * 3 if not ds else [])
+    given = out and ([out[0]] + list(out[1]) + [None] * (9 - len(out[1])))
+    res = _grad_outputs(what, want, shapes, given, x)
+    workspace = _workspace(what, f"B={B}, h={h}, w={w}",
+                           block_train_grad_workspace_bytes(layer, block, B, h, w, max_chunk_pixels), workspace, x.device)
+    with torch.cuda.device(x.device):
+        check(lib().sfa_block_train_grad(layer, block, x.data_ptr(), ms["z1"].data_ptr(), ms["mid"].data_ptr(),
+                                         ms["z2"].data_ptr(), _opt_ptr(ms.get("zd")), ms["y"].data_ptr(),
+                                         ms["gy"].data_ptr(), stats.data_ptr(), _params9(ps), float(eps), B, h, w,
+                                         _opt_ptr(res[0]), _dparams(res[1:]), int(max_chunk_pixels), workspace.data_ptr(),
+                                         workspace.numel(), _lib.stream_ptr(x.device)), "sfa_block_train_grad")
+    return res[0], res[1:]
+
+
 def _kfpn_operands(levels_by_head: dict, level0_half: bool, what: str):
     """Checks {head: [level 0, level 1, level 2]}: (names, flat contiguous tensors, channels, (B, h, w))."""
     if not isinstance(levels_by_head, dict) or not 1 <= len(levels_by_head) <= _lib.SFA_MAX_HEADS:

@@ -12,7 +12,18 @@ Traffic model (bytes, every map counted once per kernel that reads or writes it)
   gradient  dA (a, gp read, dA written), db' (dA), dW' (dA, x + partials written and read), dx (dA read, dx written)
 Arithmetic: 2 flops per multiply-add issued: forward 64 x 196 per conv pixel (the packed K with its zero fourth
 channel), dW' 64 x 192 per conv pixel (147 columns padded to three tiles), dx 3 x 64 x the live taps per image pixel
-(12.25 on average) in float64 on the vector unit, shown against the same f32 MFMA yardstick."""
+(12.25 on average) in float64 on the vector unit, shown against the same f32 MFMA yardstick.
+
+  block rows (--blocks adds them, --blocks-only prints them alone): layer1.1 at 16 frames of 152 x 152 and layer2.0
+  at 152 x 152 -> 76 x 76, training-mode forward + gradient (sfa_block_train_forward / sfa_block_train_grad, batch
+  statistics) beside the running-statistics operator's (sfa_model_block_forward / sfa_model_block_grad) from the same
+  job, each the median of 50 graph replays.  Training-mode traffic, M = one (npix_out, Cout) map, X = x:
+    forward   per convolution: its input read, z written, z read by the statistics; the two applies: z read, the skip
+              (X or zd) read, mid / y written
+    gradient  per BatchNorm: the reduce reads g, the mask and z, the apply reads them again and writes dZ; dW2 (dZ2,
+              mid), dA (dZ2, mid, dA written), dW1 (dZ1, X), dx (dZ1, [dZd | gy, y], dx written), dWd (dZd, X)
+  Arithmetic: 2 Cout 9 Cin (+ Cout Cin) flops per output pixel forward, twice that for the gradient (dW and the data
+  gradient of each convolution), against the f32 MFMA rate."""
 import json
 import os
 import sys
@@ -54,6 +65,47 @@ def train_step_us(gpu, sd, batch):
     return float(np.median(ts))
 
 
+def block_rows(gpu, eng, copy_rate):
+    rows = {}
+    us = lambda v, rate: round(v / rate * 1e6, 1)  # noqa: E731
+    for layer, block in ((1, 1), (2, 0)):
+        cin, cout, s, ds = eng.block_shape(layer, block)
+        h = 152
+        gen = torch.Generator().manual_seed(layer)
+        x = torch.randn((B, h, h, cin), generator=gen).to(gpu)
+        mods = [(cout, cin, 3), (cout, cout, 3)] + ([(cout, cin, 1)] if ds else [])
+        ps = []
+        for co, ci, k in mods:
+            ps += [(torch.randn((co, ci, k, k), generator=gen) / (k * k * ci) ** 0.5).to(gpu),
+                   torch.rand(co, generator=gen).add(0.5).to(gpu), torch.randn(co, generator=gen).mul(0.3).to(gpu)]
+        m = runtime.block_train_forward(layer, block, x, ps)
+        gy = torch.randn(m["y"].shape, generator=gen).to(gpu)
+        fws = torch.empty(runtime.block_train_forward_workspace_bytes(layer, block, B, h, h), dtype=torch.uint8, device=gpu)
+        gws = torch.empty(runtime.block_train_grad_workspace_bytes(layer, block, B, h, h), dtype=torch.uint8, device=gpu)
+        dx, dp = runtime.block_train_grad(layer, block, x, m, gy, ps)
+        tf = replay_us(lambda: runtime.block_train_forward(layer, block, x, ps, out={k: v for k, v in m.items() if v is not None},
+                                                           workspace=fws), gpu)
+        tg = replay_us(lambda: runtime.block_train_grad(layer, block, x, m, gy, ps, out=(dx, dp), workspace=gws), gpu)
+        mid, y = eng.block_forward(layer, block, x)
+        ews = torch.empty(eng.block_forward_workspace_bytes(layer, block, B, h, h), dtype=torch.uint8, device=gpu)
+        egws = torch.empty(eng.block_grad_workspace_bytes(layer, block, B, h, h), dtype=torch.uint8, device=gpu)
+        edx, edp = eng.block_grad(layer, block, x, mid, y, gy)
+        ef = replay_us(lambda: eng.block_forward(layer, block, x, out=(mid, y), workspace=ews), gpu)
+        eg = replay_us(lambda: eng.block_grad(layer, block, x, mid, y, gy, out=(edx, edp), workspace=egws), gpu)
+        npo = m["y"].numel() // cout
+        M, X = 4 * npo * cout, 4 * x.numel()
+        fbytes = (X + 2 * M) + (3 * M) + (2 * M) + (2 * M + (M if ds else X)) + ((X + 2 * M) if ds else 0)
+        nbn = 3 if ds else 2
+        gbytes = nbn * (3 * M + 4 * M) + 2 * M + 3 * M + (M + X) + (M + (M if ds else 2 * M) + X) + ((M + X) if ds else 0)
+        flops = 2 * npo * cout * (9 * cin + 9 * cout + (cin if ds else 0))
+        name = f"layer{layer}.{block}"
+        rows[name] = {"in": [B, h, h, cin], "train_forward_us": round(tf, 1), "train_grad_us": round(tg, 1),
+                      "train_forward_traffic_us": us(fbytes, copy_rate), "train_grad_traffic_us": us(gbytes, copy_rate),
+                      "train_forward_mfma_f32_us": us(flops, MFMA_F32_FLOPS), "train_grad_mfma_f32_us": us(2 * flops, MFMA_F32_FLOPS),
+                      "running_stats_forward_us": round(ef, 1), "running_stats_grad_us": round(eg, 1)}
+    return rows
+
+
 def main():
     gpu = torch.device("cuda", 0)
     arch = _lib.make_arch(dict(runtime.DEFAULT_HEADS))
@@ -62,6 +114,10 @@ def main():
     src, dst = torch.empty(1 << 28, dtype=torch.uint8, device=gpu), torch.empty(1 << 28, dtype=torch.uint8, device=gpu)
     copy_rate = 2 * src.numel() / (replay_us(lambda: dst.copy_(src), gpu) * 1e-6)  # read + write bytes per second
     del src, dst
+    if "--blocks-only" in sys.argv:
+        print(json.dumps({"frames": B, "replays": REPLAYS, "copy_GBps": round(copy_rate / 1e9, 1),
+                          "mfma_f32_TFLOPs": MFMA_F32_FLOPS / 1e12, "blocks": block_rows(gpu, eng, copy_rate)}))
+        return
     x = torch.from_numpy(synthetic.synthetic_bev(B, H, H, seed=3)).to(gpu)
     fws = torch.empty(eng.stem_forward_workspace_bytes(B, H, H), dtype=torch.uint8, device=gpu)
     a, pooled = eng.stem_forward(x)
@@ -91,6 +147,8 @@ def main():
            "stem_grad_without_dx_us": round(grad_nodx, 1), "stem_grad_without_dx_traffic_us": us(g_nodx, copy_rate),
            "stem_grad_without_dx_mfma_f32_us": us(wflops, MFMA_F32_FLOPS), "dx_us": round(grad - grad_nodx, 1)}
     del x, a, pooled, gp, dx, dp, fws, gws
+    if "--blocks" in sys.argv:
+        out["blocks"] = block_rows(gpu, eng, copy_rate)
     batch = B
     while batch >= 1:
         torch.cuda.empty_cache()
