@@ -115,7 +115,8 @@ static int launch_fpn(const ConvArgs& a, hipStream_t st) {
 
 // A strip launch: the instance with W from the conv's pre-tiled LDS image (h3sopt::W_IMAGE) when
 // the model set ConvArgs::wimg (fp16x3; the one-product mode keeps row-major W), else the row-major one.
-// conv_plan.h strip_tile_bn restates which tile width each rule below gives a conv: keep them together.
+// conv_plan.h strip_tile_bn gives the tile width of the rule's instance (body_conv_rule, which launch_conv_h
+// switches on).
 template <int BM, int BN, int WM, int OCC, int ABL, int TERMS>
 static int launch_strip(const ConvArgs& a, hipStream_t st) {
   if constexpr (TERMS == 2)
@@ -138,7 +139,6 @@ static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
   if (TERMS == 1 && sliced) return SFA_E_UNSUPPORTED;
   auto ok = [](int rc) { return rc != SFA_E_UNSUPPORTED; };
   int rc = SFA_E_UNSUPPORTED;
-  const bool strip = strip_ok(a) && !sliced;
   if (epilogue == EPI_HEAD) {
     bool image = false;  // fp16x3 with the model's W image (the one-product mode keeps row-major W)
     if constexpr (TERMS == 2) image = a.wimg != nullptr;
@@ -162,8 +162,10 @@ static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
       return rc;
     }
   }
+  // the body convs: the first choice is conv_plan.h body_conv_rule's, what its check refuses falls through
+  const BodyRule rule = body_conv_rule(a, TERMS);
   if (a.N == 64) {
-    if (strip) rc = launch_strip<128, 64, 32, 3, H3S_64, TERMS>(a, st);
+    if (rule == BODY_STRIP_128x64) rc = launch_strip<128, 64, 32, 3, H3S_64, TERMS>(a, st);
     if (!ok(rc) && a.Kpad >= 256)
       rc = launch_conv_h3_cfg<256, 64, 32, EPI_STD, 1, 32, 2, false, H3_PLAIN, 1, 64, TERMS>(a, st);
     if constexpr (TERMS == 2) {
@@ -175,22 +177,32 @@ static int launch_conv_h(const ConvArgs& a, int epilogue, hipStream_t st) {
   if (a.N % 128 == 0) {
     ConvArgs b = a;
     b.ksplit = pick_ksplit(a);
-    if (strip && b.ksplit == 1 && a.N == 256 && tile_rows(a) < 50000)
-      // layer3 (362 128-row tiles for 512 block slots): 64 x 128 tiles at 3 blocks / CU fill the
-      // chip; same per-element K order, so the same bits (tools/convbench4: 97.7 vs 102.0 us,
-      // profiles/r04a_convbench4_stem_regw_tiles.txt)
-      rc = launch_strip<64, 128, 16, 3, H3S_128, TERMS>(b, st);
-    else if (strip && b.ksplit == 2 && a.N == 512 && tile_rows(a) < 50000)
-      // layer4 (184 128 x 128 tiles x 2 slices for 512 block slots): the 64-wide layer1 form, 128 x 64
-      // tiles at 3 blocks / CU (736 blocks for 768 slots); same slices and per-element K order, so the
-      // same bits (tools/convbench4: 102.4-105.0 vs 107.4-110.7 us, profiles/r04o_convbench4_layer4_splits.txt)
-      rc = launch_strip<128, 64, 32, 3, H3S_64, TERMS>(b, st);
-    else if (strip && (3 * (a.seg[0].C >> 5)) % b.ksplit == 0)
-      rc = launch_strip<128, 128, 32, 3, H3S_128W, TERMS>(b, st);
-    else if (!strip && tile_rows(a) >= 50000)  // big-M stride-2 / two-segment: A from registers
-      // (3 blocks / CU, late round 5: 150-153 VGPRs, 722 tiles in one round; per launch within 1 %, bench
-      // +0.9 % with two steps in flight, bit-identical: profiles/r05bp_*)
-      rc = launch_conv_r3_cfg<128, 128, 32, EPI_STD, 3, 2, R3_BODY, TERMS>(b, st);
+    switch (rule) {
+      case BODY_STRIP_64x128:
+        // layer3 (362 128-row tiles for 512 block slots): 64 x 128 tiles at 3 blocks / CU fill the
+        // chip; same per-element K order, so the same bits (tools/convbench4: 97.7 vs 102.0 us,
+        // profiles/r04a_convbench4_stem_regw_tiles.txt)
+        rc = launch_strip<64, 128, 16, 3, H3S_128, TERMS>(b, st);
+        break;
+      case BODY_STRIP_128x64_KS2:
+        // layer4 (184 128 x 128 tiles x 2 slices for 512 block slots): the 64-wide layer1 form, 128 x 64
+        // tiles at 3 blocks / CU (736 blocks for 768 slots); same slices and per-element K order, so the
+        // same bits (tools/convbench4: 102.4-105.0 vs 107.4-110.7 us, profiles/r04o_convbench4_layer4_splits.txt)
+        rc = launch_strip<128, 64, 32, 3, H3S_64, TERMS>(b, st);
+        break;
+      case BODY_STRIP_128x128:
+      case BODY_STRIP_128x128_KS2:
+        rc = launch_strip<128, 128, 32, 3, H3S_128W, TERMS>(b, st);
+        break;
+      case BODY_R3:
+      case BODY_R3_KS2:  // big-M stride-2 / two-segment: A from registers
+        // (3 blocks / CU, late round 5: 150-153 VGPRs, 722 tiles in one round; per launch within 1 %, bench
+        // +0.9 % with two steps in flight, bit-identical: profiles/r05bp_*)
+        rc = launch_conv_r3_cfg<128, 128, 32, EPI_STD, 3, 2, R3_BODY, TERMS>(b, st);
+        break;
+      default:  // the conv_h3 forms below
+        break;
+    }
     if (!ok(rc)) {
       b.tile_cnt = nullptr;  // conv_h3: the reduce launch (conv_h3_kernel.h splitk_ticket)
       if ((a.Kpad / 32) % b.ksplit != 0) b.ksplit = 1;  // K not divisible into the slices: no split

@@ -132,18 +132,64 @@ inline bool strip_ok(const ConvArgs& a) {
          (g.C & 31) == 0 && a.Kpad == 9 * g.C && a.OH == g.H && a.OW == g.W;
 }
 
-// The tile width of the strip instance conv.hip's launch_conv_h gives this fp16x3 conv (its strip rules,
-// restated: 64-wide convs and the split-K 2 layer4 form on 128 x 64 tiles, the rest 128 wide), or 0 when
-// the conv takes another family. The model asks it before it hands a launch the conv's W image, which is
-// built for one tile width; the launch check (conv_h3s_image_check) refuses an image of another width.
-inline int strip_tile_bn(const ConvArgs& a) {
-  if (!strip_ok(a) || conv_sliced(a) || !a.wh || !a.winv || a.OH * a.OW < 128) return 0;
-  if (a.N == 64) return 64;
-  if (a.N % 128 != 0) return 0;
+// The rule table of the fp16 body convs (conv.hip launch_conv_h past its head and FPN rules): the instance
+// a conv is given first, BM x BN tiles and the split-K slices. launch_conv_h switches on it; what an
+// instance's own check still refuses (partials that do not fit, a K that is no multiple of the K tile)
+// falls through there to the conv_h3 forms and on to conv_x6g. tools/conv_plan_check.cpp walks it over the
+// model's sixteen residual-layer convs at every input size up to 2048 x 2048.
+enum BodyRule {
+  BODY_NONE = 0,           // no fp16 body instance: the caller's next family
+  BODY_STRIP_128x64,       // conv_h3s, the 64-wide convs (layer1)
+  BODY_STRIP_64x128,       // conv_h3s, the 256-wide convs below 3125 pixels a frame (layer3)
+  BODY_STRIP_128x64_KS2,   // conv_h3s, the 512-wide convs below 3125 pixels, 2 slices (layer4)
+  BODY_STRIP_128x128,      // conv_h3s, every other 128-column conv (layer2; layer3 from 3125 pixels)
+  BODY_STRIP_128x128_KS2,  // ... with 2 slices (layer4 from 3125 pixels)
+  BODY_R3,                 // conv_r3 128 x 128, R3_BODY: stride-2 / two-segment convs from 3125 pixels
+  BODY_R3_KS2,             // ... with 2 slices
+  BODY_H3_256x64,          // conv_h3, 64-wide convs that are no strip (or frames under 128 rows)
+  BODY_H3_128x64,          // conv_h3 on 16-wide K tiles, 64-wide convs of K < 256 (fp16x3 only)
+  BODY_H3_128x128,         // conv_h3, the 128-column convs no rule above takes
+  BODY_H3_128x128_KS2,     // ... with 2 slices
+  BODY_RULE_COUNT
+};
+
+inline const char* body_rule_name(BodyRule r) {
+  static const char* const names[BODY_RULE_COUNT] = {
+      "none",   "strip_128x64", "strip_64x128", "strip_128x64_ks2", "strip_128x128", "strip_128x128_ks2",
+      "r3_body", "r3_body_ks2", "h3_256x64",    "h3_128x64",        "h3_128x128",    "h3_128x128_ks2"};
+  return r >= 0 && r < BODY_RULE_COUNT ? names[r] : "?";
+}
+
+// terms: 2 is fp16x3, 1 the one-product mode (SFA_MATH_FP16), which has no sliced and no 16-wide-K form.
+// The strip kernel wants frames of >= 128 rows (h3s_min_frame_rows), whatever its tile.
+inline BodyRule body_conv_rule(const ConvArgs& a, int terms) {
+  const bool sliced = conv_sliced(a);
+  if (!a.wh || !a.winv || (terms == 1 && sliced)) return BODY_NONE;
+  const bool strip = strip_ok(a) && !sliced && a.OH * a.OW >= 128;
+  if (a.N == 64) {
+    if (strip) return BODY_STRIP_128x64;
+    if (a.Kpad >= 256) return BODY_H3_256x64;
+    return terms == 2 ? BODY_H3_128x64 : BODY_NONE;
+  }
+  if (a.N % 128 != 0) return BODY_NONE;
   const int ks = pick_ksplit(a);
-  if (ks == 1 && a.N == 256 && tile_rows(a) < 50000) return 128;
-  if (ks == 2 && a.N == 512 && tile_rows(a) < 50000) return 64;
-  return (3 * (a.seg[0].C >> 5)) % ks == 0 ? 128 : 0;
+  const bool big = tile_rows(a) >= 50000;
+  if (strip) {
+    if (ks == 1 && a.N == 256 && !big) return BODY_STRIP_64x128;
+    if (ks == 2 && a.N == 512 && !big) return BODY_STRIP_128x64_KS2;
+    if ((3 * (a.seg[0].C >> 5)) % ks == 0) return ks > 1 ? BODY_STRIP_128x128_KS2 : BODY_STRIP_128x128;
+  } else if (big) {
+    return ks > 1 ? BODY_R3_KS2 : BODY_R3;
+  }
+  return ks > 1 && (a.Kpad / 32) % ks == 0 ? BODY_H3_128x128_KS2 : BODY_H3_128x128;
+}
+
+// The tile width of the strip instance the rule gives this fp16x3 conv, or 0 when the conv takes another
+// family. The model asks it before it hands a launch the conv's W image, which is built for one tile
+// width; the launch check (conv_h3s_image_check) refuses an image of another width.
+inline int strip_tile_bn(const ConvArgs& a) {
+  const BodyRule r = body_conv_rule(a, 2);
+  return r == BODY_STRIP_128x64 || r == BODY_STRIP_128x64_KS2 ? 64 : r >= BODY_STRIP_64x128 && r <= BODY_STRIP_128x128_KS2 ? 128 : 0;
 }
 
 // ---- the per-family checks: SFA_OK with the launch's grid, or the refusal

@@ -7,6 +7,7 @@
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 #include <thread>
@@ -631,7 +632,145 @@ static void check_product() {
   EXPECT(product(1, 96, 96) == product(2, 96, 96) && product(1, 64, 96) == s64, "small maps: an outcome depends on the batch");
 }
 
-int main() {
+// ---------------------------------------------------------------- the body convs' rule table
+// conv_plan.h body_conv_rule on the sixteen residual-layer launches, layer li + 1 (li = 0..3), conv k = 2 block +
+// conv: as model.hip builds them for a B x H x W input, and as block.hip builds the two of one block for a caller's
+// B x h x w map (odd sizes round up at stride 2; the partial buffer only where the block is 512 wide).
+static ConvArgs model_body_conv(int B, int H, int W, int li, int k) {
+  const int planes = 64 << li, stride = li == 0 ? 1 : 2, ic = li == 0 ? 64 : planes / 2;
+  const int ih = (H / 4) >> (li > 0 ? li - 1 : 0), iw = (W / 4) >> (li > 0 ? li - 1 : 0), oh = ih / stride, ow = iw / stride;
+  ConvArgs a = k == 0 ? base_conv(B, ih, iw, ic, 3, stride, planes) : base_conv(B, oh, ow, planes, 3, 1, planes);
+  if (k == 1 && li > 0) {
+    a.nseg = 2;
+    a.kseg1 = 9 * planes;
+    a.Kpad = 9 * planes + ic;
+    make_seg(a.seg[1], P, B, ih, iw, ic, 1, stride, 0);
+  }
+  a.part = g_mem;
+  a.part_floats = (size_t)2 * B * (H / 32) * (W / 32) * 512;
+  return a;
+}
+
+static ConvArgs block_body_conv(int B, int h, int w, int li, int block, int c) {
+  const int planes = 64 << li, ds = block == 0 && li > 0, stride = ds ? 2 : 1, ic = ds ? planes / 2 : planes;
+  const int oh = (h + stride - 1) / stride, ow = (w + stride - 1) / stride;
+  ConvArgs a = c == 0 ? base_conv(B, h, w, ic, 3, stride, planes) : base_conv(B, oh, ow, planes, 3, 1, planes);
+  a.OH = oh;
+  a.OW = ow;
+  a.M = B * oh * ow;
+  if (c == 1 && ds) {
+    a.nseg = 2;
+    a.kseg1 = 9 * planes;
+    a.Kpad = 9 * planes + ic;
+    make_seg(a.seg[1], P, B, h, w, ic, 1, stride, 0);
+  }
+  if (planes >= 512) {
+    a.part = g_mem;
+    a.part_floats = (size_t)2 * a.M * planes;
+  }
+  return a;
+}
+
+// The tile and the slices each rule stands for, written out again: what strip_tile_bn and the launch must agree with.
+struct RuleTile { int fam, BM, BN, ks; };  // fam: 0 none, 1 conv_h3s, 2 conv_r3 (R3_BODY), 3 conv_h3
+static RuleTile rule_tile(BodyRule r) {
+  switch (r) {
+    case BODY_STRIP_128x64: return {1, 128, 64, 1};
+    case BODY_STRIP_64x128: return {1, 64, 128, 1};
+    case BODY_STRIP_128x64_KS2: return {1, 128, 64, 2};
+    case BODY_STRIP_128x128: return {1, 128, 128, 1};
+    case BODY_STRIP_128x128_KS2: return {1, 128, 128, 2};
+    case BODY_R3: return {2, 128, 128, 1};
+    case BODY_R3_KS2: return {2, 128, 128, 2};
+    case BODY_H3_256x64: return {3, 256, 64, 1};
+    case BODY_H3_128x64: return {3, 128, 64, 1};
+    case BODY_H3_128x128: return {3, 128, 128, 1};
+    case BODY_H3_128x128_KS2: return {3, 128, 128, 2};
+    default: return {0, 0, 0, 1};
+  }
+}
+
+// The chosen instance's own check on the launch as launch_conv_h makes it (ksplit from the rule).
+static int rule_check(const ConvArgs& a, BodyRule r, unsigned* grid) {
+  const RuleTile t = rule_tile(r);
+  ConvArgs b = a;
+  b.ksplit = t.ks;
+  if (t.fam == 1) return FRESH(conv_h3s_check(b, t.BM, t.BN, EPI_STD, grid));
+  if (t.fam == 2) return FRESH(conv_r3_check(b, t.BM, t.BN, EPI_STD, false, false, true, grid));
+  if (t.fam == 3) return FRESH(conv_h3_check(b, t.BM, t.BN, r == BODY_H3_128x64 ? 16 : 32, EPI_STD, 2, grid));
+  return SFA_E_UNSUPPORTED;
+}
+
+static const int kWalkMax = 2048;
+static long long g_first[BODY_RULE_COUNT][3];  // the smallest input (pixels, H, W) that reaches each rule
+
+static void check_body_rules() {
+  for (int r = 0; r < BODY_RULE_COUNT; ++r) g_first[r][0] = 0;
+  for (int H = 32; H <= kWalkMax; H += 32)
+    for (int W = 32; W <= kWalkMax; W += 32)
+      for (int li = 0; li < 4; ++li)
+        for (int k = 0; k < 4; ++k) {
+          const ConvArgs a1 = model_body_conv(1, H, W, li, k);
+          const BodyRule r = body_conv_rule(a1, 2);
+          const RuleTile t = rule_tile(r);
+          if (!g_first[r][0] || (long long)H * W < g_first[r][0]) g_first[r][0] = (long long)H * W, g_first[r][1] = H, g_first[r][2] = W;
+          // no intended fall-through: frames under 128 rows are given conv_h3 by the rule itself
+          for (int B : {1, 2}) {
+            const ConvArgs a = model_body_conv(B, H, W, li, k);
+            if (FRESH(conv_shape_check(a, EPI_STD, SFA_MATH_FP16X3)) != SFA_OK) continue;  // a batch run in passes
+            unsigned grid = 0;
+            const int rc = rule_check(a, body_conv_rule(a, 2), &grid);
+            EXPECT(rc == SFA_OK, "%d x %d x %d layer%d conv %d: %s refused by its check (%s)", B, H, W, li + 1, k, body_rule_name(r), g_err);
+            // split-K strips: one ticket word per output tile in the model's array (model.hip plan_bufs)
+            const long long tick_words = (long long)((B * (H / 32) * (W / 32) + 63) / 64) * (512 / 64);
+            if (rc == SFA_OK && t.fam == 1 && t.ks == 2)
+              EXPECT(grid / 2 <= tick_words, "%d x %d x %d layer%d conv %d: %u tiles, %lld ticket words", B, H, W, li + 1, k, grid / 2, tick_words);
+          }
+          EXPECT(t.fam != 0 && t.ks == (t.fam == 3 && (a1.Kpad / 32) % 2 ? 1 : pick_ksplit(a1)), "%d x %d layer%d conv %d: %s", H, W, li + 1, k, body_rule_name(r));
+          EXPECT(strip_tile_bn(a1) == (t.fam == 1 ? t.BN : 0), "%d x %d layer%d conv %d: strip_tile_bn %d, rule %s", H, W, li + 1, k,
+                 strip_tile_bn(a1), body_rule_name(r));
+          EXPECT(body_conv_rule(model_body_conv(181, H, W, li, k), 2) == r, "%d x %d layer%d conv %d: the rule depends on the batch", H, W, li + 1, k);
+          // the block operator's launch of the same conv takes the same rule
+          const int ih = (H / 4) >> (li > 0 ? li - 1 : 0), iw = (W / 4) >> (li > 0 ? li - 1 : 0);
+          const int bh = k < 2 ? ih : ih / (li > 0 ? 2 : 1), bw = k < 2 ? iw : iw / (li > 0 ? 2 : 1);
+          for (int B : {1, 2})
+            EXPECT(body_conv_rule(block_body_conv(B, bh, bw, li, k >> 1, k & 1), 2) == r, "%d x %d layer%d conv %d: block_forward takes another rule", H,
+                   W, li + 1, k);
+          // the one-product mode shares the table
+          EXPECT(body_conv_rule(a1, 1) == r, "%d x %d layer%d conv %d: SFA_MATH_FP16 takes another rule", H, W, li + 1, k);
+        }
+}
+
+// conv_plan_check --rules: "layer block conv H W -> rule" for the sixteen body convs at every input H x W (multiples of
+// 32 up to 2048); --block layer block B h w: the same two lines for block_forward on a B x h x w map.
+static int dump_rules() {
+  for (int H = 32; H <= kWalkMax; H += 32)
+    for (int W = 32; W <= kWalkMax; W += 32)
+      for (int li = 0; li < 4; ++li)
+        for (int k = 0; k < 4; ++k)
+          std::printf("%d %d %d %d %d -> %s\n", li + 1, k >> 1, (k & 1) + 1, H, W, body_rule_name(body_conv_rule(model_body_conv(1, H, W, li, k), 2)));
+  return 0;
+}
+
+static int dump_block(int layer, int block, int B, int h, int w) {
+  if (layer < 1 || layer > 4 || block < 0 || block > 1 || B < 1 || h < 1 || w < 1) return 2;
+  for (int c = 0; c < 2; ++c)
+    std::printf("%d %d %d %d %d -> %s\n", layer, block, c + 1, h, w, body_rule_name(body_conv_rule(block_body_conv(B, h, w, layer - 1, block, c), 2)));
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 2 && !std::strcmp(argv[1], "--rules")) return dump_rules();
+  if (argc >= 7 && (argc - 2) % 5 == 0 && !std::strcmp(argv[1], "--block")) {
+    for (int i = 2; i < argc; i += 5)
+      if (int rc = dump_block(std::atoi(argv[i]), std::atoi(argv[i + 1]), std::atoi(argv[i + 2]), std::atoi(argv[i + 3]), std::atoi(argv[i + 4]))) return rc;
+    return 0;
+  }
+  if (argc != 1) return 2;
+  check_body_rules();
+  for (int r = 1; r < BODY_RULE_COUNT; ++r)
+    if (g_first[r][0]) std::printf("body rule %-18s first at %lld x %lld\n", body_rule_name((BodyRule)r), g_first[r][1], g_first[r][2]);
+    else std::printf("body rule %-18s not reached up to %d x %d\n", body_rule_name((BodyRule)r), kWalkMax, kWalkMax);
   check_make_seg();
   check_families();
   check_stem_chunks();
