@@ -201,6 +201,20 @@ size_t sfa_state_floats_ex(const sfa_arch_ex* arch);
 size_t sfa_packed_floats_ex(const sfa_arch_ex* arch);
 int sfa_pack_weights_ex(const sfa_arch_ex* arch, const float* state, size_t state_floats, float* packed);
 
+/* Pack weights (device -> device): the bytes sfa_pack_weights(_ex) writes for the same state, written by
+ * kernels on `stream` from the state tensors where they live.  state[i] = the device pointer of entry i in
+ * sfa_state_entry(_ex) order (float32, contiguous), NULL exactly at the *.num_batches_tracked entries;
+ * count = sfa_state_count(_ex); packed_device = sfa_packed_floats(_ex) floats of device memory, 16-byte
+ * aligned, every byte of which is written (padding and alignment gaps as zeros).  Stream-ordered: no host
+ * synchronisation, no allocation, no memset; capturable in a HIP graph, which then holds the pointers.  A null
+ * or non-null pointer in the wrong slot, a wrong count, a pointer that is not memory of the current device and a
+ * misaligned packed_device are SFA_E_INVALID, and nothing is written.  A model handle over `packed_device`
+ * needs sfa_model_refresh_weight_images on the same stream afterwards (below). */
+int sfa_pack_weights_device(const sfa_arch* arch, const float* const* state, int count, float* packed_device,
+                            void* stream);
+int sfa_pack_weights_device_ex(const sfa_arch_ex* arch, const float* const* state, int count, float* packed_device,
+                               void* stream);
+
 /* A model handle references a device copy of the packed weights (caller-owned,
  * must outlive the handle).  No device memory is allocated.  The handle owns side
  * streams + events on the device current at creation: a forward on a stream of that
@@ -231,8 +245,8 @@ void sfa_model_destroy(sfa_model* model);
  * ANY later change of its contents, call sfa_model_refresh_weight_images(model, stream) before the next
  * forward; it rebuilds every image on `stream` (stream-ordered, no allocation, capturable) for this
  * handle and its twins.  A stale image cannot be detected.  A caller that updates weights in place and
- * cannot make that call turns the images off with SFA_OPT_W_IMAGES = 0.  (The Python model creates a new
- * handle from freshly packed weights whenever a parameter changes, heads_trainable() steps included.) */
+ * cannot make that call turns the images off with SFA_OPT_W_IMAGES = 0.  (The Python model makes that call after
+ * every sfa_pack_weights_device into the buffer of a handle it keeps, optimiser steps included.) */
 int sfa_model_refresh_weight_images(sfa_model* model, void* stream);
 /* Bytes of device memory the handle's derived weight images of the detection heads take (shared with its
  * twins); 0: it has none. */

@@ -34,6 +34,9 @@ void set_error(const char* fmt, ...);
     }                                                                                      \
   } while (0)
 
+// [p, p + bytes) is device memory of the current device, inside one allocation (pack.hip).
+bool device_memory_covers(const void* p, size_t bytes);
+
 // CU count of the device a stream runs on (persistent-grid sizing), cached per device: each slot is
 // written with the device's own answer, so concurrent first calls and launches on several devices
 // agree; 256 (MI355X) when the query fails.

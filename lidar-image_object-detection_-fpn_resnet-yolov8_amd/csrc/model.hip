@@ -19,6 +19,7 @@
 #include "aux_kernels.h"
 #include "conv.h"
 #include "conv_plan.h"
+#include "pack_plan.h"
 
 namespace sfa {
 
@@ -33,20 +34,7 @@ void set_error(const char* fmt, ...) {
   g_err = buf;
 }
 
-struct Entry {
-  std::string name;
-  std::vector<int64_t> shape;
-};
-
-static int64_t numel(const Entry& e) {
-  int64_t n = 1;
-  for (auto s : e.shape) n *= s;
-  return n;
-}
-
-static const int kFpnC[3] = {256, 128, 64};
-
-static int check_arch(const sfa_arch* a, int backbone = SFA_BACKBONE_KFPN) {
+int check_arch(const sfa_arch* a, int backbone) {
   SFA_CHECK_ARG(a != nullptr, "arch is null");
   if (a->num_layers != 18) {
     set_error("only %s is implemented (got %d layers)", backbone == SFA_BACKBONE_DECONV ? "resnet_18" : "fpn_resnet_18",
@@ -69,180 +57,12 @@ static int check_arch(const sfa_arch* a, int backbone = SFA_BACKBONE_KFPN) {
 }
 
 // The extended descriptor: the base checks of its family; reserved words zero, a known backbone.
-static int check_arch_ex(const sfa_arch_ex* x) {
+int check_arch_ex(const sfa_arch_ex* x) {
   SFA_CHECK_ARG(x != nullptr, "arch is null");
   SFA_CHECK_ARG(x->backbone == SFA_BACKBONE_KFPN || x->backbone == SFA_BACKBONE_DECONV, "unknown backbone %d",
                 x->backbone);
   for (int r : x->reserved) SFA_CHECK_ARG(r == 0, "sfa_arch_ex.reserved must be zero");
   return check_arch(&x->base, x->backbone);
-}
-
-static std::vector<int> sorted_heads(const sfa_arch* a) {
-  std::vector<int> idx(a->num_heads);
-  for (int j = 0; j < a->num_heads; ++j) idx[j] = j;
-  std::sort(idx.begin(), idx.end(), [&](int x, int y) {
-    return std::string(a->head_names[x]) < std::string(a->head_names[y]);
-  });
-  return idx;
-}
-
-// nn.Module registration order of PoseResNet (fpn_resnet.py:114-151, 42-53; resnet.py:117-158 for
-// the deconv family: deconv_layers.{0,3,6} ConvTranspose2d (Cin, 256, 4, 4), .{1,4,7} BatchNorm, then
-// the heads under their plain names).
-static std::vector<Entry> state_layout(const sfa_arch* a, int backbone = SFA_BACKBONE_KFPN) {
-  std::vector<Entry> v;
-  auto bn = [&](const std::string& p, int64_t c) {
-    v.push_back({p + ".weight", {c}});
-    v.push_back({p + ".bias", {c}});
-    v.push_back({p + ".running_mean", {c}});
-    v.push_back({p + ".running_var", {c}});
-    v.push_back({p + ".num_batches_tracked", {}});
-  };
-  v.push_back({"conv1.weight", {64, 3, 7, 7}});
-  bn("bn1", 64);
-  int inplanes = 64;
-  for (int li = 1; li <= 4; ++li) {
-    const int planes = 64 << (li - 1);
-    for (int bi = 0; bi < 2; ++bi) {
-      const std::string p = "layer" + std::to_string(li) + "." + std::to_string(bi);
-      const int cin = bi == 0 ? inplanes : planes;
-      v.push_back({p + ".conv1.weight", {planes, cin, 3, 3}});
-      bn(p + ".bn1", planes);
-      v.push_back({p + ".conv2.weight", {planes, planes, 3, 3}});
-      bn(p + ".bn2", planes);
-      if (bi == 0 && (li > 1)) {
-        v.push_back({p + ".downsample.0.weight", {planes, inplanes, 1, 1}});
-        bn(p + ".downsample.1", planes);
-      }
-    }
-    inplanes = planes;
-  }
-  const auto order = sorted_heads(a);
-  if (backbone == SFA_BACKBONE_DECONV) {
-    for (int i = 0; i < 3; ++i) {
-      v.push_back({"deconv_layers." + std::to_string(3 * i) + ".weight", {i == 0 ? 512 : 256, 256, 4, 4}});
-      bn("deconv_layers." + std::to_string(3 * i + 1), 256);
-    }
-    for (int j : order) {
-      const std::string p = a->head_names[j];
-      v.push_back({p + ".0.weight", {a->head_conv, 256, 3, 3}});
-      v.push_back({p + ".0.bias", {a->head_conv}});
-      v.push_back({p + ".2.weight", {a->head_channels[j], a->head_conv, 1, 1}});
-      v.push_back({p + ".2.bias", {a->head_channels[j]}});
-    }
-    return v;
-  }
-  const int up_out[3] = {256, 128, 64}, up_in[3] = {768, 384, 192};
-  for (int i = 0; i < 3; ++i) {
-    const std::string p = "conv_up_level" + std::to_string(i + 1);
-    v.push_back({p + ".weight", {up_out[i], up_in[i], 1, 1}});
-    v.push_back({p + ".bias", {up_out[i]}});
-  }
-  for (int f = 0; f < 3; ++f)
-    for (int j : order) {
-      const std::string p = "fpn" + std::to_string(f) + "_" + a->head_names[j];
-      v.push_back({p + ".0.weight", {a->head_conv, kFpnC[f], 3, 3}});
-      v.push_back({p + ".0.bias", {a->head_conv}});
-      v.push_back({p + ".2.weight", {a->head_channels[j], a->head_conv, 1, 1}});
-      v.push_back({p + ".2.bias", {a->head_channels[j]}});
-    }
-  return v;
-}
-
-// ----------------------------------------------------------- packed layout
-// Offsets in floats into the packed buffer.  wx: the same weights split into three
-// bf16 terms [3][N][Kpad] for the bf16x6 kernels (conv_x6_kernel.h); wh / winv: the
-// fp16x3 form, W[n][k] * 2^e[n] as two fp16 terms [2][N][Kpad] and winv[n] = 2^-e[n].
-struct PConv {
-  size_t w, b, wx, wh, winv;
-  int N, K, Kpad;
-};
-struct PHeads {
-  size_t w3, b3, w1, b1, wx, wh, winv;
-  int N, K;
-};
-// One transposed conv (deconv_h3_kernel.h): w = the four phase matrices [4][N][K] f32, K = 4 C in
-// (dy, dx, c) order, BN scale folded in; b = the BN shift [N]; wh = [4][2][N][K] fp16 terms and
-// winv = [4][N], split per phase and row.
-struct PDeconv {
-  size_t w, b, wh, winv;
-  int N, C, K;
-};
-struct Plan {
-  int backbone;
-  PConv stem;
-  PConv blk[4][2][2];  // [layer][block][conv1, conv2(+downsample)]
-  PConv fpn[3];        // KFPN
-  PDeconv dec[3];      // deconv family
-  PHeads heads[3];     // KFPN: per level; deconv family: heads[0] alone (256 channels in)
-  size_t total;
-};
-
-static Plan make_plan(const sfa_arch* a, int backbone = SFA_BACKBONE_KFPN) {
-  Plan p;
-  memset(&p, 0, sizeof p);
-  p.backbone = backbone;
-  size_t cur = 0;
-  auto take = [&](size_t n) {
-    const size_t o = cur;
-    cur = align_up(cur + n, 16);
-    return o;
-  };
-  auto conv = [&](int N, int K) {
-    PConv c;
-    c.N = N;
-    c.K = K;
-    c.Kpad = (int)align_up(K, 16);
-    c.w = take((size_t)N * c.Kpad);
-    c.b = take(N);
-    c.wx = take(((size_t)3 * N * c.Kpad + 1) / 2);
-    c.wh = take((size_t)N * c.Kpad);
-    c.winv = take(N);
-    return c;
-  };
-  p.stem = conv(64, 49 * 4);
-  int inplanes = 64;
-  for (int li = 0; li < 4; ++li) {
-    const int planes = 64 << li;
-    for (int bi = 0; bi < 2; ++bi) {
-      const int cin = bi == 0 ? inplanes : planes;
-      const bool ds = bi == 0 && li > 0;
-      p.blk[li][bi][0] = conv(planes, 9 * cin);
-      p.blk[li][bi][1] = conv(planes, 9 * planes + (ds ? inplanes : 0));
-    }
-    inplanes = planes;
-  }
-  const bool deconv = backbone == SFA_BACKBONE_DECONV;
-  if (deconv) {
-    for (int i = 0; i < 3; ++i) {
-      PDeconv& d = p.dec[i];
-      d.N = 256;
-      d.C = i == 0 ? 512 : 256;
-      d.K = 4 * d.C;
-      d.w = take((size_t)4 * d.N * d.K);
-      d.b = take(d.N);
-      d.wh = take((size_t)4 * d.N * d.K);
-      d.winv = take((size_t)4 * d.N);
-    }
-  } else {
-    p.fpn[0] = conv(256, 768);
-    p.fpn[1] = conv(128, 384);
-    p.fpn[2] = conv(64, 192);
-  }
-  for (int f = 0; f < (deconv ? 1 : 3); ++f) {
-    PHeads& h = p.heads[f];
-    h.N = a->num_heads * a->head_conv;
-    h.K = 9 * kFpnC[f];
-    h.w3 = take((size_t)h.N * h.K);
-    h.b3 = take(h.N);
-    h.w1 = take((size_t)a->num_heads * 4 * 64);
-    h.b1 = take((size_t)a->num_heads * 4);
-    h.wx = take(((size_t)3 * h.N * h.K + 1) / 2);
-    h.wh = take((size_t)h.N * h.K);
-    h.winv = take(h.N);
-  }
-  p.total = cur;
-  return p;
 }
 
 struct StateView {
@@ -463,19 +283,7 @@ static int fill_body_wimages(const sfa_model* m, hipStream_t st) {
 // current device and cover the plan (a handle over anything else, or created without a device, keeps the
 // row-major kernels); built on the null stream and waited for, so a forward on any stream finds them.
 static bool weights_on_device(const sfa_model* m) {
-  hipPointerAttribute_t at;
-  memset(&at, 0, sizeof at);
-  void* base = nullptr;
-  size_t range = 0;
-  int dev = -1;
-  const bool device_weights =
-      hipGetDevice(&dev) == hipSuccess && hipPointerGetAttributes(&at, m->w) == hipSuccess &&
-      at.type == hipMemoryTypeDevice && at.device == dev &&
-      hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &range, const_cast<float*>(m->w)) == hipSuccess &&
-      (reinterpret_cast<uintptr_t>(m->w) & 15) == 0 &&
-      (size_t)(reinterpret_cast<const char*>(m->w) - static_cast<const char*>(base)) + m->plan.total * 4 <= range;
-  if (!device_weights) (void)hipGetLastError();
-  return device_weights;
+  return (reinterpret_cast<uintptr_t>(m->w) & 15) == 0 && sfa::device_memory_covers(m->w, m->plan.total * 4);
 }
 
 static void make_wimages(sfa_model* m) {

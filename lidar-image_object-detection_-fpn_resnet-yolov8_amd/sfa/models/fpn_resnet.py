@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from sfa_hip import _lib
 from sfa_hip import dropin as _dropin
 from sfa_hip.runtime import (KfpnEngine, block_train_forward, block_train_grad, bn_unfold_grad, kfpn_combine_grad, kfpn_heads,
-                             pack_state_dict)
+                             device_packable, pack_state_dict, state_entries)
 
 BN_MOMENTUM = 0.1
 
@@ -42,6 +42,10 @@ def _bump_struct_gen(*_args, **_kw):
 torch.nn.modules.module.register_module_parameter_registration_hook(_bump_struct_gen)
 torch.nn.modules.module.register_module_buffer_registration_hook(_bump_struct_gen)
 torch.nn.modules.module.register_module_module_registration_hook(_bump_struct_gen)
+
+# Private switch of the tests and the timing tool: False sends every weight change through the host pack
+# (pack_state_dict + a new engine), the route a model whose state is not float32 on the GPU always takes.
+_DEVICE_REPACK = [True]
 
 model_urls = {
     "resnet18": "https://download.pytorch.org/models/resnet18-5c106cde.pth",
@@ -121,10 +125,12 @@ class _TrainableHeadsForward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, in_layout, x, *params):
+        ctx.save_for_backward(*params)  # the head weights backward reads again: a stale backward raises
         return _trainable_forward(ctx, eng, in_layout, x)
 
     @staticmethod
     def backward(ctx, *grads):
+        _ = ctx.saved_tensors
         _, flat = _trainable_backward(ctx, grads)
         return (None, None, None) + tuple(t if need else None for t, need in zip(flat, ctx.needs_input_grad[3:]))
 
@@ -140,12 +146,12 @@ class _LevelHeads(torch.autograd.Function):
         with torch.cuda.device(x.device):
             ys = eng.heads_forward(level, xn)
         ctx.eng, ctx.level = eng, level
-        ctx.save_for_backward(xn)
+        ctx.save_for_backward(xn, *params)
         return tuple(ys[n] for n, _ in eng.heads)
 
     @staticmethod
     def backward(ctx, *grads):
-        eng, level, (xn,) = ctx.eng, ctx.level, ctx.saved_tensors
+        eng, level, xn = ctx.eng, ctx.level, ctx.saved_tensors[0]
         B, h, w, _ = xn.shape
         with torch.cuda.device(xn.device):
             g = {n: (gr.contiguous() if gr is not None else torch.zeros((B, c, h, w), device=xn.device))
@@ -174,13 +180,13 @@ class _NeckFromLayers(torch.autograd.Function):
         with torch.cuda.device(l4.device):
             u2, u3, u4 = eng.neck_forward(*ls)
         ctx.eng = eng
-        ctx.save_for_backward(*ls, u2, u3)
+        ctx.save_for_backward(*ls, u2, u3, *params)
         return tuple(t.permute(0, 3, 1, 2) for t in (u2, u3, u4))
 
     @staticmethod
     def backward(ctx, g2, g3, g4):
         eng = ctx.eng
-        l1, l2, l3, l4, u2, u3 = ctx.saved_tensors
+        l1, l2, l3, l4, u2, u3 = ctx.saved_tensors[:6]
         need = ctx.needs_input_grad
         if not any(need[1:]):
             return (None,) * len(need)
@@ -205,13 +211,13 @@ class _BlockFromInput(torch.autograd.Function):
         with torch.cuda.device(x.device):
             mid, y = eng.block_forward(layer, block, xn)
         ctx.eng, ctx.layer, ctx.block, ctx.mods = eng, layer, block, mods
-        ctx.save_for_backward(xn, mid, y)
+        ctx.save_for_backward(xn, mid, y, *params, *[t for _, bn in mods for t in (bn.running_mean, bn.running_var)])
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
         eng, mods = ctx.eng, ctx.mods
-        xn, mid, y = ctx.saved_tensors
+        xn, mid, y = ctx.saved_tensors[:3]
         need = ctx.needs_input_grad
         pneed = [need[5 + 3 * i:8 + 3 * i] for i in range(len(mods))]
         if not need[4] and not any(any(n) for n in pneed):
@@ -280,13 +286,13 @@ class _StemFromImage(torch.autograd.Function):
         with torch.cuda.device(x.device):
             a, pooled = eng.stem_forward(x)
         ctx.eng, ctx.conv, ctx.bn = eng, conv, bn
-        ctx.save_for_backward(x, a)
+        ctx.save_for_backward(x, a, *params, bn.running_mean, bn.running_var)
         return pooled.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gp):
         eng, conv, bn = ctx.eng, ctx.conv, ctx.bn
-        x, a = ctx.saved_tensors
+        x, a = ctx.saved_tensors[:2]
         need = ctx.needs_input_grad
         n = need[4:7]
         if not need[3] and not any(n):
@@ -312,10 +318,13 @@ class _TrainableNeckForward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, in_layout, x, *params):
+        # the head weights and, through sfa_model_neck_grad's data gradients, the neck convs' weights are read again
+        ctx.save_for_backward(*params)
         return _trainable_forward(ctx, eng, in_layout, x)
 
     @staticmethod
     def backward(ctx, *grads):
+        _ = ctx.saved_tensors
         need = ctx.needs_input_grad[3:]
         dp, flat = _trainable_backward(ctx, grads, need[:6])
         return (None, None, None) + tuple(t if n else None for t, n in zip(dp + flat, need))
@@ -389,15 +398,39 @@ class PoseResNet(nn.Module):
         _bump_struct_gen()
         return out
 
+    def _device_route(self, tensors, device) -> bool:
+        return _DEVICE_REPACK[0] and len(tensors) == state_entries(self._arch) and device_packable(tensors, device)
+
     def _engine(self, device) -> KfpnEngine:
+        """The engine of ``device``.  When only values changed since the last call (the same structure, every
+        data_ptr unchanged, new versions) and the state is contiguous float32 on the engine's device, the live
+        engine is repacked in place on the current stream (KfpnEngine.repack) and stays the same object: its
+        options, workspaces, twins and captured graphs survive an optimiser step.  Anything else (a CPU-resident
+        model, another dtype, a moved or re-registered tensor) drops the engines and packs on the host."""
+        walked = self._state_tensors
         sig = self._signature()
+        tensors = self._state_tensors[1]
         if sig != self._sig:
-            self._engines = {}
-            self._sig = sig
+            # nothing is kept while a repack can still fail: an exception leaves no engine and no signature, so the
+            # next call packs again from scratch instead of returning half-written weights
+            old, engines = self._sig, self._engines
+            self._sig, self._engines = None, {}
+            same_tensors = walked is self._state_tensors or (
+                walked is not None and len(walked[1]) == len(tensors) and all(a is b for a, b in zip(walked[1], tensors)))
+            keep = (old is not None and same_tensors and len(old) == len(sig)
+                    and all(a[0] == b[0] for a, b in zip(old, sig)))
+            live = {}
+            for dev, eng in (engines.items() if keep else ()):
+                if self._device_route(tensors, dev):
+                    live[dev] = eng.repack(tensors)
+            self._sig, self._engines = sig, live
         eng = self._engines.get(device)
         if eng is None:
-            packed = pack_state_dict(self.state_dict(), self._arch)
-            eng = KfpnEngine(self._arch, packed, device, math=self._math)
+            if self._device_route(tensors, device):
+                eng = KfpnEngine.from_state(self._arch, tensors, device, math=self._math)
+            else:
+                packed = pack_state_dict(self.state_dict(), self._arch)
+                eng = KfpnEngine(self._arch, packed, device, math=self._math)
             self._engines[device] = eng
         return eng
 

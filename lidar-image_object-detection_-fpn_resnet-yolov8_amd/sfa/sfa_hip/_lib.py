@@ -118,6 +118,8 @@ _PROTOS["sfa_model_get_option"] = (_c_int, [_vp, _c_int, ctypes.POINTER(_c_int)]
 PROBE_HEADS, PROBE_SERIAL = 1, 2
 _PROTOS["sfa_model_create_twin"] = (_c_int, [_vp, ctypes.POINTER(_vp)])
 _PROTOS["sfa_model_refresh_weight_images"] = (_c_int, [_vp, _vp])
+_PROTOS["sfa_pack_weights_device"] = (_c_int, [ctypes.POINTER(SfaArch), ctypes.POINTER(_vp), _c_int, _vp, _vp])
+_PROTOS["sfa_pack_weights_device_ex"] = (_c_int, [ctypes.POINTER(SfaArchEx), ctypes.POINTER(_vp), _c_int, _vp, _vp])
 _PROTOS["sfa_model_weight_image_bytes"] = (_c_size, [_vp])
 _PROTOS["sfa_model_body_weight_image_bytes"] = (_c_size, [_vp])
 _PROTOS["sfa_model_set_probe"] = (_c_int, [_vp, _c_int])

@@ -80,18 +80,96 @@ def pack_state_dict(state: dict, arch) -> np.ndarray:
     return packed
 
 
+_LAYOUTS = {}  # descriptor bytes -> state layout (the descriptor is a plain struct)
+
+
+def _cached_layout(arch):
+    key = (type(arch).__name__, bytes(arch))
+    lay = _LAYOUTS.get(key)
+    if lay is None:
+        lay = _LAYOUTS[key] = _lib.state_layout(arch)
+    return lay
+
+
+def state_entries(arch) -> int:
+    """Entries of the reference state_dict of this descriptor (sfa_state_count(_ex))."""
+    return len(_cached_layout(arch))
+
+
+def device_packable(tensors, device) -> bool:
+    """Every float state tensor is a contiguous float32 tensor on ``device`` (what sfa_pack_weights_device reads)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return False
+    if device.index is None:  # "cuda": the current device, as a tensor's .device names it
+        device = torch.device("cuda", torch.cuda.current_device())
+    return all(
+        not t.is_floating_point() or (t.dtype == torch.float32 and t.device == device and t.is_contiguous())
+        for t in tensors)
+
+
+def _pack_on_device(arch, tensors, packed: torch.Tensor, stream: int):
+    """sfa_pack_weights_device(_ex) of the state ``tensors`` (layout order) into ``packed`` on ``stream``."""
+    layout = _cached_layout(arch)
+    if len(tensors) != len(layout):
+        raise ValueError(f"state has {len(tensors)} tensors, the layout {len(layout)}")
+    table = (ctypes.c_void_p * len(layout))()
+    for i, ((name, shape), t) in enumerate(zip(layout, tensors)):
+        if name.endswith("num_batches_tracked"):
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != packed.device:
+            raise ValueError(f"{name}: the device pack reads contiguous float32 tensors on {packed.device}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != {tuple(shape)}")
+        table[i] = t.data_ptr()
+    check(_lib.arch_fn(arch, "sfa_pack_weights_device")(ctypes.byref(arch), table, len(layout), packed.data_ptr(), stream),
+          "sfa_pack_weights_device")
+
+
 class KfpnEngine:
     """A device copy of the packed weights + an sfa_model handle + workspace cache.  ``arch`` is an
     SfaArch (fpn_resnet_18) or an SfaArchEx (either family: BACKBONE_DECONV is the plain resnet_18, which
     runs fp16x3 only and has no side streams)."""
 
     def __init__(self, arch, packed_host: np.ndarray, device, math=None, side_streams: bool = True):
+        self._create(arch, torch.from_numpy(packed_host).to(torch.device(device)), device, math, side_streams)
+
+    @classmethod
+    def from_state(cls, arch, tensors, device, math=None) -> "KfpnEngine":
+        """An engine from the state tensors where they live, without the host round trip: ``tensors`` is the
+        state list in layout order (``_lib.state_layout(arch)``; contiguous float32 tensors on ``device``, the
+        num_batches_tracked entries are skipped).  The packed buffer is allocated on the device and filled by
+        sfa_pack_weights_device (the bytes of pack_state_dict); one wait, then sfa_model_create."""
+        device = torch.device(device)
+        eng = object.__new__(cls)
+        n = int(_lib.arch_fn(arch, "sfa_packed_floats")(ctypes.byref(arch)))
+        if n == 0:
+            check(-1, "sfa_packed_floats")
+        with torch.cuda.device(device):
+            packed = torch.empty(n, dtype=torch.float32, device=device)
+            _pack_on_device(arch, tensors, packed, _lib.stream_ptr(device))
+            torch.cuda.current_stream(device).synchronize()
+        eng._create(arch, packed, device, math, True)
+        return eng
+
+    def repack(self, tensors, stream: int = None) -> "KfpnEngine":
+        """Pack the state ``tensors`` (layout order, as from_state) into ``self.weights`` in place and rebuild the
+        derived weight images, on ``stream`` (default: the current one): stream-ordered and capturable.  The
+        handle, its twins (they share the buffer and the images), the cached workspaces and graphs captured over
+        this engine stay valid and read the new weights from then on."""
+        st = _lib.stream_ptr(self.device) if stream is None else stream
+        with torch.cuda.device(self.device):
+            _pack_on_device(self.arch, tensors, self.weights, st)
+        self.refresh_weight_images(st)
+        return self
+
+    def _create(self, arch, weights: torch.Tensor, device, math, side_streams):
         self.arch = arch
         self.deconv = _lib.is_ex(arch) and arch.backbone == _lib.BACKBONE_DECONV
         self.device = torch.device(device)
         self.heads = [(arch.head_names[j].value.decode(), int(arch.head_channels[j]))
                       for j in range(arch.num_heads)]
-        self.weights = torch.from_numpy(packed_host).to(self.device)
+        self.weights = weights
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):  # the model's side stream lives on this device
             check(_lib.arch_fn(arch, "sfa_model_create")(ctypes.byref(arch), self.weights.data_ptr(), ctypes.byref(h)),

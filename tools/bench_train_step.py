@@ -23,10 +23,20 @@ channel), dW' 64 x 192 per conv pixel (147 columns padded to three tiles), dx 3 
     gradient  per BatchNorm: the reduce reads g, the mask and z, the apply reads them again and writes dZ; dW2 (dZ2,
               mid), dA (dZ2, mid, dA written), dW1 (dZ1, X), dx (dZ1, [dZd | gy, y], dx written), dWd (dZd, X)
   Arithmetic: 2 Cout 9 Cin (+ Cout Cin) flops per output pixel forward, twice that for the gradient (dW and the data
-  gradient of each convolution), against the f32 MFMA rate."""
+  gradient of each convolution), against the f32 MFMA rate.
+
+  weight update (--weight-update-only prints these alone): weight_update_us = KfpnEngine.repack (sfa_pack_weights_device
+  + sfa_model_refresh_weight_images), the median of 50 graph replays, beside the time of its byte traffic at the copy
+  rate: the state read once, the packed buffer and both image buffers written, the fp16 terms the image build reads
+  (the size of the images again).  weight_update_host_us = the host route, eager: pack_state_dict(model.state_dict())
+  + KfpnEngine(...) + one synchronise, the median of 5.  weight_update_eager_us = the device route eager, as a step
+  loop pays it: _engine() after an in-place change plus one synchronise, weight_update_eager_host_us its part until the
+  call returns (the pointer table, the argument checks, the launches), the median of 5.  The train step is followed by torch.optim.Adam's step (lr 1e-3,
+  no weight decay) and the next forward's _engine(), wall-clock with a synchronise each, as fields of their own."""
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -50,7 +60,8 @@ def train_step_us(gpu, sd, batch):
     labels, offsets = synthetic.synthetic_labels(batch, seed=2)
     tg = runtime.TargetBuilder(gpu, hm_size=(H // 4, H // 4))(labels, offsets)
     crit = Compute_Loss(gpu, differentiable=True)
-    ts = []
+    opt = torch.optim.Adam(m.parameters(), lr=1e-3, weight_decay=0)
+    ts, ts_opt, ts_eng = [], [], []
     for it in range(6):
         for p in m.parameters():
             p.grad = None
@@ -60,9 +71,61 @@ def train_step_us(gpu, sd, batch):
         total.backward()
         b.record()
         b.synchronize()
+        t0 = time.perf_counter()
+        opt.step()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        m._engine(gpu)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
         if it:
             ts.append(a.elapsed_time(b) * 1e3)
-    return float(np.median(ts))
+            ts_opt.append((t1 - t0) * 1e6)
+            ts_eng.append((t2 - t1) * 1e6)
+    return float(np.median(ts)), float(np.median(ts_opt)), float(np.median(ts_eng))
+
+
+def weight_update_rows(gpu, sd, arch, copy_rate):
+    from models.fpn_resnet import get_pose_net
+    layout = _lib.state_layout(arch)
+    tensors = [torch.zeros((), dtype=torch.int64, device=gpu) if n.endswith("num_batches_tracked")
+               else torch.from_numpy(np.asarray(sd[n], np.float32)).to(gpu) for n, _ in layout]
+    eng = runtime.KfpnEngine.from_state(arch, tensors, gpu)
+    dev = replay_us(lambda: eng.repack(tensors), gpu)
+    pack_only = replay_us(lambda: runtime._pack_on_device(arch, tensors, eng.weights, _lib.stream_ptr(gpu)), gpu)
+    state_bytes = 4 * sum(t.numel() for t in tensors if t.is_floating_point())
+    images = eng.weight_image_bytes() + eng.body_weight_image_bytes()
+    traffic = state_bytes + 4 * eng.weights.numel() + 2 * images
+    m = get_pose_net(18, dict(runtime.DEFAULT_HEADS), 64, False)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+    m = m.to(gpu).eval()
+    host = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e = runtime.KfpnEngine(arch, runtime.pack_state_dict(m.state_dict(), arch), gpu)
+        torch.cuda.synchronize()
+        host.append((time.perf_counter() - t0) * 1e6)
+        del e
+    # the same update eager, as a step loop pays it: _engine() after an in-place change, the host's share (the pointer
+    # table, the argument checks, the launches) until the call returns and the whole until the device is done
+    kept = m._engine(gpu)
+    eager_host, eager = [], []
+    for _ in range(6):
+        with torch.no_grad():
+            m.conv1.weight.add_(0.0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        assert m._engine(gpu) is kept
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        eager_host.append((t1 - t0) * 1e6)
+        eager.append((time.perf_counter() - t0) * 1e6)
+    return {"weight_update_eager_us": round(float(np.median(eager[1:])), 1),
+            "weight_update_eager_host_us": round(float(np.median(eager_host[1:])), 1),
+            "weight_update_us": round(dev, 1), "weight_pack_only_us": round(pack_only, 1),
+            "weight_update_traffic_us": round(traffic / copy_rate * 1e6, 1), "weight_update_bytes": traffic,
+            "weight_update_host_us": round(float(np.median(host)), 1)}
 
 
 def block_rows(gpu, eng, copy_rate):
@@ -114,6 +177,10 @@ def main():
     src, dst = torch.empty(1 << 28, dtype=torch.uint8, device=gpu), torch.empty(1 << 28, dtype=torch.uint8, device=gpu)
     copy_rate = 2 * src.numel() / (replay_us(lambda: dst.copy_(src), gpu) * 1e-6)  # read + write bytes per second
     del src, dst
+    if "--weight-update-only" in sys.argv:
+        print(json.dumps({"replays": REPLAYS, "copy_GBps": round(copy_rate / 1e9, 1),
+                          **weight_update_rows(gpu, sd, arch, copy_rate)}))
+        return
     if "--blocks-only" in sys.argv:
         print(json.dumps({"frames": B, "replays": REPLAYS, "copy_GBps": round(copy_rate / 1e9, 1),
                           "mfma_f32_TFLOPs": MFMA_F32_FLOPS / 1e12, "blocks": block_rows(gpu, eng, copy_rate)}))
@@ -153,11 +220,14 @@ def main():
     while batch >= 1:
         torch.cuda.empty_cache()
         try:
-            out["train_step_us"] = round(train_step_us(gpu, sd, batch), 1)
+            step, opt_us, eng_us = train_step_us(gpu, sd, batch)
+            out["train_step_us"], out["optimizer_step_us"], out["engine_update_us"] = round(step, 1), round(opt_us, 1), round(eng_us, 1)
             break
         except torch.cuda.OutOfMemoryError:
             batch //= 2
     out["train_step_frames"] = batch
+    torch.cuda.empty_cache()
+    out.update(weight_update_rows(gpu, sd, arch, copy_rate))
     print(json.dumps(out))
 
 
