@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(512) heads_dhidden_kernel(HgHeads t, const flo
   }
 }
 
-// The level's fp16x3 weight terms [2][M][K] (model.hip split_terms_h3) cut into [2][Na][K] and [2][M - Na][K], the
+// The level's fp16x3 weight terms [2][M][K] (pack_row.h pack_fp16_terms) cut into [2][Na][K] and [2][M - Na][K], the
 // form a convolution over those columns reads (its low terms follow its own high terms).  32-bit words, Kw = K / 2.
 // grid (ceil(2 M Kw / 256)), block (256)
 __global__ void __launch_bounds__(256) heads_terms_cut_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dstA,
@@ -269,7 +269,7 @@ __global__ void __launch_bounds__(256) heads_wgrad_fold_kernel(HgHeads t, const 
 // kHgDgCin input channels, K = (o, tap) = 9 M, all of it walked by this one workgroup (2 x 2 waves of 32 x 32, one
 // 16-register accumulator each): no split-K, no partials, every element of dX written once by one lane.  Lane (r, k)
 // takes dA[pixel r shifted by the flipped tap][o + k] and W1[o + k][tap][i + r]; w3 is [o][tap = ky * 3 + kx][i]
-// (model.hip put_conv), so the W1 rows are the B operand as they lie.  Per step of kHgDgSlice hidden channels the
+// (pack_plan.h PACK_CONV), so the W1 rows are the B operand as they lie.  Per step of kHgDgSlice hidden channels the
 // workgroup stages the 3 x (kHgDgPix + 2) pixel window of dA, transposed to [o][row][pixel] so that the 32 pixels
 // of a half-wave read 32 consecutive words, and the W1 slice [o][tap][i]: 12,672 + 36,864 = 49,536 bytes of LDS.
 // The next step's global loads are issued into registers before the step's 72 MFMAs per wave.

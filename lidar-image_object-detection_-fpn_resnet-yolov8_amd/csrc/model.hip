@@ -1,6 +1,6 @@
-// FPN-ResNet-18 (KFPN) and plain ResNet-18 (deconv) models: reference state_dict layout, host-side
-// weight packing (BatchNorm folding + OHWI re-layout) and the forward orchestration.  The two
-// families (sfa_backbone) share the stem and the residual layers; what follows layer4 differs.
+// FPN-ResNet-18 (KFPN) and plain ResNet-18 (deconv) models: the model handle, its options, the buffer plan and
+// the forward orchestration (the state layout and the weight pack: pack.hip).  The two families (sfa_backbone)
+// share the stem and the residual layers; what follows layer4 differs.
 //
 // Reference: models/fpn_resnet.py:112-301 (PoseResNet, BasicBlock, get_pose_net),
 //            models/resnet.py:115-284 (the plain PoseResNet: three transposed convs, one head level),
@@ -9,8 +9,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <cstring>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -32,120 +30,6 @@ void set_error(const char* fmt, ...) {
   vsnprintf(buf, sizeof buf, fmt, ap);
   va_end(ap);
   g_err = buf;
-}
-
-int check_arch(const sfa_arch* a, int backbone) {
-  SFA_CHECK_ARG(a != nullptr, "arch is null");
-  if (a->num_layers != 18) {
-    set_error("only %s is implemented (got %d layers)", backbone == SFA_BACKBONE_DECONV ? "resnet_18" : "fpn_resnet_18",
-              a->num_layers);
-    return SFA_E_UNSUPPORTED;
-  }
-  if (a->head_conv != 64) {
-    set_error("only head_conv = 64 is implemented (got %d)", a->head_conv);
-    return SFA_E_UNSUPPORTED;
-  }
-  SFA_CHECK_ARG(a->num_heads >= 1 && a->num_heads <= SFA_MAX_HEADS, "num_heads %d out of range",
-                a->num_heads);
-  for (int j = 0; j < a->num_heads; ++j) {
-    SFA_CHECK_ARG(a->head_channels[j] >= 1 && a->head_channels[j] <= 4,
-                  "head %d: channels %d out of [1, 4]", j, a->head_channels[j]);
-    SFA_CHECK_ARG(strnlen(a->head_names[j], 32) > 0 && strnlen(a->head_names[j], 32) < 32,
-                  "head %d: bad name", j);
-  }
-  return SFA_OK;
-}
-
-// The extended descriptor: the base checks of its family; reserved words zero, a known backbone.
-int check_arch_ex(const sfa_arch_ex* x) {
-  SFA_CHECK_ARG(x != nullptr, "arch is null");
-  SFA_CHECK_ARG(x->backbone == SFA_BACKBONE_KFPN || x->backbone == SFA_BACKBONE_DECONV, "unknown backbone %d",
-                x->backbone);
-  for (int r : x->reserved) SFA_CHECK_ARG(r == 0, "sfa_arch_ex.reserved must be zero");
-  return check_arch(&x->base, x->backbone);
-}
-
-struct StateView {
-  std::map<std::string, std::pair<const float*, Entry>> m;
-  const float* get(const std::string& n) const {
-    auto it = m.find(n);
-    return it == m.end() ? nullptr : it->second.first;
-  }
-};
-
-// OIHW conv weight folded by BN scale into W[o][(kh*KW+kw)*Cpad + c] + k_off.
-static void put_conv(float* W, int Kpad, int k_off, const float* w, int O, int I, int KH, int KW,
-                     int Cpad, const std::vector<double>& scale) {
-  for (int o = 0; o < O; ++o)
-    for (int c = 0; c < I; ++c)
-      for (int kh = 0; kh < KH; ++kh)
-        for (int kw = 0; kw < KW; ++kw) {
-          const double v = w[((o * I + c) * KH + kh) * KW + kw];
-          W[(size_t)o * Kpad + k_off + (kh * KW + kw) * Cpad + c] = (float)(v * scale[o]);
-        }
-}
-
-static void bn_fold(const StateView& s, const std::string& p, int C, std::vector<double>& scale,
-                    std::vector<double>& shift) {
-  const float* g = s.get(p + ".weight");
-  const float* b = s.get(p + ".bias");
-  const float* mu = s.get(p + ".running_mean");
-  const float* var = s.get(p + ".running_var");
-  scale.assign(C, 1.0);
-  shift.assign(C, 0.0);
-  for (int c = 0; c < C; ++c) {
-    scale[c] = (double)g[c] / std::sqrt((double)var[c] + 1e-5);
-    shift[c] = (double)b[c] - (double)mu[c] * scale[c];
-  }
-}
-
-// f32 -> bf16, round to nearest even (finite inputs)
-static uint16_t bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-// W (n floats) -> three bf16 terms t0 + t1 + t2 == W (each residual is exact in f32)
-static void split_terms(const float* w, size_t n, uint16_t* out) {
-  for (size_t i = 0; i < n; ++i) {
-    float x = w[i];
-    for (int t = 0; t < 3; ++t) {
-      const uint16_t b = bf16_rne(x);
-      out[t * n + i] = b;
-      uint32_t u = (uint32_t)b << 16;
-      float bf;
-      memcpy(&bf, &u, 4);
-      x -= bf;
-    }
-  }
-}
-
-// fp16x3 form of W [N][K]: per output channel n, e[n] = floor(log2 max_k |W[n][k]|) and
-// W * 2^(13 - e[n]) (every |.| < 2^14) = hi + lo with hi = fp16(.) and lo = fp16(. - hi);
-// winv[n] = 2^(e[n] - 13).  Zero rows keep scale 1.
-static void split_terms_h3(const float* w, int N, int K, uint16_t* out, float* winv) {
-  const size_t n = (size_t)N * K;
-  for (int o = 0; o < N; ++o) {
-    float mx = 0.f;
-    for (int k = 0; k < K; ++k) mx = std::max(mx, std::fabs(w[(size_t)o * K + k]));
-    int e = 13;
-    if (mx > 0.f) {
-      (void)std::frexp(mx, &e);  // mx in [2^(e-1), 2^e)
-      e -= 1;
-    }
-    const float sc = std::ldexp(1.f, 13 - e);
-    winv[o] = std::ldexp(1.f, e - 13);
-    for (int k = 0; k < K; ++k) {
-      const size_t i = (size_t)o * K + k;
-      const float x = w[i] * sc;
-      const _Float16 hi = (_Float16)x;
-      const _Float16 lo = (_Float16)(x - (float)hi);
-      memcpy(out + i, &hi, 2);
-      memcpy(out + n + i, &lo, 2);
-    }
-  }
 }
 
 }  // namespace sfa
@@ -335,200 +219,6 @@ static void make_body_wimages(sfa_model* m) {
 
 extern "C" int sfa_abi_version(void) { return SFA_ABI_VERSION; }
 extern "C" const char* sfa_last_error_string(void) { return g_err.c_str(); }
-
-// The six layout / pack / create entry points: the sfa_arch forms are the SFA_BACKBONE_KFPN case of
-// the sfa_arch_ex forms (one implementation each, by family).
-extern "C" int sfa_state_count(const sfa_arch* arch) {
-  if (check_arch(arch) != SFA_OK) return -1;
-  return (int)state_layout(arch).size();
-}
-
-extern "C" int sfa_state_count_ex(const sfa_arch_ex* x) {
-  if (check_arch_ex(x) != SFA_OK) return -1;
-  return (int)state_layout(&x->base, x->backbone).size();
-}
-
-static int state_entry(const sfa_arch* arch, int backbone, int index, char* name, int name_len, int64_t* shape4,
-                       int* ndim) {
-  SFA_CHECK_ARG(shape4 && ndim, "state_entry: null argument");
-  const auto v = state_layout(arch, backbone);
-  SFA_CHECK_ARG(index >= 0 && index < (int)v.size(), "state index %d out of range", index);
-  const Entry& e = v[index];
-  SFA_CHECK_ARG(name && name_len > (int)e.name.size(), "name buffer too small");
-  memcpy(name, e.name.c_str(), e.name.size() + 1);
-  for (int i = 0; i < 4; ++i) shape4[i] = i < (int)e.shape.size() ? e.shape[i] : 0;
-  *ndim = (int)e.shape.size();
-  return SFA_OK;
-}
-
-extern "C" int sfa_state_entry(const sfa_arch* arch, int index, char* name, int name_len,
-                               int64_t* shape4, int* ndim) {
-  int rc = check_arch(arch);
-  if (rc != SFA_OK) return rc;
-  return state_entry(arch, SFA_BACKBONE_KFPN, index, name, name_len, shape4, ndim);
-}
-
-extern "C" int sfa_state_entry_ex(const sfa_arch_ex* x, int index, char* name, int name_len, int64_t* shape4,
-                                  int* ndim) {
-  int rc = check_arch_ex(x);
-  if (rc != SFA_OK) return rc;
-  return state_entry(&x->base, x->backbone, index, name, name_len, shape4, ndim);
-}
-
-static size_t state_floats_of(const sfa_arch* arch, int backbone) {
-  size_t n = 0;
-  for (const auto& e : state_layout(arch, backbone))
-    if (e.name.find("num_batches_tracked") == std::string::npos) n += numel(e);
-  return n;
-}
-
-extern "C" size_t sfa_state_floats(const sfa_arch* arch) {
-  if (check_arch(arch) != SFA_OK) return 0;
-  return state_floats_of(arch, SFA_BACKBONE_KFPN);
-}
-
-extern "C" size_t sfa_state_floats_ex(const sfa_arch_ex* x) {
-  if (check_arch_ex(x) != SFA_OK) return 0;
-  return state_floats_of(&x->base, x->backbone);
-}
-
-extern "C" size_t sfa_packed_floats(const sfa_arch* arch) {
-  if (check_arch(arch) != SFA_OK) return 0;
-  return make_plan(arch).total;
-}
-
-extern "C" size_t sfa_packed_floats_ex(const sfa_arch_ex* x) {
-  if (check_arch_ex(x) != SFA_OK) return 0;
-  return make_plan(&x->base, x->backbone).total;
-}
-
-static int pack_weights(const sfa_arch* arch, int backbone, const float* state, size_t state_floats, float* packed) {
-  SFA_CHECK_ARG(state && packed, "pack: null argument");
-  SFA_CHECK_ARG(state_floats == state_floats_of(arch, backbone), "pack: expected %zu state floats, got %zu",
-                state_floats_of(arch, backbone), state_floats);
-  const bool deconv = backbone == SFA_BACKBONE_DECONV;
-  StateView s;
-  size_t off = 0;
-  for (const auto& e : state_layout(arch, backbone)) {
-    if (e.name.find("num_batches_tracked") != std::string::npos) continue;
-    s.m[e.name] = {state + off, e};
-    off += numel(e);
-  }
-  const Plan p = make_plan(arch, backbone);
-  std::fill(packed, packed + p.total, 0.f);
-  std::vector<double> sc, sh, sc2, sh2;
-
-  // stem: conv1 + bn1, input channels padded 3 -> 4
-  bn_fold(s, "bn1", 64, sc, sh);
-  put_conv(packed + p.stem.w, p.stem.Kpad, 0, s.get("conv1.weight"), 64, 3, 7, 7, 4, sc);
-  for (int o = 0; o < 64; ++o) packed[p.stem.b + o] = (float)sh[o];
-
-  int inplanes = 64;
-  for (int li = 0; li < 4; ++li) {
-    const int planes = 64 << li;
-    for (int bi = 0; bi < 2; ++bi) {
-      const std::string pre = "layer" + std::to_string(li + 1) + "." + std::to_string(bi);
-      const int cin = bi == 0 ? inplanes : planes;
-      const PConv& c1 = p.blk[li][bi][0];
-      bn_fold(s, pre + ".bn1", planes, sc, sh);
-      put_conv(packed + c1.w, c1.Kpad, 0, s.get(pre + ".conv1.weight"), planes, cin, 3, 3, cin, sc);
-      for (int o = 0; o < planes; ++o) packed[c1.b + o] = (float)sh[o];
-      const PConv& c2 = p.blk[li][bi][1];
-      bn_fold(s, pre + ".bn2", planes, sc, sh);
-      put_conv(packed + c2.w, c2.Kpad, 0, s.get(pre + ".conv2.weight"), planes, planes, 3, 3, planes,
-               sc);
-      if (bi == 0 && li > 0) {
-        bn_fold(s, pre + ".downsample.1", planes, sc2, sh2);
-        put_conv(packed + c2.w, c2.Kpad, 9 * planes, s.get(pre + ".downsample.0.weight"), planes,
-                 inplanes, 1, 1, inplanes, sc2);
-        for (int o = 0; o < planes; ++o) packed[c2.b + o] = (float)(sh[o] + sh2[o]);
-      } else {
-        for (int o = 0; o < planes; ++o) packed[c2.b + o] = (float)sh[o];
-      }
-    }
-    inplanes = planes;
-  }
-  // deconv family: ConvTranspose2d weight (Cin, Cout, 4, 4) -> phase (py, px) matrix
-  // W[n][(2 dy + dx) C + c] = w[c][n][3 - py - 2 dy][3 - px - 2 dx] * BN scale[n] (deconv_h3_kernel.h)
-  for (int i = 0; deconv && i < 3; ++i) {
-    const PDeconv& d = p.dec[i];
-    const float* w = s.get("deconv_layers." + std::to_string(3 * i) + ".weight");
-    bn_fold(s, "deconv_layers." + std::to_string(3 * i + 1), d.N, sc, sh);
-    for (int ph = 0; ph < 4; ++ph) {
-      const int py = ph >> 1, px = ph & 1;
-      float* Wp = packed + d.w + (size_t)ph * d.N * d.K;
-      for (int n = 0; n < d.N; ++n)
-        for (int dy = 0; dy < 2; ++dy)
-          for (int dx = 0; dx < 2; ++dx)
-            for (int c = 0; c < d.C; ++c) {
-              const double v = w[(((size_t)c * d.N + n) * 4 + (3 - py - 2 * dy)) * 4 + (3 - px - 2 * dx)];
-              Wp[(size_t)n * d.K + (2 * dy + dx) * d.C + c] = (float)(v * sc[n]);
-            }
-      split_terms_h3(Wp, d.N, d.K, reinterpret_cast<uint16_t*>(packed + d.wh) + (size_t)ph * 2 * d.N * d.K,
-                     packed + d.winv + (size_t)ph * d.N);
-    }
-    for (int n = 0; n < d.N; ++n) packed[d.b + n] = (float)sh[n];
-  }
-  const int up_out[3] = {256, 128, 64}, up_in[3] = {768, 384, 192};
-  for (int i = 0; !deconv && i < 3; ++i) {
-    const std::string pre = "conv_up_level" + std::to_string(i + 1);
-    std::vector<double> one(up_out[i], 1.0);
-    put_conv(packed + p.fpn[i].w, p.fpn[i].Kpad, 0, s.get(pre + ".weight"), up_out[i], up_in[i], 1,
-             1, up_in[i], one);
-    const float* b = s.get(pre + ".bias");
-    for (int o = 0; o < up_out[i]; ++o) packed[p.fpn[i].b + o] = b[o];
-  }
-  const int nlev = deconv ? 1 : 3;  // head levels
-  for (int f = 0; f < nlev; ++f) {
-    const PHeads& hp = p.heads[f];
-    std::vector<double> one(arch->head_conv, 1.0);
-    for (int j = 0; j < arch->num_heads; ++j) {
-      const std::string pre = deconv ? std::string(arch->head_names[j])
-                                     : "fpn" + std::to_string(f) + "_" + arch->head_names[j];
-      put_conv(packed + hp.w3 + (size_t)j * 64 * hp.K, hp.K, 0, s.get(pre + ".0.weight"), 64,
-               kFpnC[f], 3, 3, kFpnC[f], one);
-      const float* b3 = s.get(pre + ".0.bias");
-      for (int o = 0; o < 64; ++o) packed[hp.b3 + j * 64 + o] = b3[o];
-      const float* w1 = s.get(pre + ".2.weight");
-      const float* b1 = s.get(pre + ".2.bias");
-      for (int c = 0; c < arch->head_channels[j]; ++c) {
-        for (int k = 0; k < 64; ++k) packed[hp.w1 + (j * 4 + c) * 64 + k] = w1[c * 64 + k];
-        packed[hp.b1 + j * 4 + c] = b1[c];
-      }
-    }
-  }
-  // bf16x6 and fp16x3 terms of every implicit-GEMM weight matrix
-  auto split = [&](const PConv& c) {
-    split_terms(packed + c.w, (size_t)c.N * c.Kpad, reinterpret_cast<uint16_t*>(packed + c.wx));
-    split_terms_h3(packed + c.w, c.N, c.Kpad, reinterpret_cast<uint16_t*>(packed + c.wh),
-                   packed + c.winv);
-  };
-  split(p.stem);
-  for (int li = 0; li < 4; ++li)
-    for (int bi = 0; bi < 2; ++bi)
-      for (int ci = 0; ci < 2; ++ci) split(p.blk[li][bi][ci]);
-  for (int i = 0; !deconv && i < 3; ++i) split(p.fpn[i]);
-  for (int f = 0; f < nlev; ++f) {
-    const PHeads& hp = p.heads[f];
-    split_terms(packed + hp.w3, (size_t)hp.N * hp.K, reinterpret_cast<uint16_t*>(packed + hp.wx));
-    split_terms_h3(packed + hp.w3, hp.N, hp.K, reinterpret_cast<uint16_t*>(packed + hp.wh),
-                   packed + hp.winv);
-  }
-  return SFA_OK;
-}
-
-extern "C" int sfa_pack_weights(const sfa_arch* arch, const float* state, size_t state_floats,
-                                float* packed) {
-  int rc = check_arch(arch);
-  if (rc != SFA_OK) return rc;
-  return pack_weights(arch, SFA_BACKBONE_KFPN, state, state_floats, packed);
-}
-
-extern "C" int sfa_pack_weights_ex(const sfa_arch_ex* x, const float* state, size_t state_floats, float* packed) {
-  int rc = check_arch_ex(x);
-  if (rc != SFA_OK) return rc;
-  return pack_weights(&x->base, x->backbone, state, state_floats, packed);
-}
 
 static int model_create(const sfa_arch* arch, int backbone, const float* packed_device, sfa_model** out,
                         const sfa_model* twin_of = nullptr) {

@@ -1,12 +1,87 @@
-// sfa_pack_weights_device(_ex): sfa_pack_weights on the device, from the state tensors where they live into
-// the packed buffer a model handle reads, byte for byte (pack_kernel.h; the plan and its units: pack_plan.h).
-// Stream-ordered: no host synchronisation, no allocation, no memset node; capturable in a HIP graph (the
-// pointers travel by value in the kernel arguments).
+// The state layout and the weight pack: the descriptor checks, the layout and size entries, and the two drivers of
+// one description of the pack (the units of pack_plan.h, the element rules of pack_row.h).  sfa_pack_weights(_ex)
+// walks the units on the host (pack_host.h); sfa_pack_weights_device(_ex) launches one kernel per unit
+// (pack_kernel.h) from the state tensors where they live into the packed buffer a model handle reads, the same
+// bytes.  The device form is stream-ordered: no host synchronisation, no allocation, no memset node; capturable in
+// a HIP graph (the pointers travel by value in the kernel arguments).
+#include "pack_host.h"
 #include "pack_kernel.h"
 
 #include "dispatch.h"
 
 namespace sfa {
+
+int check_arch(const sfa_arch* a, int backbone) {
+  SFA_CHECK_ARG(a != nullptr, "arch is null");
+  if (a->num_layers != 18) {
+    set_error("only %s is implemented (got %d layers)", backbone == SFA_BACKBONE_DECONV ? "resnet_18" : "fpn_resnet_18",
+              a->num_layers);
+    return SFA_E_UNSUPPORTED;
+  }
+  if (a->head_conv != 64) {
+    set_error("only head_conv = 64 is implemented (got %d)", a->head_conv);
+    return SFA_E_UNSUPPORTED;
+  }
+  SFA_CHECK_ARG(a->num_heads >= 1 && a->num_heads <= SFA_MAX_HEADS, "num_heads %d out of range",
+                a->num_heads);
+  for (int j = 0; j < a->num_heads; ++j) {
+    SFA_CHECK_ARG(a->head_channels[j] >= 1 && a->head_channels[j] <= 4,
+                  "head %d: channels %d out of [1, 4]", j, a->head_channels[j]);
+    SFA_CHECK_ARG(strnlen(a->head_names[j], 32) > 0 && strnlen(a->head_names[j], 32) < 32,
+                  "head %d: bad name", j);
+  }
+  return SFA_OK;
+}
+
+// The extended descriptor: the base checks of its family; reserved words zero, a known backbone.
+int check_arch_ex(const sfa_arch_ex* x) {
+  SFA_CHECK_ARG(x != nullptr, "arch is null");
+  SFA_CHECK_ARG(x->backbone == SFA_BACKBONE_KFPN || x->backbone == SFA_BACKBONE_DECONV, "unknown backbone %d",
+                x->backbone);
+  for (int r : x->reserved) SFA_CHECK_ARG(r == 0, "sfa_arch_ex.reserved must be zero");
+  return check_arch(&x->base, x->backbone);
+}
+
+static int state_entry(const sfa_arch* arch, int backbone, int index, char* name, int name_len, int64_t* shape4,
+                       int* ndim) {
+  SFA_CHECK_ARG(shape4 && ndim, "state_entry: null argument");
+  const auto v = state_layout(arch, backbone);
+  SFA_CHECK_ARG(index >= 0 && index < (int)v.size(), "state index %d out of range", index);
+  const Entry& e = v[index];
+  SFA_CHECK_ARG(name && name_len > (int)e.name.size(), "name buffer too small");
+  memcpy(name, e.name.c_str(), e.name.size() + 1);
+  for (int i = 0; i < 4; ++i) shape4[i] = i < (int)e.shape.size() ? e.shape[i] : 0;
+  *ndim = (int)e.shape.size();
+  return SFA_OK;
+}
+
+static size_t state_floats_of(const sfa_arch* arch, int backbone) {
+  size_t n = 0;
+  for (const auto& e : state_layout(arch, backbone))
+    if (!is_batches_tracked(e)) n += numel(e);
+  return n;
+}
+
+// Every unit against what both drivers index (pack_plan.h pack_unit_fits), before either writes anything.
+static int check_units(const char* who, const std::vector<PackUnit>& units, const std::vector<Entry>& layout) {
+  for (const PackUnit& u : units)
+    if (!pack_unit_fits(u, layout)) {
+      set_error("%s: a pack unit does not fit the kernel (Kpad %d, rows %d)", who, u.Kpad, u.rows);
+      return SFA_E_UNSUPPORTED;
+    }
+  return SFA_OK;
+}
+
+static int pack_weights(const sfa_arch* arch, int backbone, const float* state, size_t state_floats, float* packed) {
+  SFA_CHECK_ARG(state && packed, "pack: null argument");
+  SFA_CHECK_ARG(state_floats == state_floats_of(arch, backbone), "pack: expected %zu state floats, got %zu",
+                state_floats_of(arch, backbone), state_floats);
+  const std::vector<Entry> layout = state_layout(arch, backbone);
+  const std::vector<PackUnit> units = pack_units(arch, backbone);
+  if (int rc = check_units("pack", units, layout)) return rc;
+  pack_host(units, pack_sources(layout, state).data(), make_plan(arch, backbone).total, packed);
+  return SFA_OK;
+}
 
 bool device_memory_covers(const void* p, size_t bytes) {
   hipPointerAttribute_t at;
@@ -46,23 +121,7 @@ static int pack_weights_device(const sfa_arch* arch, int backbone, const float* 
   SFA_CHECK_ARG(device_memory_covers(packed, plan.total * 4),
                 "pack_device: packed_device is not %zu floats of memory of the current device", plan.total);
   const std::vector<PackUnit> units = pack_units(arch, backbone);
-  for (const PackUnit& u : units) {
-    bool ok = u.Kpad % 8 == 0 && u.Kpad <= kPackMaxRow && u.rows > 0 && u.seg[0].w >= 0 && (u.bias >= 0 || u.seg[0].bn[0] >= 0);
-    for (int s = 0; s < u.nseg; ++s) {
-      const PackSeg& sg = u.seg[s];
-      const int last = u.kind == PACK_DECONV ? 4 * sg.I : sg.k_off + (sg.KH * sg.KW - 1) * sg.Cpad + sg.I;
-      ok = ok && sg.w >= 0 && sg.I <= sg.Cpad && last <= u.Kpad;
-      // every source index of the kernel lies inside the tensor the layout describes
-      const int src_rows = u.kind == PACK_DECONV ? u.N : u.O;
-      ok = ok && numel(layout[sg.w]) == (int64_t)src_rows * sg.I * sg.KH * sg.KW;
-      for (int q = 0; q < 4; ++q) ok = ok && (sg.bn[q] < 0 ? sg.bn[0] < 0 : numel(layout[sg.bn[q]]) == src_rows);
-    }
-    ok = ok && (u.bias < 0 || numel(layout[u.bias]) == u.O);
-    if (!ok) {
-      set_error("pack_device: a pack unit does not fit the kernel (Kpad %d, rows %d)", u.Kpad, u.rows);
-      return SFA_E_UNSUPPORTED;
-    }
-  }
+  if (int rc = check_units("pack_device", units, layout)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   auto src = [&](int i) { return i < 0 ? nullptr : state[i]; };
   for (const PackUnit& u : units) {
@@ -98,6 +157,65 @@ static int pack_weights_device(const sfa_arch* arch, int backbone, const float* 
 }  // namespace sfa
 
 using namespace sfa;
+
+// The layout / size / pack entry points: the sfa_arch forms are the SFA_BACKBONE_KFPN case of the sfa_arch_ex forms
+// (one implementation each, by family).
+extern "C" int sfa_state_count(const sfa_arch* arch) {
+  if (check_arch(arch) != SFA_OK) return -1;
+  return (int)state_layout(arch).size();
+}
+
+extern "C" int sfa_state_count_ex(const sfa_arch_ex* x) {
+  if (check_arch_ex(x) != SFA_OK) return -1;
+  return (int)state_layout(&x->base, x->backbone).size();
+}
+
+extern "C" int sfa_state_entry(const sfa_arch* arch, int index, char* name, int name_len,
+                               int64_t* shape4, int* ndim) {
+  int rc = check_arch(arch);
+  if (rc != SFA_OK) return rc;
+  return state_entry(arch, SFA_BACKBONE_KFPN, index, name, name_len, shape4, ndim);
+}
+
+extern "C" int sfa_state_entry_ex(const sfa_arch_ex* x, int index, char* name, int name_len, int64_t* shape4,
+                                  int* ndim) {
+  int rc = check_arch_ex(x);
+  if (rc != SFA_OK) return rc;
+  return state_entry(&x->base, x->backbone, index, name, name_len, shape4, ndim);
+}
+
+extern "C" size_t sfa_state_floats(const sfa_arch* arch) {
+  if (check_arch(arch) != SFA_OK) return 0;
+  return state_floats_of(arch, SFA_BACKBONE_KFPN);
+}
+
+extern "C" size_t sfa_state_floats_ex(const sfa_arch_ex* x) {
+  if (check_arch_ex(x) != SFA_OK) return 0;
+  return state_floats_of(&x->base, x->backbone);
+}
+
+extern "C" size_t sfa_packed_floats(const sfa_arch* arch) {
+  if (check_arch(arch) != SFA_OK) return 0;
+  return make_plan(arch).total;
+}
+
+extern "C" size_t sfa_packed_floats_ex(const sfa_arch_ex* x) {
+  if (check_arch_ex(x) != SFA_OK) return 0;
+  return make_plan(&x->base, x->backbone).total;
+}
+
+extern "C" int sfa_pack_weights(const sfa_arch* arch, const float* state, size_t state_floats,
+                                float* packed) {
+  int rc = check_arch(arch);
+  if (rc != SFA_OK) return rc;
+  return pack_weights(arch, SFA_BACKBONE_KFPN, state, state_floats, packed);
+}
+
+extern "C" int sfa_pack_weights_ex(const sfa_arch_ex* x, const float* state, size_t state_floats, float* packed) {
+  int rc = check_arch_ex(x);
+  if (rc != SFA_OK) return rc;
+  return pack_weights(&x->base, x->backbone, state, state_floats, packed);
+}
 
 extern "C" int sfa_pack_weights_device(const sfa_arch* arch, const float* const* state, int count,
                                        float* packed_device, void* stream) {

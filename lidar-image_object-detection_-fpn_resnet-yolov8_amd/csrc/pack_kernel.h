@@ -1,12 +1,13 @@
 // The device form of sfa_pack_weights: one workgroup per packed row (pack_plan.h PackUnit). The row's source
 // floats are read once, folded with the BatchNorm scale (double, as the host does) into an LDS row in packed
 // order, reduced to the row maximum, and written out as f32, three bf16 terms, two scaled fp16 terms, winv and
-// the bias. Every operation is the host's own (model.hip put_conv / bn_fold / split_terms / split_terms_h3), so
-// the bytes are the host's: compiled with -ffp-contract=off.
+// the bias. The fold, the row exponent and the two splits are the functions of pack_row.h, the ones the host walk
+// calls (pack_host.h), so the bytes are the host's: compiled with -ffp-contract=off.
 #pragma once
 
 #include "common.h"
 #include "pack_plan.h"
+#include "pack_row.h"
 
 namespace sfa {
 
@@ -36,17 +37,6 @@ struct PackGapsDev {
   int count;
 };
 
-// f32 -> bf16, round to nearest even, on the bits (finite inputs)
-__device__ __forceinline__ uint32_t pack_bf16_rne(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return u >> 16;
-}
-
-__device__ __forceinline__ uint32_t pack_half_bits(_Float16 h) {
-  return (uint32_t) __builtin_bit_cast(unsigned short, h);
-}
-
 __global__ __launch_bounds__(kPackThreads) void pack_rows_kernel(const PackUnitDev u) {
   __shared__ float row[kPackMaxRow];
   __shared__ float wave_max[kPackThreads / 64];
@@ -62,11 +52,8 @@ __global__ __launch_bounds__(kPackThreads) void pack_rows_kernel(const PackUnitD
   for (int s = 0; s < u.nseg; ++s) {
     const PackSegDev& sg = u.seg[s];
     double scale = 1.0;
-    if (live && sg.bn[0]) {
-      scale = (double)sg.bn[0][src_row] / sqrt((double)sg.bn[3][src_row] + 1e-5);
-      const double shift = (double)sg.bn[1][src_row] - (double)sg.bn[2][src_row] * scale;
-      shift_sum = s == 0 ? shift : shift_sum + shift;  // (a lone -0.0 shift stays -0.0)
-    }
+    if (live && sg.bn[0])
+      scale = pack_bn_fold(sg.bn[0][src_row], sg.bn[1][src_row], sg.bn[2][src_row], sg.bn[3][src_row], s, shift_sum);
     if (!live) continue;
     if (u.kind == PACK_DECONV) {
       const int K = 4 * sg.I;
@@ -90,16 +77,10 @@ __global__ __launch_bounds__(kPackThreads) void pack_rows_kernel(const PackUnitD
   __syncthreads();
   mx = fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]));
 
-  // e = floor(log2 max); a zero row keeps 13 (scale 1)
-  int e = 13;
-  if (mx > 0.f) {
-    (void)frexpf(mx, &e);
-    e -= 1;
-  }
-  const float sc = ldexpf(1.f, 13 - e);
+  const PackRowScale rs = pack_row_scale(mx);
 
   if (tid == 0) {
-    if (u.winv) u.winv[r] = ldexpf(1.f, e - 13);
+    if (u.winv) u.winv[r] = rs.winv;
     if (u.kind != PACK_DECONV || ph == 0) {
       float b = 0.f;
       if (live) b = u.bias ? u.bias[src_row] : (float)shift_sum;
@@ -121,12 +102,10 @@ __global__ __launch_bounds__(kPackThreads) void pack_rows_kernel(const PackUnitD
       uint32_t t[3][8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float v = x[j];
+        uint32_t tj[3];
+        pack_bf16_terms(x[j], tj);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          t[q][j] = pack_bf16_rne(v);
-          v -= __uint_as_float(t[q][j] << 16);
-        }
+        for (int q = 0; q < 3; ++q) t[q][j] = tj[q];
       }
 #pragma unroll
       for (int q = 0; q < 3; ++q)
@@ -138,11 +117,9 @@ __global__ __launch_bounds__(kPackThreads) void pack_rows_kernel(const PackUnitD
       uint32_t hi[8], lo[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float v = x[j] * sc;
-        const _Float16 h = (_Float16)v;
-        const _Float16 l = (_Float16)(v - (float)h);
-        hi[j] = pack_half_bits(h);
-        lo[j] = pack_half_bits(l);
+        const PackHalfTerms h = pack_fp16_terms(x[j], rs.sc);
+        hi[j] = h.hi;
+        lo[j] = h.lo;
       }
       *reinterpret_cast<uint4*>(u.wh + term0 + k) =
           make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));

@@ -1,6 +1,7 @@
 // The packed-weight plan: the reference state_dict layout of both families, the offsets of every packed
-// matrix (make_plan) and the flat list of pack units, the work of sfa_pack_weights and of its device form
-// (pack.hip) in one description. Plain C++ (no HIP include): tools/pack_plan_check.cpp walks it on the CPU.
+// matrix (make_plan) and the flat list of pack units, the one description of the pack that sfa_pack_weights
+// (pack_host.h) and its device form (pack_kernel.h) both walk. Plain C++ (no HIP include, g++ builds it):
+// tools/pack_plan_check.cpp walks it on the CPU.
 #pragma once
 
 #include <algorithm>
@@ -15,7 +16,7 @@
 
 namespace sfa {
 
-// The descriptor checks of every layout / pack / create entry (model.hip); only declared here.
+// The descriptor checks of every layout / pack / create entry (pack.hip); only declared here.
 int check_arch(const sfa_arch* a, int backbone = SFA_BACKBONE_KFPN);
 int check_arch_ex(const sfa_arch_ex* x);
 
@@ -341,6 +342,26 @@ inline std::vector<PackUnit> pack_units(const sfa_arch* a, int backbone = SFA_BA
     }
   }
   return v;
+}
+
+// Whether both drivers of the pack (pack_host.h, pack_kernel.h) can walk the unit: a row of 8-element steps that
+// fits the kernel's LDS row, every segment inside the row, and every source index inside the tensor `layout`
+// describes (the weight rows x I x KH x KW, a whole BatchNorm quadruple or none, the bias).
+inline bool pack_unit_fits(const PackUnit& u, const std::vector<Entry>& layout) {
+  auto holds = [&](int i, int64_t n) { return i >= 0 && i < (int)layout.size() && numel(layout[i]) == n; };
+  const bool deconv = u.kind == PACK_DECONV;
+  bool ok = (deconv || u.kind == PACK_CONV) && u.Kpad > 0 && u.Kpad % 8 == 0 && u.Kpad <= kPackMaxRow && u.N > 0 &&
+            u.O >= 1 && u.O <= u.rows && (deconv ? u.rows == 4 * u.N : u.rows <= u.N) && (u.nseg == 1 || u.nseg == 2) &&
+            (u.bias >= 0 || u.seg[0].bn[0] >= 0);
+  const int src_rows = deconv ? u.N : u.O;
+  for (int s = 0; ok && s < u.nseg; ++s) {
+    const PackSeg& sg = u.seg[s];
+    ok = sg.I >= 1 && sg.I <= sg.Cpad && sg.KH >= 1 && sg.KW >= 1 && sg.k_off >= 0 && (!deconv || sg.KH * sg.KW == 16);
+    const int last = deconv ? 4 * sg.I : sg.k_off + (sg.KH * sg.KW - 1) * sg.Cpad + sg.I;
+    ok = ok && last <= u.Kpad && holds(sg.w, (int64_t)src_rows * sg.I * sg.KH * sg.KW);
+    for (int q = 0; q < 4; ++q) ok = ok && (sg.bn[q] < 0 ? sg.bn[0] < 0 : holds(sg.bn[q], src_rows));
+  }
+  return ok && (u.bias < 0 || holds(u.bias, u.O));
 }
 
 // The destination regions of a unit, [first, second) in floats.

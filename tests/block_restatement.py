@@ -3,8 +3,8 @@ float64, with the error bounds the GPU kernels (csrc/block_kernel.h) are held to
 
 Block layer{L}.{b}: Cout = 64 2^(L-1); for b == 0 and L > 1 stride s = 2, Cin = Cout / 2 and a 1x1 stride-2
 downsample, else s = 1, Cin = Cout and the identity skip.  Maps are NHWC: x (B, h, w, Cin); mid, y, gy (B, oh, ow,
-Cout), oh = ceil(h / s).  The folded parameters are float32 as the library packs them (csrc/model.hip bn_fold /
-put_conv): W' = float32(W * scale), scale = gamma / sqrt(var + 1e-5) in float64, rows [o][(kh * 3 + kw) C + c];
+Cout), oh = ceil(h / s).  The folded parameters are float32 as the library packs them (csrc/pack_row.h pack_bn_fold,
+csrc/pack_host.h): W' = float32(W * scale), scale = gamma / sqrt(var + 1e-5) in float64, rows [o][(kh * 3 + kw) C + c];
 b' = float32(beta - mean * scale); with a downsample b2' = float32(shift2 + shift_d).
 
     a  = ReLU(conv3x3_s(x; W1') + b1')      z = conv3x3_1(a; W2') + b2' + skip      y = ReLU(z)

@@ -1,12 +1,12 @@
 """CPU restatement of the scaled-fp16 convolution arithmetic (SFA_MATH_FP16X3 / SFA_MATH_FP16) — a
 helper of tests/test_math_fp16_host.py, tests/test_gpu_math_fp16.py and tools/fp16_error_budget.py.
 
-What the library specifies (include/sfa_hip.h sfa_math, csrc/conv.h, csrc/model.hip), restated in torch:
+What the library specifies (include/sfa_hip.h sfa_math, csrc/conv.h, csrc/model.hip, csrc/pack_row.h), restated in torch:
 
 * BatchNorm (eps 1e-5) folded as sfa_pack_weights does: scale = g / sqrt(var + eps) and
   shift = b - mean * scale in f64, W = f32(w * scale); a block's conv2 and its 1x1 downsample are one
   conv over two K-segments with bias f32(shift2 + shift_ds).
-* Weight scale per output channel n (model.hip split_terms_h3): e[n] = floor(log2 max_k |W[n][k]|) over the
+* Weight scale per output channel n (pack_row.h pack_row_scale): e[n] = floor(log2 max_k |W[n][k]|) over the
   whole K-concatenated row, W * 2^(13 - e[n]); zero rows keep scale 1.
 * Activation scale per tensor and frame (conv.h amax_frame_scale): 2^(13 - e) for max |x| in [2^e, 2^(e+1))
   over the conv's input segments; zero -> 1.
@@ -49,7 +49,7 @@ def round_terms(v, terms):
 
 
 def fold_bn(sd, conv, bn):
-    """f32 OIHW weight with BN folded, f64 shift — as model.hip bn_fold / put_conv."""
+    """f32 OIHW weight with BN folded, f64 shift — as pack_row.h pack_bn_fold and the gather of pack_host.h."""
     w = sd[conv + ".weight"].to(F64)
     scale = sd[bn + ".weight"].to(F64) / torch.sqrt(sd[bn + ".running_var"].to(F64) + 1e-5)
     shift = sd[bn + ".bias"].to(F64) - sd[bn + ".running_mean"].to(F64) * scale

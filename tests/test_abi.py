@@ -48,7 +48,7 @@ def test_state_layout_matches_reference(golden):
 
 
 def _unpack_plan_offsets(arch):
-    """Recompute the packed layout independently (mirror of model.hip make_plan)."""
+    """Recompute the packed layout independently (mirror of pack_plan.h make_plan)."""
     cur = 0
     out = {}
 

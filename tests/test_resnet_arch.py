@@ -84,7 +84,7 @@ def test_bad_descriptors_are_refused(arch):
 
 
 def _plan_offsets(num_heads=5):
-    """The packed layout of the deconv family, recomputed independently (mirror of model.hip make_plan):
+    """The packed layout of the deconv family, recomputed independently (mirror of pack_plan.h make_plan):
     the shared backbone as tests/test_abi.py, then per transposed conv w [4][256][4 C], b [256],
     wh [4][2][256][4 C] fp16, winv [4][256], then the one head level."""
     cur = 0

@@ -2,8 +2,8 @@
 // against the state layout and make_plan.  Every state entry but the num_batches_tracked counters is a source
 // of exactly one unit; the units' destination regions are pairwise disjoint, lie inside [0, total) and, with the
 // alignment gaps, cover the buffer; offsets are aligned; rows x Kpad is what make_plan reserves; every source
-// index of a unit lies inside its tensor.  Head sets come from the command line as name:channels,... (one
-// argument per set; none: the production set).  Build with a sanitizer:
+// index of a unit lies inside its tensor, in this file's own words and through pack_unit_fits, the predicate both
+// drivers of the pack apply.  Head sets come from the command line (pack_check_sets.h).  Build with a sanitizer:
 //   g++ -std=c++17 -O2 -g -fsanitize=address,undefined tools/pack_plan_check.cpp -o /tmp/pack_plan_check
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../lidar-image_object-detection_-fpn_resnet-yolov8_amd/csrc/pack_plan.h"
+#include "pack_check_sets.h"
 
 using namespace sfa;
 
@@ -27,27 +28,6 @@ static long long g_checks = 0, g_bad = 0;
       }                                  \
     }                                    \
   } while (0)
-
-static bool parse_set(const char* text, sfa_arch* a) {
-  memset(a, 0, sizeof *a);
-  a->num_layers = 18;
-  a->head_conv = 64;
-  std::string s(text);
-  size_t pos = 0;
-  while (pos < s.size()) {
-    size_t end = s.find(',', pos);
-    if (end == std::string::npos) end = s.size();
-    const std::string item = s.substr(pos, end - pos);
-    const size_t colon = item.find(':');
-    if (colon == std::string::npos || colon == 0 || colon >= 32 || a->num_heads >= SFA_MAX_HEADS) return false;
-    memcpy(a->head_names[a->num_heads], item.c_str(), colon);
-    a->head_channels[a->num_heads] = atoi(item.c_str() + colon + 1);
-    if (a->head_channels[a->num_heads] < 1 || a->head_channels[a->num_heads] > 4) return false;
-    ++a->num_heads;
-    pos = end + 1;
-  }
-  return a->num_heads >= 1;
-}
 
 static void check_family(const char* what, const sfa_arch* a, int backbone) {
   const std::vector<Entry> layout = state_layout(a, backbone);
@@ -68,6 +48,7 @@ static void check_family(const char* what, const sfa_arch* a, int backbone) {
            layout[i].name.c_str(), (long long)numel(layout[i]), (long long)need);
   };
   for (const PackUnit& u : units) {
+    EXPECT(pack_unit_fits(u, layout), "%s: a unit of %d rows x %d does not fit the drivers", what, u.rows, u.Kpad);
     EXPECT(u.kind == PACK_CONV || u.kind == PACK_DECONV, "%s: kind %d", what, u.kind);
     EXPECT(u.nseg == 1 || u.nseg == 2, "%s: nseg %d", what, u.nseg);
     EXPECT(u.rows > 0 && u.O >= 1 && u.O <= u.rows && u.N > 0, "%s: rows %d O %d N %d", what, u.rows, u.O, u.N);
@@ -179,9 +160,7 @@ static void check_family(const char* what, const sfa_arch* a, int backbone) {
 }
 
 int main(int argc, char** argv) {
-  std::vector<std::string> sets;
-  for (int i = 1; i < argc; ++i) sets.push_back(argv[i]);
-  if (sets.empty()) sets.push_back("hm_cen:3,cen_offset:2,direction:2,z_coor:1,dim:3");
+  const std::vector<std::string> sets = sets_of(argc, argv);
   for (const std::string& s : sets) {
     sfa_arch a;
     if (!parse_set(s.c_str(), &a)) {
