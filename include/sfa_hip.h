@@ -1017,6 +1017,61 @@ int sfa_block_train_grad(int layer, int block, const float* x, const float* z1, 
                          float* const* dparams, int max_chunk_pixels, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ------------------------- the stem in training mode: bn1 with batch statistics, float32 conv1 --
+ * models/fpn_resnet.py:179-182 under model.train(): bn1 normalises with the mean and the biased variance of the batch
+ * and is differentiated through them.  As sfa_block_train_*, the entries take NO model handle and read the raw float32
+ * parameters in torch's layouts.  x is DEVICE float32 (B, 3, H, W) NCHW; the maps are DEVICE float32 NHWC; all 16-byte
+ * aligned.  oh = ceil(H / 2), ow = ceil(W / 2), ph = ceil(oh / 2), pw = ceil(ow / 2); n = B oh ow is what one channel
+ * of bn1 sees.
+ *   z = conv7x7_2(x; W)                 (B, oh, ow, 64), raw: no bias, no ReLU
+ *   mean, var = the batch mean and biased variance of z per channel
+ *   a = ReLU(s z + t)                   s = gamma / sqrt(var + eps),  t = beta - mean s
+ *   p = maxpool3x3_2(a)                 (B, ph, pw, 64)
+ *   params   HOST array of 3 DEVICE pointers W (64, 3, 7, 7), gamma (64), beta (64)
+ *   stats    DEVICE float32 [2][64]: mean then biased variance; the forward writes it, the gradient reads it
+ *
+ * sfa_stem_train_forward writes z, a, pooled and stats, every byte.  The convolution is float32 on
+ * v_mfma_f32_32x32x2_f32, 64 conv pixels x 64 channels per workgroup, K = the 147 (c, ky, kx) entries in torch's
+ * order (padded with zero rows to 160) inside one workgroup, the image gathered with every row and column tested,
+ * from a k-major copy of W rebuilt in the workspace every call.  Statistics, (s, t) and the apply are
+ * sfa_block_train_forward's, word for word: float64 sums of z and z^2 over blocks of pixels in pixel order, then over
+ * the blocks in block order (at most 256; max_chunk_pixels > 0 also caps a block), mean and var each rounded once to
+ * float32, s and t in float64 FROM THE ROUNDED mean and var, rounded once, one float32 FMA per element, the ReLU.
+ * The max-pool is the model's own launch.
+ *
+ * sfa_stem_train_grad: from gp = d total / d p and the maps and statistics the forward wrote
+ *   dY = a > 0 ? (pool adjoint of gp by first maximum) : 0          (sfa_model_stem_grad's adjoint)
+ *   dbeta = sum dY     dgamma = invstd sum dY (z - mean)             invstd = 1 / sqrt(var + eps)
+ *   dZ = gamma invstd (dY - sum dY / n - (z - mean) invstd^2 sum dY (z - mean) / n)
+ *   dW = wgrad_2(dZ, x) (64, 3, 7, 7)   dx = dgrad_2(dZ; W) (B, 3, H, W)     (W is the raw weight: nothing to unfold)
+ * with the two sums in float64 in the statistics' block order, dZ in float64 per element, rounded once, stored in the
+ * workspace, and dW / dx through sfa_model_stem_grad's kernels (split-K chunks of at most max_chunk_pixels conv
+ * pixels, 0: the plan's own size; dx from a [o][tap][4] copy of W rebuilt in the workspace).
+ *   grad_x       NULL (not wanted) or (B, 3, H, W); every byte written
+ *   dparams      NULL, or a HOST array of 3 DEVICE pointers dW, dgamma, dbeta in torch's shapes, each may be NULL;
+ *                every byte of a wanted output is written
+ *   params       as in the forward; beta is not read and may be NULL
+ *   x            may be NULL when dW is not wanted; z, a, gp and stats are required
+ * sfa_stem_train_chunk_pixels(which = 0) is K_c, the pixels of dW's largest chunk; which = 1 is the pixels of one
+ * statistics block (0 when refused).  No atomics, no memset, nothing allocates or synchronises; two runs are
+ * bit-identical; graph-capturable.
+ *
+ * All of these, before any launch: SFA_E_INVALID for a NULL required pointer, no output wanted, non-positive B, H or
+ * W, a negative max_chunk_pixels, a negative eps, a misaligned buffer, a workspace that is too small, a map of 2^31
+ * bytes or more (x counted at 16 bytes per pixel, and a), or n < 2 (the size functions return 0);
+ * SFA_E_UNSUPPORTED for B above 65535 or H above 262140 (the max-pool launch puts the frame and the pooled row on
+ * grid axes).  W has no limit of its own, and the 32760 of sfa_model_stem_forward's fp16x3 launch does not apply. */
+size_t sfa_stem_train_forward_workspace_size(int B, int H, int W, int max_chunk_pixels);
+size_t sfa_stem_train_grad_workspace_size(int B, int H, int W, int max_chunk_pixels);
+int sfa_stem_train_chunk_pixels(int which, int B, int H, int W, int max_chunk_pixels);
+int sfa_stem_train_forward(const float* x, const float* const* params, double eps, int B, int H, int W, float* z,
+                           float* a, float* pooled, float* stats, int max_chunk_pixels, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int sfa_stem_train_grad(const float* x, const float* z, const float* a, const float* gp, const float* stats,
+                        const float* const* params, double eps, int B, int H, int W, float* grad_x,
+                        float* const* dparams, int max_chunk_pixels, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 /* ------------------------------------------- the stem as an operator (both backbone families) --
  * models/fpn_resnet.py:179-182 on a caller's image, bn1 as the handle holds it: running statistics, folded into conv1
  * (W' = s W, b' = beta - mean s, s = gamma / sqrt(var + 1e-5)).  x is DEVICE float32 (B, 3, H, W) NCHW (SFA_IN_NCHW3;

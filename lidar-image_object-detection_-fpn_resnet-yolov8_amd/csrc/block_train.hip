@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "block_host.h"
+#include "block_train_host.h"
 #include "block_train_kernel.h"
 #include "dispatch.h"
 #include "grad_host.h"
@@ -33,39 +34,55 @@ int conv_bn(const BlockShape& s, const GradBias& sb, const float* x, const float
   if (int rc = launch({dim3((unsigned)grad_tiles(s.npix_out), (unsigned)(s.cout / kGradTile)), dim3(256), st},
                       block_conv_fwd_kernel, t, z))
     return rc;
-  const unsigned cy = (unsigned)ceil_div(s.cout, 256);
-  if (int rc = launch({dim3((unsigned)sb.blocks, cy), dim3(256), st}, bn_stats_kernel, (const float*)z, spart, sb.npix,
-                      sb.pixels, s.cout))
-    return rc;
-  return launch({dim3(cy), dim3(256), st}, bn_stats_fold_kernel, (const double*)spart, sb.blocks, s.cout, s.npix_out,
-                gamma, beta, eps, stats, coef);
+  return launch_bn_train_stats(sb, z, gamma, beta, eps, spart, stats, coef, st);
 }
 
 int apply(const BlockShape& s, const float* z, const float* c, const float* x, const float* zd, const float* cd,
           float* out, hipStream_t st) {
-  const int quads = s.npix_out * s.cout / 4;
-  return launch({dim3((unsigned)ceil_div(quads, 256)), dim3(256), st}, bn_apply_kernel, z, c, x, zd, cd, out, quads,
-                s.cout);
+  return launch_bn_train_apply(s.npix_out, s.cout, z, c, x, zd, cd, out, st);
 }
 
 // The backward of one BatchNorm: dbeta, dgamma (each may be null) and, when dz is not null, dZ.
-int bn_backward(const BlockShape& s, const GradBias& sb, const float* g, const float* gm, const float* z,
+int bn_backward(const BlockShape&, const GradBias& sb, const float* g, const float* gm, const float* z,
                 const float* stats, const float* gamma, double eps, double* rpart, double* sums, float* dgamma,
                 float* dbeta, float* dz, hipStream_t st) {
-  const unsigned cy = (unsigned)ceil_div(s.cout, 256);
-  if (int rc = launch({dim3((unsigned)sb.blocks, cy), dim3(256), st}, bn_bwd_reduce_kernel, g, gm, z, stats, rpart,
-                      sb.npix, sb.pixels, s.cout))
-    return rc;
-  if (int rc = launch({dim3(cy), dim3(256), st}, bn_bwd_fold_kernel, (const double*)rpart, sb.blocks, s.cout, stats, eps,
-                      sums, dgamma, dbeta))
-    return rc;
-  if (!dz) return SFA_OK;
-  const int total = s.npix_out * s.cout;
-  return launch({dim3((unsigned)ceil_div(total, 256)), dim3(256), st}, bn_bwd_apply_kernel, g, gm, z, stats, gamma,
-                (const double*)sums, eps, s.npix_out, total, s.cout, dz);
+  return launch_bn_train_backward(sb, g, gm, z, stats, gamma, eps, rpart, sums, dgamma, dbeta, dz, st);
 }
 
 }  // namespace
+
+int sfa::launch_bn_train_stats(const GradBias& sb, const float* z, const float* gamma, const float* beta, double eps,
+                               double* spart, float* stats, float* coef, hipStream_t st) {
+  const unsigned cy = (unsigned)ceil_div(sb.cout, 256);
+  if (int rc = launch({dim3((unsigned)sb.blocks, cy), dim3(256), st}, bn_stats_kernel, z, spart, sb.npix, sb.pixels,
+                      sb.cout))
+    return rc;
+  return launch({dim3(cy), dim3(256), st}, bn_stats_fold_kernel, (const double*)spart, sb.blocks, sb.cout, sb.npix, gamma,
+                beta, eps, stats, coef);
+}
+
+int sfa::launch_bn_train_apply(int npix, int cout, const float* z, const float* coef, const float* x, const float* zd,
+                               const float* cd, float* out, hipStream_t st) {
+  const int quads = npix * cout / 4;
+  return launch({dim3((unsigned)ceil_div(quads, 256)), dim3(256), st}, bn_apply_kernel, z, coef, x, zd, cd, out, quads,
+                cout);
+}
+
+int sfa::launch_bn_train_backward(const GradBias& sb, const float* g, const float* gm, const float* z,
+                                  const float* stats, const float* gamma, double eps, double* rpart, double* sums,
+                                  float* dgamma, float* dbeta, float* dz, hipStream_t st) {
+  const unsigned cy = (unsigned)ceil_div(sb.cout, 256);
+  if (int rc = launch({dim3((unsigned)sb.blocks, cy), dim3(256), st}, bn_bwd_reduce_kernel, g, gm, z, stats, rpart,
+                      sb.npix, sb.pixels, sb.cout))
+    return rc;
+  if (int rc = launch({dim3(cy), dim3(256), st}, bn_bwd_fold_kernel, (const double*)rpart, sb.blocks, sb.cout, stats, eps,
+                      sums, dgamma, dbeta))
+    return rc;
+  if (!dz) return SFA_OK;
+  const int total = sb.npix * sb.cout;
+  return launch({dim3((unsigned)ceil_div(total, 256)), dim3(256), st}, bn_bwd_apply_kernel, g, gm, z, stats, gamma,
+                (const double*)sums, eps, sb.npix, total, sb.cout, dz);
+}
 
 extern "C" size_t sfa_block_train_forward_workspace_size(int layer, int block, int B, int h, int w,
                                                          int max_chunk_pixels) {

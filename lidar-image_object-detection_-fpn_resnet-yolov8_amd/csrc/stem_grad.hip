@@ -14,6 +14,7 @@
 #include "conv.h"
 #include "dispatch.h"
 #include "grad_host.h"
+#include "stem_grad_host.h"
 #include "stem_grad_kernel.h"
 
 using namespace sfa;
@@ -28,6 +29,25 @@ int stem_level(const char* who, const sfa_model* model, StemLevel* sl) {
 }
 
 }  // namespace
+
+int sfa::launch_stem_pool_adjoint(const StemShape& s, const float* a, const float* gp, float* dA, hipStream_t st) {
+  return launch({dim3((unsigned)ceil_div(s.npix_a, 16)), dim3(256), st}, stem_pool_adjoint_kernel, a, gp, dA, s.oh, s.ow,
+                s.ph, s.pw, s.npix_a);
+}
+
+int sfa::launch_stem_wgrad(const BlockWgrad& g, const StemShape& s, const float* gr, const float* x, float* part,
+                           float* dW, hipStream_t st) {
+  if (int rc = launch({dim3((unsigned)g.chunks, (unsigned)kSgColTiles), dim3(256), st}, stem_wgrad_kernel, gr, x, part,
+                      s.H, s.W, s.oh, s.ow, s.npix_a, g.Kc))
+    return rc;
+  return launch_wgrad_fold(part, g.chunks, kSgC, kSgK, 1, dW, kSgK, 0, st);
+}
+
+int sfa::launch_stem_dgrad(const StemShape& s, const float* gr, const float* Wp, int ldw, float* dx, hipStream_t st) {
+  const int passes = ceil_div(s.npix_x, kSgDgradPixels);
+  return launch({dim3((unsigned)(passes < kSgDgradMaxBlocks ? passes : kSgDgradMaxBlocks)), dim3(256), st},
+                stem_dgrad_kernel, gr, Wp, ldw, dx, s.H, s.W, s.oh, s.ow, s.npix_x);
+}
 
 extern "C" size_t sfa_model_stem_forward_workspace_size(const sfa_model* model, int B, int H, int W) {
   StemLevel sl;
@@ -133,19 +153,11 @@ extern "C" int sfa_model_stem_grad(const sfa_model* model, const float* x, const
   double* bpart = reinterpret_cast<double*>(ws + plan.off_bpart);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
-  if (int rc = launch({dim3((unsigned)ceil_div(s.npix_a, 16)), dim3(256), st}, stem_pool_adjoint_kernel, a, gp, dA, s.oh,
-                      s.ow, s.ph, s.pw, s.npix_a))
-    return rc;
+  if (int rc = launch_stem_pool_adjoint(s, a, gp, dA, st)) return rc;
   if (db)
     if (int rc = launch_bias_grad(plan.bs, dA, nullptr, bpart, db, st)) return rc;
-  if (dW) {
-    if (int rc = launch({dim3((unsigned)plan.wg.chunks, (unsigned)kSgColTiles), dim3(256), st}, stem_wgrad_kernel, dA, x,
-                        part, H, W, s.oh, s.ow, s.npix_a, plan.wg.Kc))
-      return rc;
-    if (int rc = launch_wgrad_fold(part, plan.wg.chunks, kSgC, kSgK, 1, dW, kSgK, 0, st)) return rc;
-  }
+  if (dW)
+    if (int rc = launch_stem_wgrad(plan.wg, s, dA, x, part, dW, st)) return rc;
   if (!grad_x) return SFA_OK;
-  const int passes = ceil_div(s.npix_x, kSgDgradPixels);
-  return launch({dim3((unsigned)(passes < kSgDgradMaxBlocks ? passes : kSgDgradMaxBlocks)), dim3(256), st},
-                stem_dgrad_kernel, dA, sl.w, sl.K, grad_x, H, W, s.oh, s.ow, s.npix_x);
+  return launch_stem_dgrad(s, dA, sl.w, sl.K, grad_x, st);
 }

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from sfa_hip import _lib
 from sfa_hip import dropin as _dropin
 from sfa_hip.runtime import (KfpnEngine, block_train_forward, block_train_grad, bn_unfold_grad, kfpn_combine_grad, kfpn_heads,
-                             device_packable, pack_state_dict, state_entries)
+                             device_packable, pack_state_dict, state_entries, stem_train_forward, stem_train_grad)
 
 BN_MOMENTUM = 0.1
 
@@ -311,6 +311,36 @@ class _StemFromImage(torch.autograd.Function):
         return (None, None, None, dx) + tuple(out)
 
 
+class _StemTrainFromImage(torch.autograd.Function):
+    """The stem in training mode as an operator over the image and conv1.weight, bn1.weight, bn1.bias: forward is
+    sfa_stem_train_forward on the raw parameters, bn1 normalising with the statistics of the batch; backward one
+    sfa_stem_train_grad on the saved x, z, a and statistics, bn1 differentiated through them.  No engine and no host
+    repack.  Returns (pooled, stats); ``stats`` (2, 64), the batch mean and biased variance, is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, eps, x, *params):
+        ps = [p.detach().contiguous() for p in params]
+        with torch.cuda.device(x.device):
+            m = stem_train_forward(x, ps, eps)
+        ctx.eps = eps
+        ctx.save_for_backward(x, m["z"], m["a"], m["stats"], *ps)
+        ctx.mark_non_differentiable(m["stats"])
+        return m["pooled"].permute(0, 3, 1, 2), m["stats"]
+
+    @staticmethod
+    def backward(ctx, gp, _gstats):
+        x, z, a, stats = ctx.saved_tensors[:4]
+        ps = list(ctx.saved_tensors[4:])
+        need = ctx.needs_input_grad
+        if not any(need[1:]):
+            return (None,) * len(need)
+        with torch.cuda.device(x.device):
+            B, oh, ow, _ = a.shape
+            g = _nhwc_grad(gp, (B, -(-oh // 2), -(-ow // 2), 64), x.device)
+            dx, dp = stem_train_grad(x, dict(z=z, a=a, stats=stats), g, ps, ctx.eps, want_x=need[1], want_params=need[2:5])
+        return (None, dx) + tuple(dp)
+
+
 class _TrainableNeckForward(torch.autograd.Function):
     """PoseResNet.forward with the 6 neck and the 60 head parameters as differentiable inputs (neck_trainable()):
     _TrainableHeadsForward one stage deeper (_trainable_backward with the neck's part).  The input image and the
@@ -372,6 +402,7 @@ class PoseResNet(nn.Module):
         self._heads_trainable = False
         self._neck_trainable = False
         self._backbone_trainable = False
+        self._backbone_batch_stats = False
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
@@ -637,7 +668,7 @@ class PoseResNet(nn.Module):
         self._no_neck("stem_parameters")
         return [self.conv1.weight, self.bn1.weight, self.bn1.bias]
 
-    def stem_from_image(self, x):
+    def stem_from_image(self, x, batch_stats=False, update_running=True):
         """The stem (models/fpn_resnet.py:179-182: conv1, bn1, ReLU, max-pool) on a caller's image ``x``, a (B, 3, H, W)
         float32 GPU tensor: returns the pooled map (B, 64, ceil(H / 4), ceil(W / 4)) as channels-last bytes.  BatchNorm
         uses its running statistics whatever ``.training`` says, folded into conv1, exactly as :meth:`forward` does; the
@@ -645,34 +676,65 @@ class PoseResNet(nn.Module):
         :meth:`stem_parameters` (sfa_model_stem_forward; sfa_model_stem_grad and sfa_bn_unfold_grad in backward);
         parameters that do not require grad get None, and the image gradient is computed only when ``x`` requires
         grad.  x and the ReLU map are saved for backward.  The plain resnet family (models/resnet.py) refuses this
-        method although the C entries accept its handles."""
+        method although the C entries accept its handles.
+
+        ``batch_stats=True`` is the stem under ``model.train()`` instead: bn1 normalises with the mean and biased
+        variance of the batch and is differentiated through them (sfa_stem_train_forward / sfa_stem_train_grad on the
+        raw parameters, conv1 in float32; the engine is not called, nothing is repacked on the host; B oh ow must be at
+        least 2).  After the forward ``bn1.running_mean``, ``running_var`` (unbiased, n / (n - 1)) and
+        ``num_batches_tracked`` move exactly as ``nn.BatchNorm2d`` moves them in ``train()``, under ``no_grad``, unless
+        ``update_running`` is False."""
         self._no_neck("stem_from_image")
         if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
             raise _lib.SfaNativeError("PoseResNet.stem_from_image runs on the GPU (HIP) only")
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError(f"stem_from_image: expected (B, 3, H, W), got {tuple(x.shape)}")
+        if batch_stats:
+            return self._stem_train(x, update_running)
         eng = self._engine(x.device)
         x = x.float().contiguous()
         return _StemFromImage.apply(eng, self.conv1, self.bn1, x, *self.stem_parameters())
 
-    def detect_from_image(self, x):
+    def _stem_train(self, x, update_running):
+        bn = self.bn1
+        x = x.float().contiguous()
+        pooled, stats = _StemTrainFromImage.apply(float(bn.eps), x, *self.stem_parameters())
+        if update_running and bn.running_mean is not None:
+            n = x.shape[0] * (-(-x.shape[2] // 2)) * (-(-x.shape[3] // 2))
+            with torch.no_grad():
+                bn.num_batches_tracked += 1
+                m = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else float(bn.momentum)
+                bn.running_mean.mul_(1.0 - m).add_(stats[0], alpha=m)
+                bn.running_var.mul_(1.0 - m).add_(stats[1], alpha=m * n / (n - 1))
+        return pooled
+
+    def detect_from_image(self, x, batch_stats=False, update_running=True):
         """:meth:`detect_from_pooled` of :meth:`stem_from_image`: the whole detector through the differentiable
         operators on an image (B, 3, H, W), H and W multiples of 32.  The five maps carry a grad_fn reaching ``x`` (when
-        it requires grad) and all 126 parameters."""
+        it requires grad) and all 126 parameters.  ``batch_stats=True`` runs all 20 BatchNorms (bn1 and the eight
+        blocks') on batch statistics and moves their running buffers (``update_running``), as the reference's
+        ``model.train()`` forward does."""
         if isinstance(x, torch.Tensor) and x.dim() == 4 and (x.shape[2] % 32 or x.shape[3] % 32):
             raise ValueError(f"detect_from_image: H and W must be multiples of 32, got {tuple(x.shape)}")
+        if batch_stats:
+            return self.detect_from_pooled(self.stem_from_image(x, batch_stats=True, update_running=update_running),
+                                           batch_stats=True, update_running=update_running)
         return self.detect_from_pooled(self.stem_from_image(x))
 
-    def backbone_trainable(self, flag=True):
+    def backbone_trainable(self, flag=True, batch_stats=False):
         """Training of the whole detector: the deepest of the three trainable modes, it wins over
         :meth:`neck_trainable` and :meth:`heads_trainable`.  On, with grad mode enabled, ``forward(x)`` returns
         :meth:`detect_from_image` of ``x``: five maps whose backward leaves ``.grad`` at all 126 parameters that require
         grad and at ``x`` when it does.  These maps are the operators' (fp16x3 stem and blocks, float32 MFMA neck,
         saved activations), so they equal the fused forward only within the per-stage gate and not bit for bit.  The
         flipped input layout is refused in this mode, and BatchNorm stays folded with its running statistics.  Off, or
-        under ``no_grad``, forward is exactly what it is without this mode.  Returns self."""
+        under ``no_grad``, forward is exactly what it is without this mode.  ``batch_stats=True`` makes that forward
+        ``detect_from_image(x, batch_stats=True)`` instead: all 20 BatchNorms on batch statistics with their running
+        buffers moving, one training step as the reference's ``model.train()`` runs it (``.train()`` / ``.eval()``
+        themselves change nothing here).  Returns self."""
         self._no_neck("backbone_trainable")
         self._backbone_trainable = bool(flag)
+        self._backbone_batch_stats = bool(flag) and bool(batch_stats)
         return self
 
     def forward_layout(self, x, in_layout):
@@ -688,7 +750,7 @@ class PoseResNet(nn.Module):
         if self._backbone_trainable and torch.is_grad_enabled():
             if in_layout != _lib.IN_NCHW3:
                 raise ValueError("backbone_trainable: the flipped input layout is not differentiated; flip the image")
-            res = self.detect_from_image(x)
+            res = self.detect_from_image(x, batch_stats=True) if self._backbone_batch_stats else self.detect_from_image(x)
             self.kfpn_features, self.fpn_outputs = [], {}
             self.kfpn_weights, self.backbone_features = {}, {}
             return res

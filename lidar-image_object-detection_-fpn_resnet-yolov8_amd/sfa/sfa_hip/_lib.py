@@ -277,6 +277,14 @@ _PROTOS["sfa_model_stem_forward"] = (_c_int, [_vp, _vp] + [_c_int] * 3 + [_vp, _
 _PROTOS["sfa_model_stem_grad_workspace_size"] = (_c_size, [_vp] + [_c_int] * 4)
 _PROTOS["sfa_model_stem_grad_chunk_pixels"] = (_c_int, [_vp] + [_c_int] * 4)
 _PROTOS["sfa_model_stem_grad"] = (_c_int, [_vp] * 4 + [_c_int] * 3 + [_vp, ctypes.POINTER(_vp), _c_int, _vp, _c_size, _vp])
+# the stem in training mode (batch statistics): no handle, raw float32 parameters in
+_PROTOS["sfa_stem_train_forward_workspace_size"] = (_c_size, [_c_int] * 4)
+_PROTOS["sfa_stem_train_grad_workspace_size"] = (_c_size, [_c_int] * 4)
+_PROTOS["sfa_stem_train_chunk_pixels"] = (_c_int, [_c_int] * 5)
+_PROTOS["sfa_stem_train_forward"] = (_c_int, [_vp, ctypes.POINTER(_vp), ctypes.c_double] + [_c_int] * 3 + [_vp] * 4
+                                     + [_c_int, _vp, _c_size, _vp])
+_PROTOS["sfa_stem_train_grad"] = (_c_int, [_vp] * 5 + [ctypes.POINTER(_vp), ctypes.c_double] + [_c_int] * 3
+                                  + [_vp, ctypes.POINTER(_vp), _c_int, _vp, _c_size, _vp])
 HEADS_LEVEL_CIN = (256, 128, 64)  # input channels of KFPN level 0, 1, 2 (SFA_BUF_UP_LEVEL2 / 3 / 4)
 NECK_LAYER_C = (64, 128, 256, 512)  # channels of out_layer1..4, at (8, 4, 2, 1) x (h4, w4)
 NECK_PARAM_SHAPES = ((256, 768, 1, 1), (256,), (128, 384, 1, 1), (128,), (64, 192, 1, 1), (64,))  # conv_up_level1..3

@@ -1948,6 +1948,93 @@ def block_train_grad(layer: int, block: int, x, maps: dict, gy, params, eps: flo
     return res[0], res[1:]
 
 
+# ------------------------------------------------- the stem in training mode (batch statistics): no engine
+_STEM_TRAIN_PARAM_SHAPES = ((64, 3, 7, 7), (64,), (64,))
+
+
+def _stem_train_dims(what, x, params):
+    x = _require_gpu_tensor(x, f"{what} x")
+    if x.dim() != 4 or int(x.shape[1]) != 3:
+        raise ValueError(f"{what} x: {tuple(x.shape)} is not the NCHW (B, 3, H, W)")
+    B, _, H, W = (int(v) for v in x.shape)
+    params = list(params)
+    if len(params) != 3:
+        raise ValueError(f"{what}: the stem takes 3 parameters, got {len(params)}")
+    ps = []
+    for i, (t, sh) in enumerate(zip(params, _STEM_TRAIN_PARAM_SHAPES)):
+        t = _require_gpu_tensor(t, f"{what} params[{i}]").detach()
+        if tuple(t.shape) != sh or not t.is_contiguous():
+            raise ValueError(f"{what} params[{i}]: a contiguous tensor of shape {sh} is needed, got {tuple(t.shape)}")
+        ps.append(t)
+    return x, B, H, W, ps
+
+
+def stem_train_forward_workspace_bytes(B, H, W, max_chunk_pixels: int = 0) -> int:
+    return int(lib().sfa_stem_train_forward_workspace_size(B, H, W, int(max_chunk_pixels)))
+
+
+def stem_train_grad_workspace_bytes(B, H, W, max_chunk_pixels: int = 0) -> int:
+    return int(lib().sfa_stem_train_grad_workspace_size(B, H, W, int(max_chunk_pixels)))
+
+
+def stem_train_chunk_pixels(which: int, B, H, W, max_chunk_pixels: int = 0) -> int:
+    """K_c of dW (which = 0) in :func:`stem_train_grad`, or the pixels of one statistics block (1); 0 for what the
+    entries refuse."""
+    return int(lib().sfa_stem_train_chunk_pixels(int(which), B, H, W, int(max_chunk_pixels)))
+
+
+def stem_train_forward(x: torch.Tensor, params, eps: float = 1e-5, out: dict = None, max_chunk_pixels: int = 0,
+                       workspace: torch.Tensor = None) -> dict:
+    """The stem in training mode (sfa_stem_train_forward) on a caller's ``x``, float32 NCHW (B, 3, H, W) on the GPU:
+    bn1 normalises with the statistics of the batch.  ``params``: conv1.weight, bn1.weight, bn1.bias, raw contiguous
+    float32 GPU tensors in torch's shapes (no engine, no host repack).  Returns {z, a, pooled, stats}: the NHWC maps
+    (B, oh, ow, 64) of the raw convolution and of the ReLU, its max-pool (B, ph, pw, 64), and ``stats`` (2, 64), the
+    batch mean and biased variance.  ``out`` (the same keys) receives them instead; with ``out`` and ``workspace``
+    given the call only enqueues its launches."""
+    what = "stem_train_forward"
+    x, B, H, W, ps = _stem_train_dims(what, x, params)
+    ash, psh = KfpnEngine.stem_shapes(B, H, W)
+    names = ["z", "a", "pooled", "stats"]
+    bufs = dict(zip(names, _kfpn_buffers(out, names, [ash, ash, psh, (2, 64)], x, f"{what} out")))
+    workspace = _workspace(what, f"B={B}, H={H}, W={W}", stem_train_forward_workspace_bytes(B, H, W, max_chunk_pixels),
+                           workspace, x.device)
+    with torch.cuda.device(x.device):
+        check(lib().sfa_stem_train_forward(x.data_ptr(), _ptr_array(ps), float(eps), B, H, W, bufs["z"].data_ptr(),
+                                           bufs["a"].data_ptr(), bufs["pooled"].data_ptr(), bufs["stats"].data_ptr(),
+                                           int(max_chunk_pixels), workspace.data_ptr(), workspace.numel(),
+                                           _lib.stream_ptr(x.device)), "sfa_stem_train_forward")
+    return bufs
+
+
+def stem_train_grad(x, maps: dict, gp, params, eps: float = 1e-5, want_x: bool = True, want_params=(True, True, True),
+                    out=None, max_chunk_pixels: int = 0, workspace: torch.Tensor = None):
+    """The gradients of the stem in training mode (sfa_stem_train_grad), bn1 differentiated through its batch
+    statistics, from ``gp`` = d total / d pooled (NHWC), ``x`` and ``maps`` = what :func:`stem_train_forward` returned
+    (z, a and stats are read).  Returns (dx, [dW, dgamma, dbeta]) in torch's shapes, None where not wanted; every
+    element of a wanted output is written.  ``out`` = (tensor or None, 3 tensors or Nones) receives them instead of
+    fresh tensors.  With ``out`` and ``workspace`` given the call only enqueues its launches."""
+    what = "stem_train_grad"
+    x, B, H, W, ps = _stem_train_dims(what, x, params)
+    ash, psh = KfpnEngine.stem_shapes(B, H, W)
+    ms = []
+    for t, n, s in ((maps["z"], "z", ash), (maps["a"], "a", ash), (gp, "gp", psh), (maps["stats"], "stats", (2, 64))):
+        t = _require_gpu_tensor(t, f"{what} {n}")
+        if tuple(t.shape) != s:
+            raise ValueError(f"{what} {n}: {tuple(t.shape)} is not the {s} the forward wrote")
+        ms.append(t)
+    want = [bool(want_x)] + [bool(v) for v in list(want_params)[:3]]
+    want += [False] * (4 - len(want))
+    shapes = [(B, 3, H, W)] + list(_STEM_TRAIN_PARAM_SHAPES)
+    res = _grad_outputs(what, want, shapes, out and ([out[0]] + list(out[1])), x)
+    workspace = _workspace(what, f"B={B}, H={H}, W={W}", stem_train_grad_workspace_bytes(B, H, W, max_chunk_pixels),
+                           workspace, x.device)
+    with torch.cuda.device(x.device):
+        check(lib().sfa_stem_train_grad(x.data_ptr(), *(t.data_ptr() for t in ms), _ptr_array(ps), float(eps), B, H, W,
+                                        _opt_ptr(res[0]), _dparams(res[1:]), int(max_chunk_pixels), workspace.data_ptr(),
+                                        workspace.numel(), _lib.stream_ptr(x.device)), "sfa_stem_train_grad")
+    return res[0], res[1:]
+
+
 def _kfpn_operands(levels_by_head: dict, level0_half: bool, what: str):
     """Checks {head: [level 0, level 1, level 2]}: (names, flat contiguous tensors, channels, (B, h, w))."""
     if not isinstance(levels_by_head, dict) or not 1 <= len(levels_by_head) <= _lib.SFA_MAX_HEADS:

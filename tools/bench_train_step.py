@@ -32,7 +32,16 @@ channel), dW' 64 x 192 per conv pixel (147 columns padded to three tiles), dx 3 
   + KfpnEngine(...) + one synchronise, the median of 5.  weight_update_eager_us = the device route eager, as a step
   loop pays it: _engine() after an in-place change plus one synchronise, weight_update_eager_host_us its part until the
   call returns (the pointer table, the argument checks, the launches), the median of 5.  The train step is followed by torch.optim.Adam's step (lr 1e-3,
-  no weight decay) and the next forward's _engine(), wall-clock with a synchronise each, as fields of their own."""
+  no weight decay) and the next forward's _engine(), wall-clock with a synchronise each, as fields of their own.
+
+  --stem-train adds the training-mode stem (sfa_stem_train_forward / sfa_stem_train_grad, bn1 on batch statistics,
+  conv1 in float32) from the same job, each the median of 50 graph replays, and ``train_step_batch_stats_us``: the
+  train step once more with backbone_trainable(batch_stats=True).  Traffic, X = x as NCHW3, A = one (npix_a, 64) map,
+  P = the pooled map:
+    forward   conv (X read, z written), statistics (z), apply (z read, a written), pool (a read, P written)
+    gradient  dY (a, gp read, dY written), the reduce (dY, z), the apply (dY, z read, dZ written), dW (dZ, X + partials
+              written and read), dx (dZ read, dx written)
+  Arithmetic: forward 64 x 160 per conv pixel (the 147 entries padded to ten steps), dW and dx as above."""
 import json
 import os
 import sys
@@ -50,12 +59,12 @@ from sfa_hip import _lib, runtime, synthetic  # noqa: E402
 B, H = 16, 608
 
 
-def train_step_us(gpu, sd, batch):
+def train_step_us(gpu, sd, batch, batch_stats=False):
     from losses.losses import Compute_Loss
     from models.fpn_resnet import get_pose_net
     m = get_pose_net(18, dict(runtime.DEFAULT_HEADS), 64, False)
     m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
-    m = m.to(gpu).eval().backbone_trainable()
+    m = m.to(gpu).eval().backbone_trainable(batch_stats=batch_stats)
     x = torch.from_numpy(synthetic.synthetic_bev(batch, H, H, seed=3)).to(gpu)
     labels, offsets = synthetic.synthetic_labels(batch, seed=2)
     tg = runtime.TargetBuilder(gpu, hm_size=(H // 4, H // 4))(labels, offsets)
@@ -213,6 +222,25 @@ def main():
            "stem_grad_flops_us": us(wflops + xflops, MFMA_F32_FLOPS),
            "stem_grad_without_dx_us": round(grad_nodx, 1), "stem_grad_without_dx_traffic_us": us(g_nodx, copy_rate),
            "stem_grad_without_dx_mfma_f32_us": us(wflops, MFMA_F32_FLOPS), "dx_us": round(grad - grad_nodx, 1)}
+    if "--stem-train" in sys.argv:
+        ps = [torch.from_numpy(np.asarray(sd[k])).to(gpu) for k in ("conv1.weight", "bn1.weight", "bn1.bias")]
+        tf = torch.empty(runtime.stem_train_forward_workspace_bytes(B, H, H), dtype=torch.uint8, device=gpu)
+        tg = torch.empty(runtime.stem_train_grad_workspace_bytes(B, H, H), dtype=torch.uint8, device=gpu)
+        tm = runtime.stem_train_forward(x, ps)
+        tdx, tdp = runtime.stem_train_grad(x, tm, gp, ps)
+        t_fwd = replay_us(lambda: runtime.stem_train_forward(x, ps, out=tm, workspace=tf), gpu)
+        t_grad = replay_us(lambda: runtime.stem_train_grad(x, tm, gp, ps, out=(tdx, tdp), workspace=tg), gpu)
+        t_nodx = replay_us(lambda: runtime.stem_train_grad(x, tm, gp, ps, want_x=False, out=(None, tdp), workspace=tg), gpu)
+        tchunks = -(-na // runtime.stem_train_chunk_pixels(0, B, H, H))
+        tfb = (X3 + A) + A + 2 * A + (A + P)
+        tg_nodx = (A + P + A) + 2 * A + 3 * A + (A + X3 + 2 * tchunks * 64 * 147 * 4)
+        out.update({"stem_train_forward_us": round(t_fwd, 1), "stem_train_forward_traffic_us": us(tfb, copy_rate),
+                    "stem_train_forward_mfma_f32_us": us(2 * na * 64 * 160, MFMA_F32_FLOPS),
+                    "stem_train_grad_us": round(t_grad, 1), "stem_train_grad_traffic_us": us(tg_nodx + A + X3, copy_rate),
+                    "stem_train_grad_flops_us": us(wflops + xflops, MFMA_F32_FLOPS),
+                    "stem_train_grad_without_dx_us": round(t_nodx, 1),
+                    "stem_train_grad_without_dx_traffic_us": us(tg_nodx, copy_rate)})
+        del ps, tf, tg, tm, tdx, tdp
     del x, a, pooled, gp, dx, dp, fws, gws
     if "--blocks" in sys.argv:
         out["blocks"] = block_rows(gpu, eng, copy_rate)
@@ -222,6 +250,9 @@ def main():
         try:
             step, opt_us, eng_us = train_step_us(gpu, sd, batch)
             out["train_step_us"], out["optimizer_step_us"], out["engine_update_us"] = round(step, 1), round(opt_us, 1), round(eng_us, 1)
+            if "--stem-train" in sys.argv:
+                torch.cuda.empty_cache()
+                out["train_step_batch_stats_us"] = round(train_step_us(gpu, sd, batch, batch_stats=True)[0], 1)
             break
         except torch.cuda.OutOfMemoryError:
             batch //= 2
